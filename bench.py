@@ -16,16 +16,24 @@ others' (what the speculative binning's capacity prediction has to survive; `spe
 often it did not).  For N>1 every rank walks its OWN views of the replicated Gaussians (weak scaling) and the
 step ends with the RCCL exchange of the parameter gradients.  Inputs are resident in HBM before the timed region.
 
-Order of a run: W warm-up steps (per-stage event timing -> `stages_ms`), fence, untimed repetitions of the step for `--settle-ms`
-(default 40 ms; reported as `settle`: the GPU's clock settles only after ~20 ms of continuous work, 0 turns it off), fence
-(barrier + synchronize), EXACTLY K timed steps, fence.  `step_gpu_span_ms` carries every timed step's GPU span in order.
+Order of a run: W warm-up steps, fence, untimed repetitions of the step for `--settle-ms` (default 40 ms; reported as `settle`: the
+GPU's clock settles only after ~20 ms of continuous work, 0 turns it off), fence (barrier + synchronize), EXACTLY K timed steps
+(always starting from view 0 of the rank's stream, so that the same arguments give the same inputs), fence.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run measures the headline only: `metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` (wall clock of the K timed steps / K) and the workload description.
+`--dump-outputs DIR` writes what the last timed step returned to its caller (forward maps, radii, num_rendered, gradients) as
+DIR/<name>.npy in float32 (num_rendered: float64); arrays over Gaussians or pixels larger than DUMP_ITEMS rows are reduced to a fixed,
+seeded sample of DUMP_ITEMS rows, so two builds can be compared output for output.
+`--full` adds everything else, as extra objects on the same line:
+  stages_ms     per-stage event timing of the warm-up steps
   roofline      dominant kernel: algorithmic bytes per launch / its average
                 launch duration, measured with HIP events recorded by the library on the launch stream
-                during the timed region
+                during the timed region; also path_roofline, pairs, valu_roofline, stage_bytes_moved, device_memory
+  step_gpu_span_ms  every timed step's GPU span in order
   cpu_baseline  the CPU oracle (oracle/, a port of the reference algorithm) timed on this box's host
                 cores on the same workload -- a reported baseline, not the target
+  other_configs, train_iter_ms  child runs of the other BASELINE configs and of one full training iteration (C2 only)
 """
 import argparse
 import json
@@ -41,6 +49,8 @@ import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
+DUMP_ITEMS = 1 << 17   # --dump-outputs: rows kept per array (C2: 15 maps + 72 floats per Gaussian at 2^17 rows = 46 MB)
+DUMP_MAX_BYTES = 64 << 20
 # VALU issue peak in wave64 instructions: 256 CUs x 4 SIMDs x 2.4 GHz, one instruction every 2 cycles per SIMD (same guide: "issues each
 # VALU instruction over 2 cycles"; 157.3 TFLOP/s fp32 = this x 64 lanes x 2 flop)
 VALU_PEAK_GINST = 256 * 4 * 2.4 / 2.3   # 1 024 SIMDs, 2.4 GHz, 2.3 cycles per full-rate wave64 instruction (profiles/r06_valu_calibration.txt)
@@ -92,9 +102,14 @@ def main():
     ap.add_argument("--mode", choices=("train", "forward"), default="train",
                     help="'forward': the step is the forward alone under no_grad -- what the reference's inference callers execute "
                          "(render.py:32, mesh_extract.py:56: render() with both maps on; use with --flags both); metric Mimages/s")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline: per-stage and roofline figures, step spans, device memory, the CPU "
+                         "baseline, the other configs and the training iteration (the two --no-* options below trim this)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (seeded sample of large arrays)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the legs that run AFTER (outside) the timed region at N=1 on the headline config: one short bench line each for "
+                    help="with --full: skip the legs that run AFTER (outside) the timed region at N=1 on the headline config: one short bench line each for "
                          "the other BASELINE configs with a GPU (C3, C4, C5 -> `other_configs`) and one full training iteration (`train_iter_ms`)")
     ap.add_argument("--force-allreduce", action="store_true", help="run the RCCL gradient exchange even at world size 1 (path check)")
     ap.add_argument("--exchange", choices=("factored", "allreduce"), default="factored",
@@ -155,7 +170,9 @@ def main():
     last_state = []
     STAGES4 = ("preprocess_fwd", "blend_fwd") if args.mode == "forward" else ("preprocess_fwd", "blend_fwd", "blend_bwd", "preprocess_bwd")
 
-    def step():
+    kept = {}   # --dump-outputs: what the last timed step returned to its caller
+
+    def step(keep=False):
         vm, pm, cp = cams[counter[0] % nviews]
         counter[0] += 1
         if bucket is not None and args.exchange == "factored":
@@ -165,6 +182,9 @@ def main():
                                    s.require_depth, False)
         R, color, coord, mcoord, alpha, normal, depth, mdepth, radii, geom, binning, img = fw
         last_state[:] = [R, geom, binning, img]
+        if keep:
+            kept.update(num_rendered=R, color=color, coord=coord, mcoord=mcoord, alpha=alpha, normal=normal, depth=depth, mdepth=mdepth,
+                        radii=radii)
         if args.mode == "forward":
             return R, radii, None
         bw = C.rasterize_gaussians_backward(s.bg, s.means3D, radii, e, s.scales, s.rotations, 1.0, e, vm, pm,
@@ -175,6 +195,10 @@ def main():
         last_state[:] = [R, geom, binning, img]
         if bucket is not None:  # the one exchange step of the path (RCCL over xGMI)
             grads = bucket.exchange(s.means3D, cp, average=True) if args.exchange == "factored" else bucket.allreduce(average=True)
+        if keep:
+            kept.update(zip(("dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dscales", "dL_drotations"), bw))
+            if bucket is not None:   # the exchanged (averaged) gradients are what the caller receives
+                kept.update(grads)
         return R, radii, grads
 
     def fence():
@@ -182,9 +206,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    # Warm-up: the per-stage breakdown (`stages_ms`) is measured HERE, with an event pair around every stage.  Each recorded
+    # Warm-up: with --full the per-stage breakdown (`stages_ms`) is measured HERE, with an event pair around every stage.  Each recorded
     # stage boundary costs ~10 us of stream bubble (10 stages = ~0.1 ms per step), so the timed steps below record events
-    # around the dominant kernel only -- the one the roofline object reports, live, inside the timed region.
+    # around the dominant kernel only -- the one the roofline object reports, live, inside the timed region.  A plain run records none.
     # Python's cyclic collector is emptied HERE -- before the warm-up, not between the warm-up and the timed region -- and held off until
     # the timed region ends: a generation-2 pass over a torch process's ~1 M objects is a 5-30 ms host stall (seen as ONE step of 6 / 30 /
     # 31 ms on C2 / C4 / C5 lines of round 6 whose median span was 1.41 / 4.09 / 7.71).  Emptying it right before the timed region (the
@@ -197,20 +221,22 @@ def main():
     gc.disable()
     # one event per step boundary on the launch stream (~2 us each, no bubble: nothing waits on them): the spans between them say what a
     # step costs on the GPU, so that a host stalled by a neighbour (the boxes' hosts are shared) shows up as wall >> median span
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)] if args.full else []
     if args.warmup > 1:  # first call: allocator growth, code-object load -- keep it out of the per-stage averages
         R, radii, _ = step()
         fence()
-    C.profile_collect()
-    C.profile_enable(True)
+    if args.full:
+        C.profile_collect()
+        C.profile_enable(True)
     for _ in range(args.warmup - 1 if args.warmup > 1 else args.warmup):
         R, radii, _ = step()
     fence()
-    C.profile_enable(False)
-    stages_warm = C.profile_collect()
     dom = None
-    if args.warmup > 0:
-        dom = max(STAGES4, key=lambda k: stages_warm[k][0] / max(stages_warm[k][1], 1))
+    if args.full:
+        C.profile_enable(False)
+        stages_warm = C.profile_collect()
+        if args.warmup > 0:
+            dom = max(STAGES4, key=lambda k: stages_warm[k][0] / max(stages_warm[k][1], 1))
     # Clock settling (disclosed on the line as `settle`): after an idle period the GPU reaches its sustained clock only after ~20 ms of
     # continuous work -- with `--views 1` as with rotating views the first ~15 steps after the warm-up's fence run 10 % slow and decay
     # smoothly (`step_gpu_span_ms.in_step_order` of a run with --settle-ms 0: 1.42 1.37 1.41 1.38 1.36 ... 1.29), and W = 5 warm-up steps
@@ -236,38 +262,49 @@ def main():
             R, radii, _ = step()
         fence()
         settle_ms_per_step = (time.perf_counter() - t_s) * 1e3 / n_settle   # what these steps -- the first after the warm-up -- took
-    # the dominant kernel is timed live on every 2nd step of the timed region (the event pair around it is a ~12 us stream bubble;
-    # every 2nd step of a 9-view rotation still visits every view)
-    C.profile_enable(True, only=dom, every=2 if (dom is not None and args.steps >= 8) else 1)   # no warm-up steps: every stage, in the timed region
+    # the timed steps always start at view 0: how many settle steps ran depends on the clock, the inputs of the timed steps must not
+    counter[0] = 0
+    if args.full:
+        # the dominant kernel is timed live on every 2nd step of the timed region (the event pair around it is a ~12 us stream bubble;
+        # every 2nd step of a 9-view rotation still visits every view)
+        C.profile_enable(True, only=dom, every=2 if (dom is not None and args.steps >= 8) else 1)   # no warm-up steps: every stage, in the timed region
     if bucket is not None and hasattr(bucket, "collect_timing"):
         bucket.collect_timing()      # drop the warm-up steps' exchange timings
     C.binning_stats(reset=True)
     Rs, vis = [], []
-    torch.cuda.reset_peak_memory_stats(dev)
-    mem_before = torch.cuda.memory_allocated(dev)
+    if args.full:
+        torch.cuda.reset_peak_memory_stats(dev)
+        mem_before = torch.cuda.memory_allocated(dev)
+    dump = args.dump_outputs is not None
     t0 = time.perf_counter()
-    marks[0].record()
+    if args.full:
+        marks[0].record()
     for i in range(args.steps):
-        R, radii, _ = step()
-        marks[i + 1].record()
+        R, radii, _ = step(keep=dump and i == args.steps - 1)
+        if args.full:
+            marks[i + 1].record()
+            vis.append(radii)      # kept alive, counted after the timed region
         Rs.append(R)
-        vis.append(radii)          # kept alive, counted after the timed region
     fence()
     elapsed = time.perf_counter() - t0
     if gc_was_enabled:
         gc.enable()
-    spans = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     xch = bucket.collect_timing() if (bucket is not None and hasattr(bucket, "collect_timing")) else []
-    peak_step_bytes = torch.cuda.max_memory_allocated(dev) - mem_before - sum(r.numel() * 4 for r in vis[:-1])
-    C.profile_enable(False)
     spec_calls, spec_misses = C.binning_stats()
-    timed = C.profile_collect()
-    if dom is None:
-        stages = timed
-        dom = max(STAGES4, key=lambda k: timed[k][0] / max(timed[k][1], 1))
-    else:
-        stages = dict(stages_warm)
-        stages[dom] = timed[dom]
+    if args.full:
+        spans = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
+        peak_step_bytes = torch.cuda.max_memory_allocated(dev) - mem_before - sum(r.numel() * 4 for r in vis[:-1])
+        C.profile_enable(False)
+        timed = C.profile_collect()
+        if dom is None:
+            stages = timed
+            dom = max(STAGES4, key=lambda k: timed[k][0] / max(timed[k][1], 1))
+        else:
+            stages = dict(stages_warm)
+            stages[dom] = timed[dom]
+    if dump and rank == 0:
+        dump_outputs(args.dump_outputs, kept, P, H, W)
+    kept.clear()
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -276,37 +313,8 @@ def main():
     value = world * P / 1e6 / (elapsed / args.steps)
 
     if rank == 0:
-        # algorithmic bytes: per-step averages over the views the timed steps rendered
-        Pv = int(round(sum(int((r > 0).sum().item()) for r in vis) / max(len(vis), 1)))
         R = int(round(sum(Rs) / max(len(Rs), 1)))
         c, d = int(s.require_coord), int(s.require_depth)
-        ab = algorithmic_bytes(P, Pv, R, W * H, s.sh_degree, c, d)
-        # per STEP, not per recorded interval: a stage may be timed in several pieces (block_lists: one kernel before the tile sort,
-        # one after it)
-        nrec = {k: v[1] for k, v in stages.items()}
-        if args.mode == "forward":
-            per_step = max(nrec.get("preprocess_fwd", 0) if dom != "preprocess_fwd" else nrec.get("blend_fwd", 0), 1)
-        else:
-            per_step = max(nrec.get("preprocess_bwd", 0) if dom != "preprocess_bwd" else nrec.get("blend_bwd", 0), 1)
-        ms = {k: (v[0] / (v[1] if k == dom else per_step) if v[1] else 0.0) for k, v in stages.items()}
-        grouped = {"preprocess_fwd": ms["preprocess_fwd"],
-                   "binning": ms["sort_depth"] + ms["scan"] + ms["emit_instances"] + ms["sort_tile"] + ms["tile_ranges"],
-                   "blend_fwd": ms["blend_fwd"] + ms.get("block_lists", 0.0), "blend_bwd": ms["blend_bwd"] + ms["acc_zero"], "preprocess_bwd": ms["preprocess_bwd"]}
-        dom_ms = ms[dom]
-        achieved = ab[dom] / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
-        gpu_ms = sum(grouped.values())
-        kernel_name = {"blend_bwd": "blend_bwd_"}.get(dom, dom + "_")   # prefix of the kernel's name in the rocprof summaries
-        tag = args.config if args.flags == "config" else args.config + "_both"
-        if args.mode == "forward":
-            tag += "_fwd"
-            for k in ("blend_bwd", "preprocess_bwd"):
-                ab["total"] -= ab[k]
-                ab[k] = 0
-        traffic, traffic_note = pmc_traffic(kernel_name, tag, args.config, P, W, H)
-        pairs = pair_evaluations(C, s, last_state, c)
-        streams = pairs["formulation"].startswith("entry streams")
-        bmoved = binning_bytes_moved(P, R, ((W + 15) // 16) * ((H + 15) // 16), streams)
-        valu = valu_roofline(kernel_name, tag, args.config, P, W, H, dom_ms)
         if args.mode == "forward":
             metric, unit, value = f"forward-only Mimages/s, {args.config} (render.py / mesh_extract.py: render() under no_grad)", "Mimages/s", world / 1e6 / (elapsed / args.steps)
         else:
@@ -321,54 +329,87 @@ def main():
                        "parallelism": f"view-parallel x{world}" + ((", RCCL all-reduce of 44 B + all-gather of 12 B/Gaussian/view (SH gradient factored)"
                                                                      if args.exchange == "factored" else ", RCCL all-reduce of 236 B/Gaussian grads")
                                                                     if world > 1 else ""),
-                       "views": nviews, "num_rendered": int(R), "num_rendered_min_max": [int(min(Rs)), int(max(Rs))], "visible": Pv},
+                       "views": nviews, "num_rendered": int(R), "num_rendered_min_max": [int(min(Rs)), int(max(Rs))]},
             "speculation": {"speculative_forwards": spec_calls, "redone": spec_misses,
                             "miss_rate": round(spec_misses / spec_calls, 4) if spec_calls else None},
-            "roofline": {"bound": "hbm", "kernel": kernel_name, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_note,
-                         "algorithmic_bytes_per_launch": int(ab[dom]), "avg_launch_ms": round(dom_ms, 4),
-                         "launches_timed": int(stages[dom][1]), "timed_with": "HIP events on the launch stream, inside the timed region"},
-            "path_roofline": {"algorithmic_bytes_per_view": int(ab["total"]), "gpu_ms_per_view": round(gpu_ms, 4),
-                              "achieved_GBs_gpu_time": round(ab["total"] / (gpu_ms * 1e-3) / 1e9, 1) if gpu_ms > 0 else 0.0,
-                              "achieved_GBs_wall": round(ab["total"] / (ms_per_step * 1e-3) / 1e9, 1),
-                              "frac_wall": round(ab["total"] / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
             "settle": {"untimed_steps": n_settle, "ms": args.settle_ms, "ms_per_step_during_settle": None if settle_ms_per_step is None else round(settle_ms_per_step, 4),
                        "note": "untimed repetitions of the step between the W warm-up steps and the timed region, until the GPU has worked for `ms`: "
                                "its clock settles only after ~20 ms of continuous work (first steps after an idle period run ~10 % slow); "
                                "ms_per_step_during_settle = wall clock of these very steps, i.e. what a line without them would read"},
-            "step_gpu_span_ms": {"median": round(spans[len(spans) // 2], 4), "min": round(spans[0], 4), "max": round(spans[-1], 4), "mean": round(sum(spans) / len(spans), 4), "in_step_order": [round(marks[i].elapsed_time(marks[i + 1]), 3) for i in range(args.steps)],
-                                 "note": "HIP-event spans between consecutive steps on the launch stream; ms_per_step is the wall clock of the whole region / steps; "
-                                         "Python's cyclic GC is collected before and disabled during the timed region (a gen-2 pass is a 5-30 ms host stall)"},
-            "device_memory": {"peak_bytes_of_one_step": int(peak_step_bytes),
-                              "reference_formula_bytes": int(139 * P + 44 * W * H + 24 * R),
-                              "reference_with_outputs_and_gradients_bytes": int(139 * P + 44 * W * H + 24 * R + 60 * W * H + 360 * P),
-                              "note": "peak torch allocation above the resident inputs during the timed steps (state buffers incl. entry-stream capacity, "
-                                      "outputs, accumulators, gradients); reference: 139 B/Gaussian + 44 B/pixel + 24 B/instance of state "
-                                      "(rasterizer_impl.cu:190-250); second figure: plus its 15 output planes (60 B/pixel) and its gradient / per-Gaussian "
-                                      "sum tensors (360 B/Gaussian at SH degree 3, rasterize_points.cu:175-193), still without its sort temp"},
-            "stages_ms": {k: round(v, 4) for k, v in ms.items()},
-            "stages_ms_source": "warm-up steps with an event pair per stage; the roofline kernel is re-timed alone inside the timed steps",
-            "stage_GBs": {k: round(ab[k] / (grouped[k] * 1e-3) / 1e9, 1) if grouped[k] > 0 else 0.0 for k in grouped},
-            # the binning line above divides the REFERENCE algorithm's bytes (6-pass 64-bit sort) by this implementation's time; what the
-            # implementation itself moves is about half of that (binning_bytes_moved)
-            "stage_bytes_moved": stage_bytes_moved(tag, args.config, P, W, H, grouped),
-            "binning_bytes_moved": {"bytes": int(bmoved), "GBs": round(bmoved / (grouped["binning"] * 1e-3) / 1e9, 1) if grouped["binning"] > 0 else 0.0},
-            # the render kernels are gather + ALU bound -- (pixel, list entry) evaluations per second next to their GB/s
-            "pairs": {"formulation": pairs["formulation"], "evaluated_per_pass": pairs["evaluated"], "reference_definition_per_pass": pairs["tilewide"],
-                      "blend_fwd_Gpairs_s": round(pairs["evaluated"] / (ms["blend_fwd"] * 1e-3) / 1e9, 1) if ms["blend_fwd"] > 0 else 0.0,
-                      "blend_bwd_Gpairs_s": round(pairs["evaluated"] / (ms["blend_bwd"] * 1e-3) / 1e9, 1) if ms["blend_bwd"] > 0 else 0.0,
-                      "note": "evaluated = pixel slots the kernels walk in the last view of the run (entry streams: 32 x entries each 8x4 block "
-                              "consumed); reference_definition = 256 x entries each tile's walk reaches (SURVEY 8d)"},
-            "valu_roofline": valu,
         }
+        if args.full:
+            # algorithmic bytes: per-step averages over the views the timed steps rendered
+            Pv = int(round(sum(int((r > 0).sum().item()) for r in vis) / max(len(vis), 1)))
+            ab = algorithmic_bytes(P, Pv, R, W * H, s.sh_degree, c, d)
+            # per STEP, not per recorded interval: a stage may be timed in several pieces (block_lists: one kernel before the tile sort,
+            # one after it)
+            nrec = {k: v[1] for k, v in stages.items()}
+            if args.mode == "forward":
+                per_step = max(nrec.get("preprocess_fwd", 0) if dom != "preprocess_fwd" else nrec.get("blend_fwd", 0), 1)
+            else:
+                per_step = max(nrec.get("preprocess_bwd", 0) if dom != "preprocess_bwd" else nrec.get("blend_bwd", 0), 1)
+            ms = {k: (v[0] / (v[1] if k == dom else per_step) if v[1] else 0.0) for k, v in stages.items()}
+            grouped = {"preprocess_fwd": ms["preprocess_fwd"],
+                       "binning": ms["sort_depth"] + ms["scan"] + ms["emit_instances"] + ms["sort_tile"] + ms["tile_ranges"],
+                       "blend_fwd": ms["blend_fwd"] + ms.get("block_lists", 0.0), "blend_bwd": ms["blend_bwd"] + ms["acc_zero"], "preprocess_bwd": ms["preprocess_bwd"]}
+            dom_ms = ms[dom]
+            achieved = ab[dom] / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+            gpu_ms = sum(grouped.values())
+            kernel_name = {"blend_bwd": "blend_bwd_"}.get(dom, dom + "_")   # prefix of the kernel's name in the rocprof summaries
+            tag = args.config if args.flags == "config" else args.config + "_both"
+            if args.mode == "forward":
+                tag += "_fwd"
+                for k in ("blend_bwd", "preprocess_bwd"):
+                    ab["total"] -= ab[k]
+                    ab[k] = 0
+            traffic, traffic_note = pmc_traffic(kernel_name, tag, args.config, P, W, H)
+            pairs = pair_evaluations(C, s, last_state, c)
+            streams = pairs["formulation"].startswith("entry streams")
+            bmoved = binning_bytes_moved(P, R, ((W + 15) // 16) * ((H + 15) // 16), streams)
+            valu = valu_roofline(kernel_name, tag, args.config, P, W, H, dom_ms)
+            out["config"]["visible"] = Pv
+            out.update({
+                "roofline": {"bound": "hbm", "kernel": kernel_name, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_note,
+                             "algorithmic_bytes_per_launch": int(ab[dom]), "avg_launch_ms": round(dom_ms, 4),
+                             "launches_timed": int(stages[dom][1]), "timed_with": "HIP events on the launch stream, inside the timed region"},
+                "path_roofline": {"algorithmic_bytes_per_view": int(ab["total"]), "gpu_ms_per_view": round(gpu_ms, 4),
+                                  "achieved_GBs_gpu_time": round(ab["total"] / (gpu_ms * 1e-3) / 1e9, 1) if gpu_ms > 0 else 0.0,
+                                  "achieved_GBs_wall": round(ab["total"] / (ms_per_step * 1e-3) / 1e9, 1),
+                                  "frac_wall": round(ab["total"] / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
+                "step_gpu_span_ms": {"median": round(spans[len(spans) // 2], 4), "min": round(spans[0], 4), "max": round(spans[-1], 4), "mean": round(sum(spans) / len(spans), 4), "in_step_order": [round(marks[i].elapsed_time(marks[i + 1]), 3) for i in range(args.steps)],
+                                     "note": "HIP-event spans between consecutive steps on the launch stream; ms_per_step is the wall clock of the whole region / steps; "
+                                             "Python's cyclic GC is collected before and disabled during the timed region (a gen-2 pass is a 5-30 ms host stall)"},
+                "device_memory": {"peak_bytes_of_one_step": int(peak_step_bytes),
+                                  "reference_formula_bytes": int(139 * P + 44 * W * H + 24 * R),
+                                  "reference_with_outputs_and_gradients_bytes": int(139 * P + 44 * W * H + 24 * R + 60 * W * H + 360 * P),
+                                  "note": "peak torch allocation above the resident inputs during the timed steps (state buffers incl. entry-stream capacity, "
+                                          "outputs, accumulators, gradients); reference: 139 B/Gaussian + 44 B/pixel + 24 B/instance of state "
+                                          "(rasterizer_impl.cu:190-250); second figure: plus its 15 output planes (60 B/pixel) and its gradient / per-Gaussian "
+                                          "sum tensors (360 B/Gaussian at SH degree 3, rasterize_points.cu:175-193), still without its sort temp"},
+                "stages_ms": {k: round(v, 4) for k, v in ms.items()},
+                "stages_ms_source": "warm-up steps with an event pair per stage; the roofline kernel is re-timed alone inside the timed steps",
+                "stage_GBs": {k: round(ab[k] / (grouped[k] * 1e-3) / 1e9, 1) if grouped[k] > 0 else 0.0 for k in grouped},
+                # the binning line above divides the REFERENCE algorithm's bytes (6-pass 64-bit sort) by this implementation's time; what the
+                # implementation itself moves is about half of that (binning_bytes_moved)
+                "stage_bytes_moved": stage_bytes_moved(tag, args.config, P, W, H, grouped),
+                "binning_bytes_moved": {"bytes": int(bmoved), "GBs": round(bmoved / (grouped["binning"] * 1e-3) / 1e9, 1) if grouped["binning"] > 0 else 0.0},
+                # the render kernels are gather + ALU bound -- (pixel, list entry) evaluations per second next to their GB/s
+                "pairs": {"formulation": pairs["formulation"], "evaluated_per_pass": pairs["evaluated"], "reference_definition_per_pass": pairs["tilewide"],
+                          "blend_fwd_Gpairs_s": round(pairs["evaluated"] / (ms["blend_fwd"] * 1e-3) / 1e9, 1) if ms["blend_fwd"] > 0 else 0.0,
+                          "blend_bwd_Gpairs_s": round(pairs["evaluated"] / (ms["blend_bwd"] * 1e-3) / 1e9, 1) if ms["blend_bwd"] > 0 else 0.0,
+                          "note": "evaluated = pixel slots the kernels walk in the last view of the run (entry streams: 32 x entries each 8x4 block "
+                                  "consumed); reference_definition = 256 x entries each tile's walk reaches (SURVEY 8d)"},
+                "valu_roofline": valu,
+            })
         if xch:   # N > 1 (or --force-allreduce): what the gradient exchange costs and how much of it the step waits for (view_parallel.py)
             out["exchange_ms"] = round(sum(t[0] for t in xch) / len(xch), 4)
             out["exchange_exposed_ms"] = round(sum(t[1] for t in xch) / len(xch), 4)
             out["exchange_note"] = ("rank 0, mean over the timed steps, GPU clock: exchange_ms = first collective of the step issued (under the "
                                     "backward) -> gradients ready; exchange_exposed_ms = the part after the backward's last kernel was queued")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(scene_cpu, cfg["seed"])
-        if (world == 1 and not launched and not args.no_other_configs and args.config == "C2" and args.flags == "config" and args.mode == "train"
+        if (args.full and world == 1 and not launched and not args.no_other_configs and args.config == "C2" and args.flags == "config" and args.mode == "train"
                 and not args.points and not args.mu_px):
             del s, g, cams                      # the other configs run in child processes of their own: give the memory back first
             torch.cuda.empty_cache()
@@ -377,6 +418,44 @@ def main():
     if launched:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_sample(n):
+    """The rows --dump-outputs keeps of an array of n Gaussians or n pixels: all of them, or DUMP_ITEMS of them drawn by a fixed seed
+    (the same rows for the same n in every run and every build)."""
+    import numpy as np
+    if n <= DUMP_ITEMS:
+        return None
+    return np.sort(np.random.default_rng(20240607 + n).choice(n, DUMP_ITEMS, replace=False))
+
+
+def dump_outputs(out_dir, arrays, P, H, W):
+    """DIR/<name>.npy for every output of the last timed step: per-Gaussian arrays (first axis P) and maps ([C, H, W]) reduced to the
+    rows dump_sample() picks, as float32; num_rendered as a float64 array of one element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        if not torch.is_tensor(t):
+            a = np.array([t], dtype=np.float64)
+        else:
+            t = t.detach()
+            if t.dim() == 3 and tuple(t.shape[1:]) == (H, W):        # map: pixels are the rows
+                t = t.reshape(t.shape[0], H * W)
+                idx = dump_sample(H * W)
+                if idx is not None:
+                    t = t[:, torch.from_numpy(idx).to(t.device)]
+            elif t.dim() >= 1 and t.shape[0] == P:                   # per Gaussian
+                idx = dump_sample(P)
+                if idx is not None:
+                    t = t[torch.from_numpy(idx).to(t.device)]
+            a = t.float().cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit(f"--dump-outputs: {total} bytes at {name}, more than {DUMP_MAX_BYTES}")
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def other_configs_and_train_iter():
@@ -392,7 +471,7 @@ def other_configs_and_train_iter():
 
     def left():
         return BUDGET - (time.time() - t_start)
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--no-other-configs"]
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "3", "--full", "--no-cpu-baseline", "--no-other-configs"]
     legs = [("C4", ["--config", "C4"]), ("C5", ["--config", "C5"]), ("C3", ["--config", "C3"]), ("C2_both_maps", ["--flags", "both"]),
             ("C2_both_maps_forward_only", ["--flags", "both", "--mode", "forward"])]
     for name, extra in legs:

@@ -1,6 +1,7 @@
 #!/bin/bash
 # bench lines of the BASELINE configs (args: extra bench flags)
 set -u
+set -- --full "$@"   # the summary below reads stages_ms
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 for c in C2 C3 C4 C5; do

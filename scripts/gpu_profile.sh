@@ -19,7 +19,7 @@ rm -rf $OUT; mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
 B="$GRAFT_REPO_ROOT/bench.py --config $CFG $EXTRA_ARGS"
-NOCPU=""; { [ "$CFG" != "C2" ] || [ -n "$SFX" ]; } && NOCPU="--no-cpu-baseline"
+NOCPU="--full"; { [ "$CFG" != "C2" ] || [ -n "$SFX" ]; } && NOCPU="--full --no-cpu-baseline"
 python $B --steps 20 --warmup 10 $NOCPU > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -c 300 $OUT/bench.json
 timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/kt --output-format csv -- python $B --steps 20 --warmup 10 --no-cpu-baseline --no-other-configs > $OUT/rocprof_bench.log 2>&1; echo "rocprof rc=$?"
 find $OUT/kt -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats.csv \;

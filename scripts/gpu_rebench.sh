@@ -8,7 +8,7 @@ run() { # suffix, bench args...
   local suf=$1; shift
   local out=gpurun_out/profiles_$TAG$suf
   mkdir -p $out
-  local nocpu="--no-cpu-baseline --no-other-configs"; [ -z "$suf" ] && nocpu=""
+  local nocpu="--full --no-cpu-baseline --no-other-configs"; [ -z "$suf" ] && nocpu="--full"
   timeout 900 python bench.py --steps 20 --warmup 10 $nocpu "$@" > $out/bench.json 2> $out/bench.err; echo "bench$suf rc=$? $(tail -c 120 $out/bench.json)"
 }
 run ""

@@ -35,10 +35,10 @@ PY
       if [ -n "$arg" ]; then timeout 2400 python -m pytest tests -m gpu -q -p no:cacheprovider --durations=25 -k "$args" > gpurun_out/${TAG}_pytest_$n.log 2>&1; else timeout 2400 python -m pytest tests -m gpu -q -p no:cacheprovider --durations=25 > gpurun_out/${TAG}_pytest_$n.log 2>&1; fi
       echo "pytest rc=$?"; tail -4 gpurun_out/${TAG}_pytest_$n.log ;;
     smoke) timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/${TAG}_smoke.log 2>&1; echo "smoke rc=$?"; tail -2 gpurun_out/${TAG}_smoke.log ;;
-    bench)
+    bench) args="--full $args"
       timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs $args > gpurun_out/${TAG}_bench_$n.log 2>&1
       tail -1 gpurun_out/${TAG}_bench_$n.log | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('bench[$n] ${RADEGS_LIB:-intree} $args', d['value'], d['ms_per_step'], {k: round(v,4) for k,v in d['stages_ms'].items() if v})" 2>/dev/null || tail -3 gpurun_out/${TAG}_bench_$n.log ;;
-    benchfull)
+    benchfull) args="--full $args"
       timeout 900 python bench.py $args > gpurun_out/${TAG}_benchfull_$n.log 2>&1; tail -1 gpurun_out/${TAG}_benchfull_$n.log | cut -c1-400 ;;
     env) k=${arg%%=*}; v=${arg#*=}; if [ -z "$v" ]; then unset $k; else export $k="$v"; fi ;;
     ab) if [ "$arg" = base ]; then unset RADEGS_LIB; else export RADEGS_LIB=$PWD/gpurun_ab/libradegs_$arg.so; fi ;;

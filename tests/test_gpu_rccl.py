@@ -52,7 +52,7 @@ def test_exchange_collectives_run_through_rccl_and_match_the_plain_backward(tmp_
 
 @pytest.mark.parametrize("exchange", ["factored", "allreduce"])
 def test_bench_under_the_launcher_with_the_exchange_forced(exchange):
-    p = _launch([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--force-allreduce",
+    p = _launch([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline", "--force-allreduce",
                  "--exchange", exchange, "--points", "200000"])
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1]
