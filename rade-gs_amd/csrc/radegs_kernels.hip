@@ -151,7 +151,7 @@ __global__ void __launch_bounds__(256) emit_instances_kernel(int P, const uint32
   // Two chores that used to be kernels of their own (a 5 us copy and a 5 us fill per forward): the tile ranges start at (0,0)
   // (rasterizer_impl.cu:383's memset; tile_ranges_kernel runs two sorts later), and num_rendered goes to the host's pinned words
   // without a copy engine command or an event: the count, then this forward's sequence number with release order (the host polls the
-  // sequence word once everything else of the forward is queued, rg_launch.inc::binning_finish).
+  // sequence word once everything else of the forward is queued, rg_launch.inc::finish_speculative).
   if (ranges_to_clear) {
     for (int k = i; k < 2 * gx * gy; k += (int)gridDim.x * 256) ranges_to_clear[k] = 0u;
   }

@@ -226,19 +226,32 @@ static bool image_has_streams(const void* img) {
   return g_stream_images.find(img) != g_stream_images.end();
 }
 
-template <bool C, bool D>
-static void launch_blend_bwd(int ppl, int ntiles, const BlendBwdArgs& a, hipStream_t s) {
-  if (ppl == 2) hipLaunchKernelGGL((blend_bwd_packed_kernel<C, D, 2>), dim3(ntiles * 2), dim3(64), 0, s, a);
-  else hipLaunchKernelGGL((blend_bwd_packed_kernel<C, D, 4>), dim3(ntiles), dim3(64), 0, s, a);
+// Run-time flags as template arguments: f(std::true_type or std::false_type, ...), one instantiation per combination.
+template <class F> static void dispatch(bool a, F&& f) { if (a) f(std::true_type()); else f(std::false_type()); }
+template <class F> static void dispatch(bool coord, bool depth, F&& f) {   // the blend kernels' <COORD, DEPTH>
+  dispatch(coord, [&](auto c) { dispatch(depth, [&](auto d) { f(c, d); }); });
 }
 
 // The Gaussian-side inputs shared by radegs_forward and radegs_integrate.
 struct GaussIn {
   int P, D, M;
-  const float* means3D; const float* scales; const float* rotations; const float* cov3D_precomp;
-  const float* opacities; const float* shs; const float* colors_precomp;
+  const float *means3D, *scales, *rotations, *cov3D_precomp, *opacities, *shs, *colors_precomp;
   int* radii;
 };
+template <class Args> static GaussIn gauss_in(const Args* A) {
+  return GaussIn{A->P, A->D, A->M, A->means3D, A->scales, A->rotations, A->cov3D_precomp, A->opacities, A->shs, A->colors_precomp, A->radii};
+}
+// The checks of the Gaussian-side inputs that radegs_forward, radegs_integrate and radegs_backward_from_sums share, in this order and
+// with upstream's messages ("excatly" included).  `present`: the caller's required pointers are all there; `colors`: the call takes
+// SHs or precomputed colours.
+template <class Args> static int check_gaussians(const Args* A, bool present, bool colors) {
+  if (!present) return fail(RADEGS_ERR_INVALID_ARG, "missing required tensor");
+  if (colors && (A->shs == nullptr) == (A->colors_precomp == nullptr))
+    return fail(RADEGS_ERR_INVALID_ARG, "Please provide excatly one of either SHs or precomputed colors!");
+  if (((A->scales == nullptr) || (A->rotations == nullptr)) == (A->cov3D_precomp == nullptr))
+    return fail(RADEGS_ERR_INVALID_ARG, "Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!");
+  return 0;
+}
 
 // ---- speculative binning --------------------------------------------------------------------------------------------------
 // The reference sizes the binning buffer from num_rendered, which it reads back with a blocking copy in the middle of
@@ -252,47 +265,29 @@ struct GaussIn {
 // schedules) would otherwise ping-pong one hint between very different counts.
 struct HintKey { int dev, W, H; bool operator==(const HintKey& o) const { return dev == o.dev && W == o.W && H == o.H; } };
 struct HintKeyHash { size_t operator()(const HintKey& k) const { return ((size_t)k.dev * 1000003u + (size_t)k.W) * 1000003u + (size_t)k.H; } };
-static std::mutex g_hint_mu;
-// What the previous forwards of a (device, W, H) needed: instances (num_rendered), chunks of entry-stream storage, and whether the
-// streams of such a view exceeded RADEGS_STREAMS_MAX_MB (the launcher then stops asking for them instead of redoing every forward).
+// What the previous forwards of a (device, W, H) needed: instances (num_rendered), chunks of entry-stream storage, the splat size S
+// (use_streams), whether the depths of such a view once left the 3-pass sort's window, and whether its streams exceeded
+// RADEGS_STREAMS_MAX_MB (the launcher then stops asking for them instead of redoing every forward).
 // The "do not fit" verdict is not for ever (ADVICE r5): one oversized view -- a densification peak before pruning -- would otherwise keep
-// this (device, W, H) on the slower tile-wide path for the rest of the run.  It holds for kNoFitForwards forwards, then the streams are
+// this (device, W, H) on the slower tile-wide path for the rest of the run.  It holds for kNoFitForwards attempts, then the streams are
 // tried again (and refused again for as long if the lists still exceed the budget).
 constexpr uint32_t kNoFitForwards = 64;
-struct Hint { uint32_t R = 0, chunks = 0; float weighted_size = 0.0f; uint32_t no_fit_left = 0; };
-static std::unordered_map<HintKey, Hint, HintKeyHash> g_hint;
-static Hint hint_load(const HintKey& k) {
-  std::lock_guard<std::mutex> l(g_hint_mu);
-  auto it = g_hint.find(k);
-  return it == g_hint.end() ? Hint() : it->second;
+struct History { uint32_t R = 0, chunks = 0; float weighted_size = 0.0f; uint32_t no_fit_left = 0; bool sort4 = false; };
+static std::mutex g_hist_mu;
+static std::unordered_map<HintKey, History, HintKeyHash> g_hist;
+// The record as an attempt finds it; the attempt ticks the no-fit countdown (*no_fit: the streams stay refused this time).
+static History history_begin(const HintKey& k, bool* no_fit) {
+  std::lock_guard<std::mutex> l(g_hist_mu);
+  auto it = g_hist.find(k);
+  *no_fit = it != g_hist.end() && it->second.no_fit_left != 0u;
+  if (*no_fit) it->second.no_fit_left--;
+  return it == g_hist.end() ? History() : it->second;
 }
-static Hint& hint_slot(const HintKey& k) {   // g_hint_mu held
-  if (g_hint.size() > 1024 && g_hint.find(k) == g_hint.end()) g_hint.clear();
-  return g_hint[k];
+template <class F> static void history_update(const HintKey& k, F&& f) {
+  std::lock_guard<std::mutex> l(g_hist_mu);
+  if (g_hist.size() > 1024 && g_hist.find(k) == g_hist.end()) g_hist.clear();
+  f(g_hist[k]);
 }
-static void hint_store(const HintKey& k, uint32_t R, float weighted_size) {
-  std::lock_guard<std::mutex> l(g_hint_mu);
-  Hint& h = hint_slot(k);
-  h.R = R;
-  if (weighted_size > 0.0f) h.weighted_size = weighted_size;
-}
-static void hint_store_chunks(const HintKey& k, uint32_t chunks, bool do_not_fit) {
-  std::lock_guard<std::mutex> l(g_hint_mu);
-  Hint& h = hint_slot(k);
-  h.chunks = std::max(chunks, h.chunks - h.chunks / 64);
-  h.no_fit_left = do_not_fit ? kNoFitForwards : 0u;
-}
-// one forward at this (device, W, H) goes by: true while the streams stay refused
-static bool hint_no_fit_tick(const HintKey& k) {
-  std::lock_guard<std::mutex> l(g_hint_mu);
-  auto it = g_hint.find(k);
-  if (it == g_hint.end() || it->second.no_fit_left == 0u) return false;
-  it->second.no_fit_left--;
-  return true;
-}
-static std::unordered_map<HintKey, bool, HintKeyHash> g_sort32;   // (device, W, H) whose depths did not fit the 3-pass sort's window once
-static bool sort32_load(const HintKey& k) { std::lock_guard<std::mutex> l(g_hint_mu); return g_sort32.find(k) != g_sort32.end(); }
-static void sort32_store(const HintKey& k) { std::lock_guard<std::mutex> l(g_hint_mu); if (g_sort32.size() > 1024) g_sort32.clear(); g_sort32[k] = true; }
 // Words of the mapped host block the kernels write directly (system-scope stores into pinned, coherent host memory).
 enum { PIN_COUNT = 0,      // num_rendered of the forward in flight (emit_instances_kernel)
        PIN_KEY_OVERFLOW,   // a visible depth key outside the 3-pass sort's window (preprocess_fwd_kernel)
@@ -339,16 +334,294 @@ static int check_stream_error(int dev) {
   return 0;
 }
 
-// A speculative binning whose counts the host has not looked at yet (binning_finish does).
 static std::atomic<unsigned long long> g_spec_calls{0}, g_spec_misses{0};   // speculative forwards / those that had to be redone
 
-struct BinPending {
-  bool pending = false; uint32_t cap = 0, hint = 0, seq = 0; HintKey key{0, 0, 0}; bool hint_forced = false; bool sort27 = false; hipStream_t stream = nullptr;
-  bool streams = false; size_t chunk_cap = 0;   // the forward builds entry streams into storage for chunk_cap chunks
+// ---- one forward or integrate: attempts at the binning until one fits ---------------------------------------------------------
+// How an attempt ended: its binning fitted; or the forward is redone with exact sizes (a capacity was too small); or with exact sizes
+// and the 4-pass depth sort (a visible depth key left the 3-pass sort's window, so the order is not to be trusted).
+enum Outcome { kFits = 0, kRedoExact, kRedo4Pass };
+
+// What an attempt settles before its first launch.  The first attempt of a call is speculative where it can be (history, a mapped
+// host block, no debug sync) and exact otherwise; a redo is exact, with the 4-pass sort after kRedo4Pass.
+struct Plan {
+  Switches sw;
+  HintKey key{0, 0, 0};
+  History hist;                 // the record of `key` as this attempt found it
+  bool no_fit = false;          // entry streams refused at `key` this time (History::no_fit_left)
+  bool speculative = false, hint_forced = false;   // hint_forced: the prediction is RADEGS_SPECULATE_HINT's (no R nor S is recorded)
+  uint32_t hint = 0, cap = 0;   // predicted num_rendered; speculative: capacity of the instance arrays
+  uint32_t seq = 0;             // speculative: what the device writes to PIN_SEQ once the counts have landed (0: exact)
+  PinnedCount* pin = nullptr;   // the mapped host words of this thread and device, if it has them
+  const PrimsCheck* prims = nullptr;   // RADEGS_PRIMS=rocprim: depth sort, scan and tile sort through the device library
+  // depth sort: three 9-bit passes over (key - bits(0.2f)) instead of four 8-bit ones, valid while every visible z < 13 107 -- the
+  // preprocess flags a key outside that window in a mapped host word (size_exact, finish_speculative look at it)
+  bool sort27 = false;
+  bool key16 = false;           // 16-bit tile keys (a third less sort traffic) wherever the tile id fits
+  bool rect = false;            // packed tile rectangles (8 bits per field): gathered into depth order by the scan, read by the emission
+  bool mask_in_key = false;     // with entry streams, the block mask rides in a 32-bit tile KEY (scenes of 2^24 Gaussians and more)
+  bool sq_sum = false;          // the scan adds up S's numerator, sum over the Gaussians of (tiles touched)^2
+  int tile_bits = 0;
 };
 
-// 0: the speculative binning fitted (R is valid); 1: capacity too small (instances, or chunks of entry-stream storage); 2: a depth key
-// outside the 3-pass sort's window (redo with the 4-pass sort); < 0: error
+struct Alloc {
+  radegs_alloc_fn fn; void* user;
+  void* operator()(size_t bytes) const { return fn(user, bytes); }
+};
+// One forward or integrate call: its inputs and allocators, and the state its attempts carve.
+struct Binning {
+  GaussIn G; CamArgs cam; bool coord = false;
+  float4* inte_rec = nullptr;   // != nullptr: the INTE preprocess (integrate path), which also writes [P][8] floats there
+  Alloc geom, bin, image;
+  bool streams_allowed = false, dbg = false; hipStream_t stream = nullptr;
+  GeomState gs; BinState bs; ImageState is;
+  size_t chunk_cap = 0;         // with entry streams (is.blk_chunks != nullptr): chunks of list storage in the image state
+  uint32_t R = 0;               // num_rendered, once the host knows it
+};
+
+static int plan_attempt(const Binning& B, Outcome prev, Plan& p) {
+  p.sw = switches();
+  if (p.sw.rocprim) {
+    if (!prims_check().ok) return fail(RADEGS_ERR_INVALID_ARG, "RADEGS_PRIMS=rocprim: libradegs_prims_check.so (test-only) is not next to the library");
+    p.prims = &prims_check();
+  }
+  int devid = 0;
+  (void)hipGetDevice(&devid);
+  p.key = HintKey{devid, B.cam.W, B.cam.H};
+  p.hist = history_begin(p.key, &p.no_fit);
+  p.hint_forced = p.sw.speculate_hint > 0;   // tests: force a (too small) prediction
+  p.hint = p.hint_forced ? (uint32_t)p.sw.speculate_hint : p.hist.R;
+  PinnedCount& pin = pinned_for(devid);
+  if (devid < 64 && pin.ok()) p.pin = &pin;
+  // the device library's primitives come plain: no speculation, rect gather, 16-bit keys, 27-bit sort or S statistic around them
+  const bool own = p.prims == nullptr;
+  p.speculative = prev == kFits && p.sw.speculate != 0 && p.hint > 0 && !B.dbg && own && p.pin;
+  p.sort27 = own && p.pin && prev != kRedo4Pass && !p.hist.sort4;
+  p.tile_bits = (int)higher_msb((uint32_t)(B.cam.gx * B.cam.gy));
+  p.key16 = own && p.tile_bits <= 16;
+  p.rect = own && B.cam.gx <= 255 && B.cam.gy <= 255;
+  p.sq_sum = own;
+  p.mask_in_key = mask_rides_in_key(p.sw, B.G.P);
+  if (p.speculative) {
+    p.cap = (uint32_t)std::min<uint64_t>((uint64_t)p.hint + p.hint / 4 + 4096, 0x7FFFFFFFull);
+    p.seq = ++pin.seq;
+  }
+  return 0;
+}
+
+static int alloc_geometry(Binning& B, const Plan& p) {
+  const size_t P = (size_t)B.G.P;
+  size_t temp = std::max(sort_temp_bytes(P), scan_temp_bytes(P));
+  if (p.prims) temp = std::max(temp, p.prims->temp_geom(P));
+  void* ptr = B.geom(GeomState::carve(nullptr, P, B.coord, temp).total);
+  if (!ptr) return fail(RADEGS_ERR_ALLOC, "geometry buffer allocation failed");
+  B.gs = GeomState::carve(ptr, P, B.coord, temp);
+  return 0;
+}
+
+// Image state for `capacity` instances; its tail holds the sub-tile entry streams when the call allows them and use_streams() says so
+// (is.blk_chunks != nullptr afterwards).  With entry streams its tail holds `chunk_cap` chunks: what the previous forward at this
+// (device, W, H) needed + 25 % when the overflow can be noticed without a stall (speculative attempt: finish_speculative), otherwise the
+// capacity that cannot overflow (stream_chunk_capacity_safe); never more than RADEGS_STREAMS_MAX_MB -- a speculative attempt may try
+// its luck inside that budget, an exact one then goes without streams.
+static bool alloc_image(Binning& B, const Plan& p, size_t capacity, float weighted_size) {
+  const Switches& sw = p.sw;
+  const bool overflow_is_detected = p.speculative;
+  bool streams = B.streams_allowed && use_streams(sw, (long long)capacity, B.G.P, weighted_size) && !(p.no_fit && sw.streams < 0);
+  size_t chunk_cap = 0;
+  if (streams) {
+    const uint32_t hint = p.hist.chunks;
+    const size_t safe = stream_chunk_capacity_safe(std::max<size_t>(capacity, 1), (size_t)(B.cam.gx * B.cam.gy));
+    const size_t budget = sw.streams_max_bytes / (kChunkWords * sizeof(uint32_t));
+    chunk_cap = (overflow_is_detected && hint) ? std::min(safe, (size_t)hint + hint / 4 + 4096) : safe;
+    if (overflow_is_detected && sw.speculate_chunks > 0) chunk_cap = (size_t)sw.speculate_chunks;
+    if (chunk_cap > budget) chunk_cap = overflow_is_detected ? budget : 0;
+    if (chunk_cap > 0xFFFFFFF0ull) chunk_cap = 0xFFFFFFF0ull;   // chunk indices are 32-bit (0.8 TB of lists)
+    streams = chunk_cap != 0;
+  }
+  const size_t W = (size_t)B.cam.W, H = (size_t)B.cam.H;
+  void* ptr = B.image(ImageState::carve(nullptr, W, H, chunk_cap).total);
+  if (!ptr && streams) {   // the stream-sized state did not fit: the tile-wide formulation needs none of it
+    streams = false; chunk_cap = 0;
+    ptr = B.image(ImageState::carve(nullptr, W, H, 0).total);
+  }
+  if (!ptr) return false;
+  B.is = ImageState::carve(ptr, W, H, chunk_cap);
+  B.chunk_cap = chunk_cap;
+  if (!streams) B.is.blk_chunks = nullptr;
+  note_stream_image(ptr, streams);
+  g_last_forward_streams = streams ? 1 : 0;
+  return true;
+}
+
+// Binning state and image state for `capacity` instances.
+static int alloc_binning(Binning& B, const Plan& p, size_t capacity, float weighted_size) {
+  size_t temp = sort_temp_bytes(capacity);
+  if (p.prims) temp = std::max(temp, p.prims->temp_bin(capacity, p.tile_bits));
+  void* ptr = B.bin(BinState::carve(nullptr, capacity, temp).total);
+  if (!ptr) return fail(RADEGS_ERR_ALLOC, "binning buffer allocation failed");
+  B.bs = BinState::carve(ptr, capacity, temp);
+  if (!alloc_image(B, p, capacity, weighted_size)) return fail(RADEGS_ERR_ALLOC, "image buffer allocation failed");
+  return 0;
+}
+
+// 1. per-Gaussian preprocess, 2. depth order of the Gaussians, 3. instance offsets in that order
+static int queue_geometry(Binning& B, const Plan& p) {
+  const GaussIn& G = B.G;
+  const GeomState& gs = B.gs;
+  hipStream_t stream = B.stream;
+  if (p.sort27) p.pin->h[PIN_KEY_OVERFLOW] = 0u;
+  {
+    StageTimer tm(ST_PRE_FWD, stream);
+    PreFwdArgs pa;
+    pa.P = G.P; pa.D = G.D; pa.M = G.M;
+    pa.means3D = G.means3D; pa.scales = G.scales; pa.rotations = G.rotations; pa.cov3D_precomp = G.cov3D_precomp;
+    pa.opacities = G.opacities; pa.shs = G.shs; pa.colors_precomp = G.colors_precomp;
+    pa.cam = B.cam; pa.write_b = B.coord ? 1 : 0;
+    pa.radii = G.radii; pa.inte_rec = B.inte_rec; pa.splat_a = reinterpret_cast<float4*>(gs.splat_a); pa.splat_b = reinterpret_cast<float4*>(gs.splat_b);
+    pa.tiles_touched = gs.tiles_touched; pa.depth_key = gs.depth_key; pa.clamped = gs.clamped; pa.rect = gs.rect;
+    pa.key_overflow = p.sort27 ? p.pin->dev() + PIN_KEY_OVERFLOW : nullptr;
+    dispatch(B.inte_rec != nullptr, [&](auto inte) { hipLaunchKernelGGL(preprocess_fwd_kernel<inte>, dim3((G.P + 255) / 256), dim3(256), 0, stream, pa); });
+    RG_LAUNCH_CHECK("preprocess_fwd_kernel", B.dbg, stream);
+  }
+  const size_t P = (size_t)G.P;
+  {
+    StageTimer tm(ST_SORT_DEPTH, stream);
+    if (p.prims) RG_HIP(p.prims->sort_by_depth(gs.temp, gs.temp_bytes, gs.depth_key, gs.depth_key_sorted, gs.idx_sorted, P, stream));
+    else if (p.sort27) RG_HIP(radix_sort_pairs_u32_27(gs.temp, gs.temp_bytes, gs.depth_key, gs.depth_key_sorted, nullptr, gs.idx_sorted, P, kDepthKeyBase, stream));
+    else RG_HIP(radix_sort_pairs_u32(gs.temp, gs.temp_bytes, gs.depth_key, gs.depth_key_sorted, nullptr, gs.idx_sorted, P, 32, stream));
+  }
+  {
+    StageTimer tm(ST_SCAN, stream);
+    if (p.prims) RG_HIP(p.prims->scan(gs.temp, gs.temp_bytes, gs.tiles_touched, gs.idx_sorted, gs.offsets, P, stream));
+    else RG_HIP(inclusive_scan_gather_u32(gs.temp, gs.temp_bytes, p.rect ? gs.rect : gs.tiles_touched, gs.idx_sorted, gs.offsets, P, stream,
+                                          p.rect ? gs.rect_sorted : nullptr, gs.tile_sq_sum));
+  }
+  return 0;
+}
+
+// 4. exact sizes: the one host sync of the reference's forward -- num_rendered sizes the binning buffer (rasterizer_impl.cu:354)
+static int size_exact(Binning& B, const Plan& p, Outcome& out) {
+  uint32_t R = 0;
+  unsigned long long sq = 0ull;
+  RG_HIP(hipMemcpyAsync(&R, B.gs.offsets + (B.G.P - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, B.stream));
+  if (p.sq_sum) RG_HIP(hipMemcpyAsync(&sq, B.gs.tile_sq_sum, sizeof(sq), hipMemcpyDeviceToHost, B.stream));
+  RG_HIP(hipStreamSynchronize(B.stream));
+  if (p.sort27 && p.pin->h[PIN_KEY_OVERFLOW] != 0u) {
+    history_update(p.key, [](History& h) { h.sort4 = true; });
+    out = kRedo4Pass;
+    return 0;
+  }
+  if (R > 0x7FFFFFFFu) return fail(RADEGS_ERR_INVALID_ARG, "num_rendered overflows int32");
+  const float weighted_size = (R && p.sq_sum) ? (float)((double)sq / (double)R) : 0.0f;
+  if (!p.hint_forced)
+    history_update(p.key, [&](History& h) { h.R = std::max(R, p.hint - p.hint / 64); if (weighted_size > 0.0f) h.weighted_size = weighted_size; });
+  B.R = R;
+  return alloc_binning(B, p, R, weighted_size);
+}
+
+// 5. instances, 6. sorted by tile, 7. tile ranges: for the capacity of a speculative attempt (the real count is read on the device) or
+// for the exact count
+static int queue_instances(Binning& B, const Plan& p) {
+  const GeomState& gs = B.gs; const BinState& bs = B.bs; const ImageState& is = B.is;
+  hipStream_t stream = B.stream;
+  if (!p.speculative && B.R == 0) {
+    RG_HIP(hipMemsetAsync(is.ranges, 0, (size_t)(B.cam.gx * B.cam.gy) * 2 * sizeof(uint32_t), stream));
+    RG_HIP(hipMemsetAsync(is.stream_tag, 0, 4 * sizeof(uint32_t), stream));
+    return 0;
+  }
+  const int P = B.G.P;
+  const uint32_t n = p.speculative ? p.cap : B.R;
+  const uint32_t* n_dev = p.speculative ? gs.offsets + (P - 1) : nullptr;
+  const bool streams = is.blk_chunks != nullptr;
+  const bool mask_in_key = streams && p.mask_in_key;
+  const bool key16 = p.key16 && !mask_in_key;
+  {
+    StageTimer tm(ST_EMIT, stream);
+    // with entry streams every instance also learns which blocks of its tile it can reach (top byte of the value); the kernel also
+    // clears the tile ranges and, speculative, mirrors num_rendered into the host's pinned words
+    uint32_t* const count_mirror = p.speculative ? p.pin->dev() : nullptr;
+    dispatch(streams, [&](auto masks) {
+      hipLaunchKernelGGL(emit_instances_kernel<masks>, dim3((P + 255) / 256), dim3(256), 0, stream, P, gs.idx_sorted, gs.offsets,
+                         gs.tiles_touched, reinterpret_cast<const float4*>(gs.splat_a), B.G.radii, p.rect ? gs.rect_sorted : nullptr,
+                         B.cam.gx, B.cam.gy, bs.tile_keys, bs.point_list_unsorted, n, is.ranges, count_mirror, p.seq, is.stream_tag,
+                         key16 ? 1 : 0, mask_in_key ? 1 : 0, gs.tile_sq_sum);
+    });
+    RG_LAUNCH_CHECK("emit_instances_kernel", B.dbg, stream);
+  }
+  {
+    StageTimer tm(ST_SORT_TILE, stream);
+    if (p.prims)
+      RG_HIP(p.prims->sort_by_tile(bs.temp, bs.temp_bytes, bs.tile_keys, bs.tile_keys_sorted, bs.point_list_unsorted, bs.point_list, (size_t)n,
+                                   p.tile_bits, stream));
+    else if (key16)
+      RG_HIP(radix_sort_pairs_u16(bs.temp, bs.temp_bytes, reinterpret_cast<const uint16_t*>(bs.tile_keys), reinterpret_cast<uint16_t*>(bs.tile_keys_sorted),
+                                  bs.point_list_unsorted, bs.point_list, (size_t)n, p.tile_bits, stream, n_dev));
+    else
+      RG_HIP(radix_sort_pairs_u32(bs.temp, bs.temp_bytes, bs.tile_keys, bs.tile_keys_sorted, bs.point_list_unsorted, bs.point_list,
+                                  (size_t)n, p.tile_bits, stream, n_dev));
+  }
+  {
+    StageTimer tm(ST_RANGES, stream);
+    if (key16)   // 8 keys per thread
+      hipLaunchKernelGGL(tile_ranges_kernel<uint16_t>, dim3((n + 8 * kRangeThreads - 1) / (8 * kRangeThreads)), dim3(kRangeThreads), 0, stream,
+                         (int)n, reinterpret_cast<const uint16_t*>(bs.tile_keys_sorted), reinterpret_cast<uint2*>(is.ranges), n_dev, 0xFFFFu, (int)n);
+    else         // 4 keys per thread
+      hipLaunchKernelGGL(tile_ranges_kernel<uint32_t>, dim3((n + 4 * kRangeThreads - 1) / (4 * kRangeThreads)), dim3(kRangeThreads), 0, stream,
+                         (int)n, bs.tile_keys_sorted, reinterpret_cast<uint2*>(is.ranges), n_dev, mask_in_key ? kGidMask : 0xFFFFFFFFu, (int)n);
+    RG_LAUNCH_CHECK("tile_ranges_kernel", B.dbg, stream);
+  }
+  return 0;
+}
+
+// 7b. sub-tile entry lists (rg_streams.inc) and 8. the blend of a forward
+static int queue_blend(const Binning& B, const Plan& p, const RadegsFwdArgs* A) {
+  const GeomState& gs = B.gs; const BinState& bs = B.bs; const ImageState& is = B.is; const CamArgs& cam = B.cam;
+  hipStream_t stream = B.stream;
+  const int ntiles = cam.gx * cam.gy;
+  const bool streams = is.blk_chunks != nullptr;
+  if (streams) {
+    StageTimer tm(ST_BLOCK_LISTS, stream);
+    uint32_t* const pin_words = p.speculative ? p.pin->dev() : nullptr;   // a speculative forward reports to the host's mapped words
+    BlockListArgs la;
+    la.ranges = reinterpret_cast<const uint2*>(is.ranges); la.point_list = bs.point_list; la.keys_sorted = bs.tile_keys_sorted;
+    la.gx = cam.gx; la.ntiles = ntiles;
+    la.blk_count = is.blk_count; la.blk_base = is.blk_base; la.blk_chunks = is.blk_chunks;
+    la.wg_need = is.wg_need; la.stream_meta = is.stream_tag; la.chunk_capacity = (uint32_t)B.chunk_cap;
+    // a grid that fills the chip once (8 workgroups of 4 waves per CU), a multiple of 8 so that tiles keep their XCD
+    const int list_grid = std::min(ntiles, kListGridMax);
+    // block_lists_kernel's FIRST workgroups sort the blocks of every 64-tile neighbourhood by list length (balance_blocks needs the counts
+    // only): their number rounded up to a multiple of 8, so that a list-building workgroup runs on the XCD block_counts_kernel's ran on
+    const int nblocks = ntiles * kBlocksPerTile;
+    const int bal_groups = (((nblocks + kBalanceBlocks - 1) / kBalanceBlocks) + 7) & ~7;
+    la.list_grid = list_grid; la.bal_groups = bal_groups; la.blk_order = is.blk_order;
+    la.pin_chunks = pin_words ? pin_words + PIN_CHUNKS : nullptr; la.pin_seq = pin_words ? pin_words + PIN_SEQ : nullptr; la.seq = p.seq;
+    dispatch(p.mask_in_key, [&](auto mask_in_key) {
+      hipLaunchKernelGGL(block_counts_kernel<mask_in_key>, dim3(list_grid), dim3(kListThreads), 0, stream, la);
+      hipLaunchKernelGGL(block_lists_kernel<mask_in_key>, dim3(bal_groups + list_grid), dim3(kListThreads), 0, stream, la);
+    });
+    RG_LAUNCH_CHECK("block_lists_kernel", B.dbg, stream);
+  }
+  {
+    StageTimer tm(ST_BLEND_FWD, stream);
+    BlendFwdArgs ba;
+    ba.ranges = reinterpret_cast<const uint2*>(is.ranges); ba.point_list = bs.point_list;
+    ba.splat_a = reinterpret_cast<const float4*>(gs.splat_a); ba.splat_b = reinterpret_cast<const float4*>(gs.splat_b);
+    ba.W = cam.W; ba.H = cam.H; ba.gx = cam.gx; ba.ntiles = ntiles; ba.focal_x = cam.focal_x; ba.focal_y = cam.focal_y;
+    ba.bg = A->background;
+    ba.out_color = A->out_color; ba.out_coord = A->out_coord; ba.out_mcoord = A->out_mcoord; ba.out_depth = A->out_depth;
+    ba.out_mdepth = A->out_mdepth; ba.out_alpha = A->out_alpha; ba.out_normal = A->out_normal;
+    ba.n_contrib = is.n_contrib; ba.accum_coord = is.accum_coord; ba.accum_depth = is.accum_depth; ba.normal_length = is.normal_length;
+    ba.blk_count = is.blk_count; ba.blk_base = is.blk_base; ba.blk_consumed = is.blk_consumed; ba.blk_chunks = is.blk_chunks; ba.blk_order = is.blk_order;
+    const bool coord = A->require_coord != 0, depth = A->require_depth != 0;
+    if (streams) dispatch(coord, depth, [&](auto c, auto d) { hipLaunchKernelGGL((blend_fwd_streams_kernel<c, d>), dim3(ntiles * 2), dim3(64), 0, stream, ba); });
+    else dispatch(coord, depth, [&](auto c, auto d) {   // tile-wide: one wave per 16x8 strip, 2 pixels per lane (measured best on every BASELINE config)
+      hipLaunchKernelGGL((blend_fwd_kernel<c, d, 2>), dim3(ntiles * 2), dim3(64), 0, stream, ba);
+    });
+    RG_LAUNCH_CHECK("blend_fwd_kernel", B.dbg, stream);
+  }
+  return 0;
+}
+
 static inline void cpu_relax() {
 #if defined(__x86_64__) || defined(__i386__)
   __builtin_ia32_pause();
@@ -358,262 +631,72 @@ static inline void cpu_relax() {
   std::atomic_signal_fence(std::memory_order_seq_cst);
 #endif
 }
-static int binning_finish(const BinPending& p, int* R) {
-  PinnedCount& pin = pinned_for(p.key.dev);
+// The host looks at the counts of a speculative attempt: records them and tells whether the predicted capacities held.
+static int finish_speculative(Binning& B, const Plan& p, Outcome& out) {
+  volatile uint32_t* const h = p.pin->h;
   // the count leaves the emission kernel early in the forward and everything else is queued behind it by now: normally it is there
   // already.  Poll the sequence word (written after the count, release order); a stream that does not deliver within ~2 s of polling is
   // synchronised the ordinary way so that a device error surfaces as an error code, not as a hang.
-  {
-    uint32_t spins = 0;
-    while (pin.h[PIN_SEQ] != p.seq) {
-      if (++spins <= 4096u) { cpu_relax(); continue; }   // ~50 us of busy polling: the usual case ends here
-      if (spins > 4096u + 40000u) {
-        RG_HIP(hipStreamSynchronize(p.stream));
-        if (pin.h[PIN_SEQ] != p.seq) return fail(RADEGS_ERR_HIP, "num_rendered did not arrive from the device");
-        break;
-      }
-      struct timespec ts = {0, 50000};
-      nanosleep(&ts, nullptr);
+  for (uint32_t spins = 0; h[PIN_SEQ] != p.seq;) {
+    if (++spins <= 4096u) { cpu_relax(); continue; }   // ~50 us of busy polling: the usual case ends here
+    if (spins > 4096u + 40000u) {
+      RG_HIP(hipStreamSynchronize(B.stream));
+      if (h[PIN_SEQ] != p.seq) return fail(RADEGS_ERR_HIP, "num_rendered did not arrive from the device");
+      break;
     }
-    std::atomic_thread_fence(std::memory_order_acquire);
+    struct timespec ts = {0, 50000};
+    nanosleep(&ts, nullptr);
   }
-  const uint32_t R32 = pin.h[PIN_COUNT];
-  if (R32 > 0x7FFFFFFFu) return fail(RADEGS_ERR_INVALID_ARG, "num_rendered overflows int32");
-  const uint64_t sq = (uint64_t)pin.h[PIN_SQ_LO] | ((uint64_t)pin.h[PIN_SQ_HI] << 32);
-  if (!p.hint_forced) hint_store(p.key, std::max(R32, p.hint - p.hint / 64), R32 ? (float)((double)sq / (double)R32) : 0.0f);
+  std::atomic_thread_fence(std::memory_order_acquire);
+  const uint32_t R = h[PIN_COUNT];
+  if (R > 0x7FFFFFFFu) return fail(RADEGS_ERR_INVALID_ARG, "num_rendered overflows int32");
+  const uint64_t sq = (uint64_t)h[PIN_SQ_LO] | ((uint64_t)h[PIN_SQ_HI] << 32);
+  const float weighted_size = R ? (float)((double)sq / (double)R) : 0.0f;
+  if (!p.hint_forced)
+    history_update(p.key, [&](History& r) { r.R = std::max(R, p.hint - p.hint / 64); if (weighted_size > 0.0f) r.weighted_size = weighted_size; });
   bool chunk_overflow = false;
-  if (p.streams) {
-    const uint32_t need = pin.h[PIN_CHUNKS];
-    chunk_overflow = pin.h[PIN_CHUNK_OVERFLOW] != 0u || need > p.chunk_cap;
+  if (B.is.blk_chunks) {
+    const uint32_t need = h[PIN_CHUNKS];
+    chunk_overflow = h[PIN_CHUNK_OVERFLOW] != 0u || need > B.chunk_cap;
     // lists that do not even fit the configured budget: stop asking for streams at this (device, W, H)
-    hint_store_chunks(p.key, need, (size_t)need * kChunkWords * sizeof(uint32_t) > switches().streams_max_bytes);
+    const bool no_fit = (size_t)need * kChunkWords * sizeof(uint32_t) > p.sw.streams_max_bytes;
+    history_update(p.key, [&](History& r) { r.chunks = std::max(need, r.chunks - r.chunks / 64); r.no_fit_left = no_fit ? kNoFitForwards : 0u; });
   }
-  *R = (int)R32;
+  B.R = R;
   g_spec_calls++;
-  if (p.sort27 && pin.h[PIN_KEY_OVERFLOW] != 0u) { g_spec_misses++; sort32_store(p.key); return 2; }
-  if (R32 > p.cap || chunk_overflow) g_spec_misses++;
-  return (R32 > p.cap || chunk_overflow) ? 1 : 0;
+  if (p.sort27 && h[PIN_KEY_OVERFLOW] != 0u) {
+    history_update(p.key, [](History& r) { r.sort4 = true; });
+    out = kRedo4Pass;
+  } else {
+    out = (R > p.cap || chunk_overflow) ? kRedoExact : kFits;
+  }
+  if (out != kFits) g_spec_misses++;
+  return 0;
 }
 
-// Stages 1-7 of the forward (preprocess and binning); returns num_rendered or < 0.
-// inte_rec != nullptr selects the INTE preprocess (integrate path), which also writes [P][8] floats there.
-// The image state is allocated here too, as soon as the capacity of the binning is known: its tail holds the sub-tile entry
-// streams when `streams_allowed` and use_streams() say so (is.blk_chunks != nullptr afterwards).
-// pend != nullptr: a speculative binning returns WITHOUT waiting for its counts (pend->pending, provisional return value = the
-// capacity); the caller queues the rest of the forward and then calls binning_finish.  force: 0 = as configured, 1 = exact
-// sizes (no speculation), 2 = exact sizes and the 4-pass depth sort (a depth key did not fit the 3-pass sort's window).
-static int geometry_and_binning(const GaussIn& G, const CamArgs& cam, bool coord, float4* inte_rec, radegs_alloc_fn geom_alloc,
-                                void* geom_user, radegs_alloc_fn binning_alloc, void* binning_user, radegs_alloc_fn image_alloc,
-                                void* image_user, bool streams_allowed, bool dbg, hipStream_t stream, GeomState& gs, BinState& bs,
-                                ImageState& is, BinPending* pend = nullptr, int force = 0) {
-  const int P = G.P;
-  const int ntiles = cam.gx * cam.gy;
-  const Switches sw = switches();
-  // Image state for `capacity` instances.  With entry streams its tail holds `chunk_cap` chunks: what the previous forward at this
-  // (device, W, H) needed + 25 % when the overflow can be noticed without a stall (speculative forward: binning_finish), otherwise the
-  // capacity that cannot overflow (stream_chunk_capacity_safe); never more than RADEGS_STREAMS_MAX_MB -- a speculative forward may try
-  // its luck inside that budget, an exact one then goes without streams.
-  size_t chunk_cap = 0;
-  bool no_fit = false;   // the lists of an earlier view at this (device, W, H) exceeded the stream budget (set below, once per forward)
-  auto alloc_image = [&](size_t capacity, float weighted_size, const Hint& hint, bool overflow_is_detected) -> bool {
-    bool streams = streams_allowed && use_streams(sw, (long long)capacity, P, weighted_size) && !(no_fit && sw.streams < 0);
-    chunk_cap = 0;
-    if (streams) {
-      const size_t safe = stream_chunk_capacity_safe(std::max<size_t>(capacity, 1), (size_t)ntiles);
-      const size_t budget = sw.streams_max_bytes / (kChunkWords * sizeof(uint32_t));
-      chunk_cap = (overflow_is_detected && hint.chunks) ? std::min(safe, (size_t)hint.chunks + hint.chunks / 4 + 4096) : safe;
-      if (overflow_is_detected && sw.speculate_chunks > 0) chunk_cap = (size_t)sw.speculate_chunks;
-      if (chunk_cap > budget) chunk_cap = overflow_is_detected ? budget : 0;
-      if (chunk_cap > 0xFFFFFFF0ull) chunk_cap = 0xFFFFFFF0ull;   // chunk indices are 32-bit (0.8 TB of lists)
-      streams = chunk_cap != 0;
-    }
-    const size_t plain = ImageState::carve(nullptr, (size_t)cam.W, (size_t)cam.H, 0).total;
-    void* iptr = image_alloc(image_user, ImageState::carve(nullptr, (size_t)cam.W, (size_t)cam.H, chunk_cap).total);
-    if (!iptr && streams) {   // the stream-sized state did not fit: the tile-wide formulation needs none of it
-      streams = false; chunk_cap = 0;
-      iptr = image_alloc(image_user, plain);
-    }
-    if (!iptr) return false;
-    is = ImageState::carve(iptr, (size_t)cam.W, (size_t)cam.H, chunk_cap);
-    if (!streams) is.blk_chunks = nullptr;
-    note_stream_image(iptr, streams);
-    g_last_forward_streams = streams ? 1 : 0;
-    return true;
-  };
-
-  // RADEGS_PRIMS=rocprim selects the device-library scan/sort (kept as a cross-check of the hand-written ones)
-  const bool use_rocprim = sw.rocprim;
-  if (use_rocprim && !prims_check().ok) return fail(RADEGS_ERR_INVALID_ARG, "RADEGS_PRIMS=rocprim: libradegs_prims_check.so (test-only) is not next to the library");
-  static const PrimsCheck no_check;
-  const PrimsCheck& pc = use_rocprim ? prims_check() : no_check;
-  size_t gtemp = std::max(sort_temp_bytes((size_t)P), scan_temp_bytes((size_t)P));
-  if (use_rocprim) gtemp = std::max(gtemp, pc.temp_geom((size_t)P));
-  const size_t gbytes = GeomState::carve(nullptr, (size_t)P, coord, gtemp).total;
-  void* gptr = geom_alloc(geom_user, gbytes);
-  if (!gptr) return fail(RADEGS_ERR_ALLOC, "geometry buffer allocation failed");
-  gs = GeomState::carve(gptr, (size_t)P, coord, gtemp);
-
-  const int tile_bits = (int)higher_msb((uint32_t)ntiles);
-  // packed tile rectangles (8 bits per field): gathered into depth order by the scan, read sequentially by the emission
-  const bool rect_fits = cam.gx <= 255 && cam.gy <= 255 && !use_rocprim;
-  // 16-bit tile keys (a third less sort traffic) wherever the tile id fits
-  const bool key16_ok = tile_bits <= 16 && !use_rocprim;
-  int devid = 0;
-  (void)hipGetDevice(&devid);
-  const int spec_env = sw.speculate;
-  const int hint_env = sw.speculate_hint;  // tests: force a (too small) prediction
-  const HintKey hkey{devid, cam.W, cam.H};
-  const Hint hrec = hint_load(hkey);
-  no_fit = hint_no_fit_tick(hkey);
-  uint32_t hint = hrec.R;
-  if (hint_env > 0) hint = (uint32_t)hint_env;
-  PinnedCount& pin = pinned_for(devid);
-  const bool have_pin = devid < 64 && pin.ok();
-  const bool speculative = force == 0 && spec_env != 0 && hint > 0 && !dbg && !use_rocprim && have_pin;
-  // depth sort: three 9-bit passes over (key - bits(0.2f)) instead of four 8-bit ones, valid while every visible z < 13 107 -- the
-  // preprocess flags a key outside that window in a mapped host word, looked at below (exact path) or in binning_finish (speculative
-  // path); the forward is then redone with the 4-pass sort and the (device, W, H) remembers.
-  const bool sort27 = have_pin && !use_rocprim && force != 2 && !sort32_load(hkey);
-  if (sort27) pin.h[PIN_KEY_OVERFLOW] = 0u;
-  auto alloc_binning = [&](size_t capacity) -> bool {
-    size_t btemp = sort_temp_bytes(capacity);
-    if (use_rocprim) btemp = std::max(btemp, pc.temp_bin(capacity, tile_bits));
-    void* bptr = binning_alloc(binning_user, BinState::carve(nullptr, capacity, btemp).total);
-    if (!bptr) return false;
-    bs = BinState::carve(bptr, capacity, btemp);
-    return true;
-  };
-  uint32_t cap = 0;
-  if (speculative) {
-    cap = (uint32_t)std::min<uint64_t>((uint64_t)hint + hint / 4 + 4096, 0x7FFFFFFFull);
-    if (!alloc_binning((size_t)cap)) return fail(RADEGS_ERR_ALLOC, "binning buffer allocation failed");
-    if (!alloc_image((size_t)cap, hrec.weighted_size, hrec, true)) return fail(RADEGS_ERR_ALLOC, "image buffer allocation failed");
-  }
-
-  // 1. per-Gaussian preprocess
-  {
-    StageTimer tm(ST_PRE_FWD, stream);
-    PreFwdArgs pa;
-    pa.P = P; pa.D = G.D; pa.M = G.M;
-    pa.means3D = G.means3D; pa.scales = G.scales; pa.rotations = G.rotations; pa.cov3D_precomp = G.cov3D_precomp;
-    pa.opacities = G.opacities; pa.shs = G.shs; pa.colors_precomp = G.colors_precomp;
-    pa.cam = cam; pa.write_b = coord ? 1 : 0;
-    pa.radii = G.radii; pa.inte_rec = inte_rec; pa.splat_a = reinterpret_cast<float4*>(gs.splat_a); pa.splat_b = reinterpret_cast<float4*>(gs.splat_b);
-    pa.tiles_touched = gs.tiles_touched; pa.depth_key = gs.depth_key; pa.clamped = gs.clamped; pa.rect = gs.rect;
-    pa.key_overflow = sort27 ? pin.dev() + PIN_KEY_OVERFLOW : nullptr;
-    if (inte_rec) hipLaunchKernelGGL(preprocess_fwd_kernel<true>, dim3((P + 255) / 256), dim3(256), 0, stream, pa);
-    else hipLaunchKernelGGL(preprocess_fwd_kernel<false>, dim3((P + 255) / 256), dim3(256), 0, stream, pa);
-    RG_LAUNCH_CHECK("preprocess_fwd_kernel", dbg, stream);
-  }
-  const uint32_t* R_dev = nullptr;
-  {
-    // 2. depth order of the Gaussians, 3. instance offsets in that order
-    {
-      StageTimer tm(ST_SORT_DEPTH, stream);
-      if (use_rocprim) RG_HIP(pc.sort_by_depth(gs.temp, gs.temp_bytes, gs.depth_key, gs.depth_key_sorted, gs.idx_sorted, (size_t)P, stream));
-      else if (sort27) RG_HIP(radix_sort_pairs_u32_27(gs.temp, gs.temp_bytes, gs.depth_key, gs.depth_key_sorted, nullptr, gs.idx_sorted, (size_t)P, kDepthKeyBase, stream));
-      else RG_HIP(radix_sort_pairs_u32(gs.temp, gs.temp_bytes, gs.depth_key, gs.depth_key_sorted, nullptr, gs.idx_sorted, (size_t)P, 32, stream));
-    }
-    {
-      StageTimer tm(ST_SCAN, stream);
-      if (use_rocprim) RG_HIP(pc.scan(gs.temp, gs.temp_bytes, gs.tiles_touched, gs.idx_sorted, gs.offsets, (size_t)P, stream));
-      else if (rect_fits) RG_HIP(inclusive_scan_gather_u32(gs.temp, gs.temp_bytes, gs.rect, gs.idx_sorted, gs.offsets, (size_t)P, stream, gs.rect_sorted, gs.tile_sq_sum));
-      else RG_HIP(inclusive_scan_gather_u32(gs.temp, gs.temp_bytes, gs.tiles_touched, gs.idx_sorted, gs.offsets, (size_t)P, stream, nullptr, gs.tile_sq_sum));
-    }
-    R_dev = gs.offsets + (P - 1);
-  }
-
-  // 5-7 for a given capacity of the instance arrays; n_dev != nullptr: the real count is read on the device
-  auto queue_instances = [&](uint32_t capacity, const uint32_t* n_dev, uint32_t* count_mirror, uint32_t seq) -> int {
-    // scenes of 2^24 Gaussians and more with entry streams: the block mask rides in the top byte of a 32-bit tile KEY instead of the value's
-    const bool mask_in_key = is.blk_chunks != nullptr && mask_rides_in_key(sw, P);
-    const bool key16 = key16_ok && !mask_in_key;
-    {
-      StageTimer tm(ST_EMIT, stream);
-      // with entry streams every instance also learns which blocks of its tile it can reach (top byte of the value); the kernel also
-      // clears the tile ranges and mirrors num_rendered into the host's pinned word (count_mirror, speculative path)
-      if (is.blk_chunks)
-        hipLaunchKernelGGL(emit_instances_kernel<true>, dim3((P + 255) / 256), dim3(256), 0, stream, P, gs.idx_sorted, gs.offsets,
-                           gs.tiles_touched, reinterpret_cast<const float4*>(gs.splat_a), G.radii, rect_fits ? gs.rect_sorted : nullptr,
-                           cam.gx, cam.gy, bs.tile_keys, bs.point_list_unsorted, capacity, is.ranges, count_mirror, seq, is.stream_tag, key16 ? 1 : 0,
-                           mask_in_key ? 1 : 0, gs.tile_sq_sum);
-      else
-        hipLaunchKernelGGL(emit_instances_kernel<false>, dim3((P + 255) / 256), dim3(256), 0, stream, P, gs.idx_sorted, gs.offsets,
-                           gs.tiles_touched, reinterpret_cast<const float4*>(gs.splat_a), G.radii, rect_fits ? gs.rect_sorted : nullptr,
-                           cam.gx, cam.gy, bs.tile_keys, bs.point_list_unsorted, capacity, is.ranges, count_mirror, seq, is.stream_tag, key16 ? 1 : 0,
-                           mask_in_key ? 1 : 0, gs.tile_sq_sum);
-      RG_LAUNCH_CHECK("emit_instances_kernel", dbg, stream);
-    }
-    {
-      StageTimer tm(ST_SORT_TILE, stream);
-      if (use_rocprim)
-        RG_HIP(pc.sort_by_tile(bs.temp, bs.temp_bytes, bs.tile_keys, bs.tile_keys_sorted, bs.point_list_unsorted, bs.point_list, (size_t)capacity,
-                            tile_bits, stream));
-      else if (key16)
-        RG_HIP(radix_sort_pairs_u16(bs.temp, bs.temp_bytes, reinterpret_cast<const uint16_t*>(bs.tile_keys), reinterpret_cast<uint16_t*>(bs.tile_keys_sorted),
-                                    bs.point_list_unsorted, bs.point_list, (size_t)capacity, tile_bits, stream, n_dev));
-      else
-        RG_HIP(radix_sort_pairs_u32(bs.temp, bs.temp_bytes, bs.tile_keys, bs.tile_keys_sorted, bs.point_list_unsorted, bs.point_list,
-                                    (size_t)capacity, tile_bits, stream, n_dev));
-    }
-    {
-      StageTimer tm(ST_RANGES, stream);
-      if (key16)   // 8 keys per thread
-        hipLaunchKernelGGL(tile_ranges_kernel<uint16_t>, dim3((capacity + 8 * kRangeThreads - 1) / (8 * kRangeThreads)), dim3(kRangeThreads), 0, stream,
-                           (int)capacity, reinterpret_cast<const uint16_t*>(bs.tile_keys_sorted), reinterpret_cast<uint2*>(is.ranges), n_dev, 0xFFFFu,
-                           (int)capacity);
-      else         // 4 keys per thread
-        hipLaunchKernelGGL(tile_ranges_kernel<uint32_t>, dim3((capacity + 4 * kRangeThreads - 1) / (4 * kRangeThreads)), dim3(kRangeThreads), 0, stream,
-                           (int)capacity, bs.tile_keys_sorted, reinterpret_cast<uint2*>(is.ranges), n_dev, mask_in_key ? kGidMask : 0xFFFFFFFFu,
-                           (int)capacity);
-      RG_LAUNCH_CHECK("tile_ranges_kernel", dbg, stream);
-    }
-    return 0;
-  };
-
-  if (speculative) {
-    // 4'. num_rendered leaves for the host without a wait; 5-7 run for the predicted capacity
-    const uint32_t seq = ++pin.seq;
-    const int rc = queue_instances(cap, R_dev, pin.dev(), seq);
+// Stages 1-7 (preprocess and binning) of a forward or integrate, and for a forward (A != nullptr) 7b-8 (lists and blend); returns
+// num_rendered or < 0.  Each attempt is planned, allocates and queues the stages; a speculative one queues the blend too before the
+// host looks at its counts.  An attempt that did not fit is redone from the start, once its work has drained.
+static int bin_and_blend(Binning& B, const RadegsFwdArgs* A) {
+  Outcome prev = kFits;
+  for (;;) {
+    Plan p;
+    Outcome out = kFits;
+    int rc = plan_attempt(B, prev, p);
     if (rc < 0) return rc;
-    BinPending p;
-    p.pending = true; p.cap = cap; p.hint = hint; p.seq = seq; p.key = hkey; p.hint_forced = hint_env > 0; p.sort27 = sort27; p.stream = stream;
-    p.streams = is.blk_chunks != nullptr; p.chunk_cap = chunk_cap;
-    if (pend) { *pend = p; return (int)cap; }   // the caller queues the rest of the forward before looking at the counts
-    int R = 0;
-    const int st = binning_finish(p, &R);
-    if (st <= 0) return st < 0 ? st : R;
-    RG_HIP(hipStreamSynchronize(stream));   // prediction too small: redo with exact sizes
-    return geometry_and_binning(G, cam, coord, inte_rec, geom_alloc, geom_user, binning_alloc, binning_user, image_alloc, image_user,
-                                streams_allowed, dbg, stream, gs, bs, is, nullptr, st);
+    if ((rc = alloc_geometry(B, p)) < 0) return rc;
+    if (p.speculative && (rc = alloc_binning(B, p, p.cap, p.hist.weighted_size)) < 0) return rc;   // before the first launch
+    if ((rc = queue_geometry(B, p)) < 0) return rc;
+    if (!p.speculative && (rc = size_exact(B, p, out)) < 0) return rc;
+    if (out == kFits) {
+      if ((rc = queue_instances(B, p)) < 0) return rc;
+      if (A && (rc = queue_blend(B, p, A)) < 0) return rc;
+      if (p.speculative && (rc = finish_speculative(B, p, out)) < 0) return rc;
+      if (out == kFits) return (int)B.R;
+    }
+    if (p.speculative) RG_HIP(hipStreamSynchronize(B.stream));   // (an exact attempt has synchronised already)
+    prev = out;
   }
-
-  // 4. exact sizes: the one host sync of the reference's forward -- num_rendered sizes the binning buffer (rasterizer_impl.cu:354)
-  uint32_t R32 = 0;
-  unsigned long long sq = 0ull;
-  RG_HIP(hipMemcpyAsync(&R32, R_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-  if (!use_rocprim) RG_HIP(hipMemcpyAsync(&sq, gs.tile_sq_sum, sizeof(sq), hipMemcpyDeviceToHost, stream));
-  RG_HIP(hipStreamSynchronize(stream));
-  if (sort27 && pin.h[PIN_KEY_OVERFLOW] != 0u) {   // a visible depth key outside the 3-pass sort's window: the order is not to be trusted
-    sort32_store(hkey);
-    return geometry_and_binning(G, cam, coord, inte_rec, geom_alloc, geom_user, binning_alloc, binning_user, image_alloc, image_user,
-                                streams_allowed, dbg, stream, gs, bs, is, pend, 2);
-  }
-  if (R32 > 0x7FFFFFFFu) return fail(RADEGS_ERR_INVALID_ARG, "num_rendered overflows int32");
-  const float weighted_size = (R32 && !use_rocprim) ? (float)((double)sq / (double)R32) : 0.0f;
-  if (hint_env <= 0) hint_store(hkey, std::max(R32, hint - hint / 64), weighted_size);
-  const int R = (int)R32;
-  if (!alloc_binning((size_t)R)) return fail(RADEGS_ERR_ALLOC, "binning buffer allocation failed");
-  if (!alloc_image((size_t)R, weighted_size, hint_load(hkey), false)) return fail(RADEGS_ERR_ALLOC, "image buffer allocation failed");
-  if (pend) { *pend = BinPending(); pend->streams = is.blk_chunks != nullptr; pend->chunk_cap = chunk_cap; pend->key = hkey; }
-  if (R > 0) {
-    const int rc = queue_instances((uint32_t)R, nullptr, nullptr, 0u);
-    if (rc < 0) return rc;
-  } else {
-    RG_HIP(hipMemsetAsync(is.ranges, 0, (size_t)ntiles * 2 * sizeof(uint32_t), stream));
-    RG_HIP(hipMemsetAsync(is.stream_tag, 0, 4 * sizeof(uint32_t), stream));
-  }
-  return R;
 }
 
 }  // namespace rg
@@ -639,110 +722,25 @@ int radegs_forward(const RadegsFwdArgs* A, radegs_alloc_fn geom_alloc, void* geo
   if (!A || !geom_alloc || !binning_alloc || !image_alloc) return fail(RADEGS_ERR_INVALID_ARG, "null argument");
   if (A->P < 0 || A->width <= 0 || A->height <= 0) return fail(RADEGS_ERR_INVALID_ARG, "bad sizes");
   if (A->P == 0) return 0;  // rasterize_points.cu:90: nothing is launched
-  if (!A->means3D || !A->opacities || !A->viewmatrix || !A->projmatrix || !A->cam_pos || !A->background || !A->radii ||
-      !A->out_color || !A->out_alpha)
-    return fail(RADEGS_ERR_INVALID_ARG, "missing required tensor");
-  if ((A->shs == nullptr) == (A->colors_precomp == nullptr))
-    return fail(RADEGS_ERR_INVALID_ARG, "Please provide excatly one of either SHs or precomputed colors!");
-  if (((A->scales == nullptr) || (A->rotations == nullptr)) == (A->cov3D_precomp == nullptr))
-    return fail(RADEGS_ERR_INVALID_ARG, "Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!");
+  int rc = check_gaussians(A, A->means3D && A->opacities && A->viewmatrix && A->projmatrix && A->cam_pos && A->background && A->radii &&
+                                  A->out_color && A->out_alpha, true);
+  if (rc < 0) return rc;
   if (A->prefiltered) return fail(RADEGS_ERR_INVALID_ARG, "prefiltered=True is not supported (it selects the integrate path upstream)");
   if (A->shs && (A->D + 1) * (A->D + 1) > A->M) return fail(RADEGS_ERR_INVALID_ARG, "sh_degree needs more SH rows than provided");
   const bool coord = A->require_coord != 0, depth = A->require_depth != 0;
   if (coord && (!A->out_coord || !A->out_mcoord)) return fail(RADEGS_ERR_INVALID_ARG, "coord outputs missing");
   if (depth && (!A->out_depth || !A->out_mdepth)) return fail(RADEGS_ERR_INVALID_ARG, "depth outputs missing");
   if ((coord || depth) && !A->out_normal) return fail(RADEGS_ERR_INVALID_ARG, "normal output missing");
-  hipStream_t stream = static_cast<hipStream_t>(stream_v);
-  const bool dbg = A->debug != 0;
-  const int P = A->P, W = A->width, H = A->height;
-  {
-    int devid = 0;
-    (void)hipGetDevice(&devid);
-    const int rc = check_stream_error(devid);
-    if (rc < 0) return rc;
-  }
-  const CamArgs cam = make_cam(A->viewmatrix, A->projmatrix, A->cam_pos, W, H, A->tan_fovx, A->tan_fovy, A->kernel_size, A->scale_modifier);
-  const int ntiles = cam.gx * cam.gy;
-  ImageState is;
-  GaussIn G;
-  G.P = P; G.D = A->D; G.M = A->M; G.means3D = A->means3D; G.scales = A->scales; G.rotations = A->rotations;
-  G.cov3D_precomp = A->cov3D_precomp; G.opacities = A->opacities; G.shs = A->shs; G.colors_precomp = A->colors_precomp; G.radii = A->radii;
-  GeomState gs;
-  BinState bs;
-  BinPending pend;
-  int R = geometry_and_binning(G, cam, coord, nullptr, geom_alloc, geom_user, binning_alloc, binning_user, image_alloc, image_user,
-                               true, dbg, stream, gs, bs, is, &pend);
-  if (R < 0) return R;
-  // 7b + 8: sub-tile entry lists and the blend, queued behind the binning
-  auto queue_blend = [&]() -> int {
-  const bool streams = is.blk_chunks != nullptr;
-  uint32_t* const pin_words = pend.pending ? pinned_for(pend.key.dev).dev() : nullptr;   // a speculative forward reports to the host's mapped words
-  if (streams) {  // 7b. sub-tile entry lists (rg_streams.inc)
-    StageTimer tm(ST_BLOCK_LISTS, stream);
-    BlockListArgs la;
-    la.ranges = reinterpret_cast<const uint2*>(is.ranges); la.point_list = bs.point_list; la.keys_sorted = bs.tile_keys_sorted;
-    la.gx = cam.gx; la.ntiles = ntiles;
-    la.blk_count = is.blk_count; la.blk_base = is.blk_base; la.blk_chunks = is.blk_chunks;
-    la.wg_need = is.wg_need; la.stream_meta = is.stream_tag; la.chunk_capacity = (uint32_t)pend.chunk_cap;
-    // a grid that fills the chip once (8 workgroups of 4 waves per CU), a multiple of 8 so that tiles keep their XCD
-    const int list_grid = std::min(ntiles, kListGridMax);
-    // block_lists_kernel's FIRST workgroups sort the blocks of every 64-tile neighbourhood by list length (balance_blocks needs the counts
-    // only): their number rounded up to a multiple of 8, so that a list-building workgroup runs on the XCD block_counts_kernel's ran on
-    const int nblocks = ntiles * kBlocksPerTile;
-    const int bal_groups = (((nblocks + kBalanceBlocks - 1) / kBalanceBlocks) + 7) & ~7;
-    la.list_grid = list_grid; la.bal_groups = bal_groups; la.blk_order = is.blk_order;
-    la.pin_chunks = pin_words ? pin_words + PIN_CHUNKS : nullptr; la.pin_seq = pin_words ? pin_words + PIN_SEQ : nullptr; la.seq = pend.seq;
-    if (mask_rides_in_key(switches(), P)) {
-      hipLaunchKernelGGL(block_counts_kernel<true>, dim3(list_grid), dim3(kListThreads), 0, stream, la);
-      hipLaunchKernelGGL(block_lists_kernel<true>, dim3(bal_groups + list_grid), dim3(kListThreads), 0, stream, la);
-    } else {
-      hipLaunchKernelGGL(block_counts_kernel<false>, dim3(list_grid), dim3(kListThreads), 0, stream, la);
-      hipLaunchKernelGGL(block_lists_kernel<false>, dim3(bal_groups + list_grid), dim3(kListThreads), 0, stream, la);
-    }
-    RG_LAUNCH_CHECK("block_lists_kernel", dbg, stream);
-  }
-  // 8. blend
-  {
-    StageTimer tm(ST_BLEND_FWD, stream);
-    BlendFwdArgs ba;
-    ba.ranges = reinterpret_cast<const uint2*>(is.ranges); ba.point_list = bs.point_list;
-    ba.splat_a = reinterpret_cast<const float4*>(gs.splat_a); ba.splat_b = reinterpret_cast<const float4*>(gs.splat_b);
-    ba.W = W; ba.H = H; ba.gx = cam.gx; ba.ntiles = ntiles; ba.focal_x = cam.focal_x; ba.focal_y = cam.focal_y;
-    ba.bg = A->background;
-    ba.out_color = A->out_color; ba.out_coord = A->out_coord; ba.out_mcoord = A->out_mcoord; ba.out_depth = A->out_depth;
-    ba.out_mdepth = A->out_mdepth; ba.out_alpha = A->out_alpha; ba.out_normal = A->out_normal;
-    ba.n_contrib = is.n_contrib; ba.accum_coord = is.accum_coord; ba.accum_depth = is.accum_depth; ba.normal_length = is.normal_length;
-    ba.blk_count = is.blk_count; ba.blk_base = is.blk_base; ba.blk_consumed = is.blk_consumed; ba.blk_chunks = is.blk_chunks; ba.blk_order = is.blk_order;
-    if (streams) {
-      if (coord && depth) hipLaunchKernelGGL((blend_fwd_streams_kernel<true, true>), dim3(ntiles * 2), dim3(64), 0, stream, ba);
-      else if (coord) hipLaunchKernelGGL((blend_fwd_streams_kernel<true, false>), dim3(ntiles * 2), dim3(64), 0, stream, ba);
-      else if (depth) hipLaunchKernelGGL((blend_fwd_streams_kernel<false, true>), dim3(ntiles * 2), dim3(64), 0, stream, ba);
-      else hipLaunchKernelGGL((blend_fwd_streams_kernel<false, false>), dim3(ntiles * 2), dim3(64), 0, stream, ba);
-    } else {   // tile-wide: one wave per 16x8 strip, 2 pixels per lane (measured best on every BASELINE config)
-      if (coord && depth) hipLaunchKernelGGL((blend_fwd_kernel<true, true, 2>), dim3(ntiles * 2), dim3(64), 0, stream, ba);
-      else if (coord) hipLaunchKernelGGL((blend_fwd_kernel<true, false, 2>), dim3(ntiles * 2), dim3(64), 0, stream, ba);
-      else if (depth) hipLaunchKernelGGL((blend_fwd_kernel<false, true, 2>), dim3(ntiles * 2), dim3(64), 0, stream, ba);
-      else hipLaunchKernelGGL((blend_fwd_kernel<false, false, 2>), dim3(ntiles * 2), dim3(64), 0, stream, ba);
-    }
-    RG_LAUNCH_CHECK("blend_fwd_kernel", dbg, stream);
-  }
-    return 0;
-  };
-  int rc = queue_blend();
-  if (rc < 0) return rc;
-  if (pend.pending) {   // only now does the host look at the counts of the speculative binning
-    const int st = binning_finish(pend, &R);
-    if (st < 0) return st;
-    if (st > 0) {       // prediction too small: everything again with exact sizes
-      RG_HIP(hipStreamSynchronize(stream));
-      R = geometry_and_binning(G, cam, coord, nullptr, geom_alloc, geom_user, binning_alloc, binning_user, image_alloc, image_user, true, dbg,
-                               stream, gs, bs, is, &pend, st);
-      if (R < 0) return R;
-      rc = queue_blend();
-      if (rc < 0) return rc;
-    }
-  }
-  return R;
+  int devid = 0;
+  (void)hipGetDevice(&devid);
+  if ((rc = check_stream_error(devid)) < 0) return rc;
+  Binning B;
+  B.G = gauss_in(A);
+  B.cam = make_cam(A->viewmatrix, A->projmatrix, A->cam_pos, A->width, A->height, A->tan_fovx, A->tan_fovy, A->kernel_size, A->scale_modifier);
+  B.coord = coord;
+  B.geom = {geom_alloc, geom_user}; B.bin = {binning_alloc, binning_user}; B.image = {image_alloc, image_user};
+  B.streams_allowed = true; B.dbg = A->debug != 0; B.stream = static_cast<hipStream_t>(stream_v);
+  return bin_and_blend(B, A);
 }
 
 // The per-Gaussian backward (computeCov2DCUDA + preprocessCUDA bwd, backward.cu:145-628) over the records `acc`; acc_final: the records
@@ -853,19 +851,16 @@ int radegs_backward(const RadegsBwdArgs* A, radegs_alloc_fn accum_alloc, void* a
     constexpr uint64_t kStreamBwdMaxAccBytes = 0xFFFFFFFFull;
     const bool acc_fits = (uint64_t)A->P * (uint64_t)((coord ? 32 : 16) * sizeof(float)) <= kStreamBwdMaxAccBytes;
     if (image_has_streams(A->image_buffer) && sw.streams_bwd && acc_fits) {
-      if (coord && depth) hipLaunchKernelGGL((blend_bwd_streams_kernel<true, true>), dim3(ntiles * 2), dim3(64), 0, stream, ba);
-      else if (coord) hipLaunchKernelGGL((blend_bwd_streams_kernel<true, false>), dim3(ntiles * 2), dim3(64), 0, stream, ba);
-      else if (depth) hipLaunchKernelGGL((blend_bwd_streams_kernel<false, true>), dim3(ntiles * 2), dim3(64), 0, stream, ba);
-      else hipLaunchKernelGGL((blend_bwd_streams_kernel<false, false>), dim3(ntiles * 2), dim3(64), 0, stream, ba);
+      dispatch(coord, depth, [&](auto c, auto d) { hipLaunchKernelGGL((blend_bwd_streams_kernel<c, d>), dim3(ntiles * 2), dim3(64), 0, stream, ba); });
     } else {
       // one wave per 16x8 strip (2 pixels per lane); one wave per tile (4 per lane) once every entry covers the tile anyway: within 1 %
       // either way up to 200 tiles per Gaussian on synthetic scenes, -8 % on C5 (4K, heavy overdraw: 4.41 against 4.80 ms); never with
       // the coord map (+5 %)
       const int ppl = (sw.bwd_ppl == 2 || sw.bwd_ppl == 4) ? sw.bwd_ppl : ((!coord && (long long)R >= 64ll * P) ? 4 : 2);
-      if (coord && depth) launch_blend_bwd<true, true>(ppl, ntiles, ba, stream);
-      else if (coord) launch_blend_bwd<true, false>(ppl, ntiles, ba, stream);
-      else if (depth) launch_blend_bwd<false, true>(ppl, ntiles, ba, stream);
-      else launch_blend_bwd<false, false>(ppl, ntiles, ba, stream);
+      dispatch(coord, depth, [&](auto c, auto d) {
+        if (ppl == 2) hipLaunchKernelGGL((blend_bwd_packed_kernel<c, d, 2>), dim3(ntiles * 2), dim3(64), 0, stream, ba);
+        else hipLaunchKernelGGL((blend_bwd_packed_kernel<c, d, 4>), dim3(ntiles), dim3(64), 0, stream, ba);
+      });
     }
     RG_LAUNCH_CHECK("blend_bwd_kernel", dbg, stream);
   }
@@ -887,9 +882,8 @@ int radegs_backward_from_sums(const RadegsBwdArgs* A, const float* sums, void* s
   if (!A->dL_dmean2D || !A->dL_dcolor || !A->dL_dopacity || !A->dL_dmean3D || !A->dL_dcov3D || !A->dL_dscale || !A->dL_drot)
     return fail(RADEGS_ERR_INVALID_ARG, "gradient outputs missing");
   if (A->shs && !A->dL_dsh) return fail(RADEGS_ERR_INVALID_ARG, "dL_dsh missing");
-  if (!A->radii || !A->means3D || !A->viewmatrix || !A->projmatrix || !A->cam_pos) return fail(RADEGS_ERR_INVALID_ARG, "missing required tensor");
-  if (((A->scales == nullptr) || (A->rotations == nullptr)) == (A->cov3D_precomp == nullptr))
-    return fail(RADEGS_ERR_INVALID_ARG, "Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!");
+  const int rc = check_gaussians(A, A->radii && A->means3D && A->viewmatrix && A->projmatrix && A->cam_pos, false);
+  if (rc < 0) return rc;
   if (reinterpret_cast<uintptr_t>(sums) & 15u) return fail(RADEGS_ERR_INVALID_ARG, "sums must be 16-byte aligned");
   hipStream_t stream = static_cast<hipStream_t>(stream_v);
   const bool coord = A->require_coord != 0;
@@ -923,30 +917,27 @@ int radegs_integrate(const RadegsIntegrateArgs* A, radegs_alloc_fn geom_alloc, v
     }
     return 0;
   }
-  if (!A->means3D || !A->opacities || !A->viewmatrix || !A->projmatrix || !A->cam_pos || !A->background || !A->points3D)
-    return fail(RADEGS_ERR_INVALID_ARG, "missing required tensor");
-  if ((A->shs == nullptr) == (A->colors_precomp == nullptr))
-    return fail(RADEGS_ERR_INVALID_ARG, "Please provide excatly one of either SHs or precomputed colors!");
-  if (((A->scales == nullptr) || (A->rotations == nullptr)) == (A->cov3D_precomp == nullptr))
-    return fail(RADEGS_ERR_INVALID_ARG, "Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!");
+  const int rc = check_gaussians(A, A->means3D && A->opacities && A->viewmatrix && A->projmatrix && A->cam_pos && A->background && A->points3D,
+                                 true);
+  if (rc < 0) return rc;
   if (A->shs && (A->D + 1) * (A->D + 1) > A->M) return fail(RADEGS_ERR_INVALID_ARG, "sh_degree needs more SH rows than provided");
   const CamArgs cam = make_cam(A->viewmatrix, A->projmatrix, A->cam_pos, W, H, A->tan_fovx, A->tan_fovy, A->kernel_size, A->scale_modifier);
   const int ntiles = cam.gx * cam.gy;
-  ImageState is;
   const size_t ptemp = scan_temp_bytes(HW);
   const size_t pbytes = PointState::carve(nullptr, (size_t)P, (size_t)PN, HW, ptemp).total;
   void* pptr = point_alloc(point_user, pbytes);
   if (!pptr) return fail(RADEGS_ERR_ALLOC, "point buffer allocation failed");
   PointState ps = PointState::carve(pptr, (size_t)P, (size_t)PN, HW, ptemp);
 
-  GaussIn G;
-  G.P = P; G.D = A->D; G.M = A->M; G.means3D = A->means3D; G.scales = A->scales; G.rotations = A->rotations;
-  G.cov3D_precomp = A->cov3D_precomp; G.opacities = A->opacities; G.shs = A->shs; G.colors_precomp = A->colors_precomp; G.radii = A->radii;
-  GeomState gs;
-  BinState bs;
-  const int R = geometry_and_binning(G, cam, false, reinterpret_cast<float4*>(ps.inte_rec), geom_alloc, geom_user, binning_alloc,
-                                     binning_user, image_alloc, image_user, false, dbg, stream, gs, bs, is);
+  Binning B;
+  B.G = gauss_in(A); B.cam = cam; B.inte_rec = reinterpret_cast<float4*>(ps.inte_rec);
+  B.geom = {geom_alloc, geom_user}; B.bin = {binning_alloc, binning_user}; B.image = {image_alloc, image_user};
+  B.dbg = dbg; B.stream = stream;
+  const int R = bin_and_blend(B, nullptr);
   if (R < 0) return R;
+  const GeomState& gs = B.gs;
+  const BinState& bs = B.bs;
+  const ImageState& is = B.is;
 
   // query points: project, count per pixel, scan, scatter (a counting sort on the pixel index)
   RG_HIP(hipMemsetAsync(ps.pix_count, 0, HW * sizeof(uint32_t), stream));

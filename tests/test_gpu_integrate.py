@@ -115,13 +115,28 @@ def test_integrate_empty_inputs():
     assert close(got[0], ref[0]).all()
 
 
-def test_integrate_debug_mode_and_determinism():
+def test_integrate_debug_mode_and_determinism(monkeypatch):
+    """Debug mode (a sync after every launch), the exact binning and a speculative one whose forced prediction is far too small (the
+    integrate is redone with exact sizes) all give the same result."""
+    import diff_gaussian_rasterization._C as C
     s = make_scene(3000, 128, 96, sh_degree=1, mu_px=4.0, seed=36, kernel_size=0.0, pose="random", require_coord=False, require_depth=True)
     pts = _points(s, 10000, 6)
     R1, a, _ = _run(s, pts, debug=True)
     R2, b, _ = _run(s, pts)
     assert R1 == R2
     for x, y in zip(a, b):
+        assert np.array_equal(x, y, equal_nan=True)
+    runs = []
+    for env in (dict(RADEGS_SPECULATE="0"), dict(RADEGS_SPECULATE="1", RADEGS_SPECULATE_HINT="1000")):   # R1 is ~30 000
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        C.reload_env()
+        C.binning_stats(reset=True)
+        runs.append(_run(s, pts)[:2])
+        stats = C.binning_stats()
+    assert stats == (2, 2), stats   # both integrate calls of _run were speculative and redone
+    assert runs[0][0] == runs[1][0] == R1
+    for x, y in zip(runs[0][1], runs[1][1]):
         assert np.array_equal(x, y, equal_nan=True)
 
 

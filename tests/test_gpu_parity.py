@@ -408,17 +408,36 @@ def test_handwritten_sort_matches_device_library():
     assert outs[0] == outs[1], outs
 
 
-def test_depths_beyond_the_three_pass_sort_window():
+def test_depths_beyond_the_three_pass_sort_window(monkeypatch):
     """The depth sort runs three 9-bit passes over (key - bits(0.2f)), valid while every visible depth is below 13 107; the per-Gaussian
     kernel flags a key outside that window and the forward is redone with the four-pass sort (rg_launch.inc).  A scene scaled 3 000x
-    (depths 6 000 ... 30 000) takes that path on its first frame, the remembered 4-pass sort on the next; both must equal the oracle."""
+    (depths 6 000 ... 30 000) takes that path on its first frame, the remembered 4-pass sort on the next; both must equal the oracle.
+    At a (W, H) whose history the unscaled scene seeded, the first far frame is speculative: it is redone straight with the 4-pass sort
+    and must equal the RADEGS_SPECULATE=0 forward."""
     import diff_gaussian_rasterization._C as C
+    from gpu_util import HipRun
     s = make_scene(3000, 176, 144, sh_degree=1, mu_px=3.0, seed=77, kernel_size=0.0, require_coord=False, require_depth=True)
     s = s._replace(means3D=s.means3D * 3000.0, scales=s.scales * 3000.0)
     C.binning_stats(reset=True)
     o, _ = check_forward(s)
     check_backward(s, o, seed=77)
     o, _ = check_forward(s)          # the (device, W, H) remembers: no redo any more, same result
+
+    near = make_scene(3000, 192, 144, sh_degree=1, mu_px=3.0, seed=77, kernel_size=0.0, require_coord=False, require_depth=True)
+    far = near._replace(means3D=near.means3D * 3000.0, scales=near.scales * 3000.0)
+    monkeypatch.setenv("RADEGS_SPECULATE", "1")
+    C.reload_env()
+    HipRun(near, _dev()).forward_native()   # history at 192 x 144: a prediction that holds far's instances, the 3-pass sort
+    C.binning_stats(reset=True)
+    spec = HipRun(far, _dev()).forward_native()
+    torch.cuda.synchronize()
+    assert C.binning_stats() == (1, 1)     # one speculative forward, redone
+    monkeypatch.setenv("RADEGS_SPECULATE", "0")
+    C.reload_env()
+    exact = HipRun(far, _dev()).forward_native()
+    assert spec[0] == exact[0]
+    for a, b in zip(spec[1:9], exact[1:9]):
+        assert torch.equal(a, b)
 
 
 def test_very_long_tile_lists():
