@@ -370,6 +370,53 @@ int radegs_adam_step(int count, const RadegsAdamTensor* tensors, double beta1, d
 size_t radegs_knn_scratch_bytes(int P);
 int radegs_knn_mean_dist2(int P, const float* points, void* scratch, float* out /* [P] */, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Adaptive density control: the stage of the training iteration after the backward.  All pointers:
+ * device; float32 unless typed otherwise.
+ *
+ * radegs_densify_stats: GaussianModel.add_densification_stats (scene/gaussian_model.py:743-747) and train.py:186's
+ * max_radii2D update for one view, in place, one launch, no host read.  grad_means2D: [P,3] (xy signed, column 2 the
+ * abs-gradient).  visible: [P] bytes, or NULL = radii > 0 (then radii is required).  For each visible row
+ *   accum += sqrt(gx^2+gy^2); accum_abs += |g2|; accum_abs_max = max(., |g2|); denom += 1; max_radii2D = max(., radii)
+ * (max_radii2D or radii NULL: that line is skipped).  Invisible rows are not written.
+ * radegs_densify_stats_reduced: the same update from view_parallel's rank-reduced [P,3] statistics (sum |grad xy|,
+ * sum |grad abs|, number of ranks that saw the Gaussian) and radii_max; rows whose count is 0 are not written;
+ * accum_abs_max takes the max with the SUM column (the per-rank maximum is not transmitted).
+ *
+ * GaussianModel.densify_and_prune (scene/gaussian_model.py:717-741) is plan + apply around the one host read it needs:
+ *   radegs_densify_plan   every clone / split / prune decision and the index of every surviving output row.
+ *       abs_threshold: DEVICE scalar Q (upstream's torch.quantile);  dense_threshold = percent_dense * extent;
+ *       prune_big != 0: also prune max(exp(_scaling)) > big_threshold (= 0.1 * extent; upstream's `if max_screen_size`).
+ *       The max_radii2D > max_screen_size term is not an input: upstream zeroes max_radii2D before it reads it.
+ *       workspace: radegs_densify_plan_bytes(P) bytes, 16-byte aligned, kept untouched until apply has run.
+ *       counts4 (device ints): {rows out, clone-selected, split-selected, pruned by the final prune} -- the last three are
+ *       upstream's return tuple.  The caller reads counts4 back, allocates, and calls
+ *   radegs_densify_apply  writes all output arrays at P_out = counts4[0] rows in upstream's row order: surviving unsplit
+ *       originals, clones, first children, second children.  unit_normals: [P,3,3] standard-normal draws indexed by source
+ *       row (slot 0 the clone, 1 / 2 the children): xyz' = xyz + R(q/|q|) (z o exp(_scaling)); children store
+ *       _scaling' = log(exp(_scaling) / 1.6); everything else is copied; moments of new rows are zero.
+ *       tensors: [0..5] xyz[P,3] f_dc[P,3] f_rest[P,rest_floats] opacity[P,1] scaling[P,3] rotation[P,4], [6..11] their
+ *       exp_avg, [12..17] their exp_avg_sq; a moment pair may be NULL (in and out: a group without optimizer state).
+ * P = 0 and P_out = 0 are legal and launch nothing.
+ * --------------------------------------------------------------------------------------------------------------- */
+#define RADEGS_DENSIFY_NUM_TENSORS 18
+#define RADEGS_DENSIFY_MAX_P (1 << 29)
+typedef struct RadegsDensifyTensors {
+  const float* in[RADEGS_DENSIFY_NUM_TENSORS];
+  float* out[RADEGS_DENSIFY_NUM_TENSORS];
+} RadegsDensifyTensors;
+int radegs_densify_stats(int P, const float* grad_means2D /* [P,3] */, const int* radii /* [P] */, const unsigned char* visible /* [P] */,
+                         float* accum, float* accum_abs, float* accum_abs_max, float* denom, float* max_radii2D, void* stream);
+int radegs_densify_stats_reduced(int P, const float* densify_stats /* [P,3] */, const int* radii_max /* [P] or NULL */, float* accum,
+                                 float* accum_abs, float* accum_abs_max, float* denom, float* max_radii2D, void* stream);
+size_t radegs_densify_plan_bytes(int P);
+int radegs_densify_plan(int P, const float* accum, const float* accum_abs, const float* denom, const float* scaling_raw /* [P,3] */,
+                        const float* opacity_raw /* [P,1] */, float max_grad, const float* abs_threshold, float dense_threshold,
+                        float min_opacity, int prune_big, float big_threshold, void* workspace, size_t workspace_bytes, int* counts4,
+                        void* stream);
+int radegs_densify_apply(int P, int P_out, int rest_floats, const RadegsDensifyTensors* tensors, const float* unit_normals /* [P,3,3] */,
+                         const void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

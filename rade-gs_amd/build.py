@@ -36,6 +36,7 @@ UNITS = {
     "radegs_filter3d": ["radegs_filter3d.hip", os.path.join("..", "..", "include", "radegs.h")],
     "radegs_photometric": ["radegs_photometric.hip", os.path.join("..", "..", "include", "radegs.h")],
     "radegs_adam": ["radegs_adam.hip", os.path.join("..", "..", "include", "radegs.h")],
+    "radegs_densify": ["radegs_densify.hip", "rg_prims.h", os.path.join("..", "..", "include", "radegs.h")],
     "radegs_knn": ["radegs_knn.hip", "rg_prims.h", os.path.join("..", "..", "include", "radegs.h")],
 }
 # Units outside the rasterizer's decision chain have no bit-exactness contract with the oracle: let them contract to fma.

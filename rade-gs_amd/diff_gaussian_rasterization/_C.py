@@ -87,7 +87,8 @@ EXPORTED_SYMBOLS = ("radegs_forward", "radegs_backward", "radegs_backward_from_s
                     "radegs_filter3d_forward", "radegs_filter3d_backward", "radegs_compute_filter3d",
                     "radegs_photometric_scratch_bytes",
                     "radegs_photometric_forward", "radegs_photometric_backward", "radegs_adam_step", "radegs_knn_scratch_bytes",
-                    "radegs_knn_mean_dist2")
+                    "radegs_knn_mean_dist2", "radegs_densify_stats", "radegs_densify_stats_reduced", "radegs_densify_plan_bytes",
+                    "radegs_densify_plan", "radegs_densify_apply")
 
 _lib = None
 # test hook: when True, the per-Gaussian accumulation scratch of the last backward is kept in LAST_ACC

@@ -1,6 +1,9 @@
 """HIP-backed mirror of GaussianModel.get_scaling_n_opacity_with_3D_filter (scene/gaussian_model.py:156-166), the
 per-Gaussian step gaussian_renderer.render() runs right before the rasterizer (gaussian_renderer/__init__.py:63).
-SURVEY 8f N3.  One streaming kernel per direction instead of ~10 / ~20 eager torch kernels.  GPU only."""
+SURVEY 8f N3.  One streaming kernel per direction instead of ~10 / ~20 eager torch kernels.  GPU only.
+
+Also the HIP-backed adaptive density control of the same class: add_densification_stats,
+densify_and_prune and patch_gaussian_model, which installs both on the reference's GaussianModel."""
 import ctypes
 
 import torch
@@ -8,6 +11,12 @@ import torch
 from diff_gaussian_rasterization import _C
 
 _bound = False
+DENSIFY_NUM_TENSORS = 18
+
+
+class RadegsDensifyTensors(ctypes.Structure):
+    _fields_ = [("inp", ctypes.c_void_p * DENSIFY_NUM_TENSORS), ("out", ctypes.c_void_p * DENSIFY_NUM_TENSORS)]
+
 
 
 def _lib():
@@ -21,6 +30,17 @@ def _lib():
         L.radegs_filter3d_backward.argtypes = [ctypes.c_int] + [vp] * 8
         L.radegs_compute_filter3d.restype = ctypes.c_int
         L.radegs_compute_filter3d.argtypes = [ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_float, vp, vp, vp, vp]
+        L.radegs_densify_stats.restype = ctypes.c_int
+        L.radegs_densify_stats.argtypes = [ctypes.c_int] + [vp] * 9
+        L.radegs_densify_stats_reduced.restype = ctypes.c_int
+        L.radegs_densify_stats_reduced.argtypes = [ctypes.c_int] + [vp] * 8
+        L.radegs_densify_plan_bytes.restype = ctypes.c_size_t
+        L.radegs_densify_plan_bytes.argtypes = [ctypes.c_int]
+        L.radegs_densify_plan.restype = ctypes.c_int
+        L.radegs_densify_plan.argtypes = [ctypes.c_int] + [vp] * 5 + [ctypes.c_float, vp, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_float,
+                                                                    vp, ctypes.c_size_t, vp, vp]
+        L.radegs_densify_apply.restype = ctypes.c_int
+        L.radegs_densify_apply.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RadegsDensifyTensors), vp, vp, vp]
         _bound = True
     return L
 
@@ -98,3 +118,196 @@ def compute_3D_filter(xyz, cameras):
     if rc != 0:
         raise RuntimeError(f"radegs_compute_filter3d failed ({rc})")
     return out
+
+
+# ---- adaptive density control (scene/gaussian_model.py:717-747, train.py:186-187) ----
+# upstream's optimizer group name -> model attribute, in the order of RadegsDensifyTensors
+_DENSIFY_PARAMS = (("xyz", "_xyz"), ("f_dc", "_features_dc"), ("f_rest", "_features_rest"), ("opacity", "_opacity"), ("scaling", "_scaling"),
+                   ("rotation", "_rotation"))
+_STATS = ("xyz_gradient_accum", "xyz_gradient_accum_abs", "xyz_gradient_accum_abs_max", "denom")
+
+
+def _rows(t, name, P, dtype=torch.float32):
+    """a per-Gaussian array as the kernels address it: on the GPU, `dtype`, contiguous, P rows"""
+    _C._require_gpu(t, name)
+    if t.dtype != dtype or t.dim() < 1 or t.size(0) != P or not t.is_contiguous():
+        raise RuntimeError(f"`{name}` must be a contiguous {dtype} GPU tensor with {P} rows")
+    return t
+
+
+def _stat_ptrs(model, P):
+    ptrs = [_C._ptr(_rows(getattr(model, n), n, P)) for n in _STATS]
+    for n in _STATS:
+        if getattr(model, n).numel() != P:
+            raise RuntimeError(f"`{n}` must have one element per Gaussian")
+    return ptrs
+
+
+@torch.no_grad()
+def add_densification_stats(model, viewspace_point_tensor, update_filter=None, radii=None):
+    """GaussianModel.add_densification_stats for one view, in place, as one launch with no host read-back (upstream's boolean-mask
+    indexing blocks the host once per statement).  `viewspace_point_tensor`: the rasterizer's means2D input after backward (its
+    `.grad` is read) or the [P,3] gradient itself.  `update_filter`: bool / uint8 [P], or None = `radii > 0`.  With `radii` (int32
+    [P]) the same launch also does train.py:186's `max_radii2D = max(max_radii2D, radii)` on the visible rows."""
+    g = viewspace_point_tensor.grad if viewspace_point_tensor.grad is not None else viewspace_point_tensor
+    P = model.xyz_gradient_accum.shape[0]
+    g = _rows(g, "viewspace_point_tensor.grad", P)
+    if g.dim() != 2 or g.size(1) != 3:
+        raise RuntimeError("`viewspace_point_tensor.grad` must be (P,3)")
+    if update_filter is None and radii is None:
+        raise RuntimeError("add_densification_stats needs `update_filter` or `radii`")
+    mask = None
+    if update_filter is not None:
+        if update_filter.dtype not in (torch.bool, torch.uint8):
+            raise RuntimeError("`update_filter` must be a bool or uint8 mask")
+        mask = _rows(update_filter, "update_filter", P, update_filter.dtype).view(torch.uint8)
+    rad = None if radii is None else _rows(radii, "radii", P, torch.int32)
+    mr = None if radii is None else _rows(model.max_radii2D, "max_radii2D", P)
+    with torch.cuda.device(g.device):
+        rc = _lib().radegs_densify_stats(P, _C._ptr(g), _C._ptr(rad), _C._ptr(mask), *_stat_ptrs(model, P), _C._ptr(mr), _C._stream(g.device))
+    if rc != 0:
+        raise RuntimeError(f"radegs_densify_stats failed ({rc})")
+
+
+@torch.no_grad()
+def add_reduced_densification_stats(model, densify_stats, radii_max=None):
+    """The same update from the statistics view_parallel hands out already reduced over the ranks
+    (`FactoredGradExchange(...)["densify_stats"]` [P,3]: sum |grad xy|, sum |grad abs|, number of ranks that saw the Gaussian, and
+    `["radii_max"]` int32 [P]).  xyz_gradient_accum_abs_max takes the max with the summed column."""
+    P = model.xyz_gradient_accum.shape[0]
+    st = _rows(densify_stats, "densify_stats", P)
+    if st.dim() != 2 or st.size(1) != 3:
+        raise RuntimeError("`densify_stats` must be (P,3)")
+    rad = None if radii_max is None else _rows(radii_max, "radii_max", P, torch.int32)
+    mr = None if radii_max is None else _rows(model.max_radii2D, "max_radii2D", P)
+    with torch.cuda.device(st.device):
+        rc = _lib().radegs_densify_stats_reduced(P, _C._ptr(st), _C._ptr(rad), *_stat_ptrs(model, P), _C._ptr(mr), _C._stream(st.device))
+    if rc != 0:
+        raise RuntimeError(f"radegs_densify_stats_reduced failed ({rc})")
+
+
+def densify_plan(accum, accum_abs, denom, scaling_raw, opacity_raw, max_grad, abs_threshold, dense_threshold, min_opacity, big_threshold=None):
+    """radegs_densify_plan: returns (workspace, counts) -- counts is a DEVICE int32[4] = rows out, clone-selected, split-selected,
+    pruned; `abs_threshold` a device scalar.  Nothing is read back."""
+    P = scaling_raw.shape[0]
+    dev = scaling_raw.device
+    for t, n in ((accum, "accum"), (accum_abs, "accum_abs"), (denom, "denom"), (scaling_raw, "_scaling"), (opacity_raw, "_opacity")):
+        _rows(t, n, P)
+    _C._require_gpu(abs_threshold, "abs_threshold")
+    if abs_threshold.dtype != torch.float32 or abs_threshold.numel() != 1:
+        raise RuntimeError("`abs_threshold` must be one float32 on the GPU")
+    L = _lib()
+    nbytes = L.radegs_densify_plan_bytes(P)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    counts = torch.empty(4, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.radegs_densify_plan(P, _C._ptr(accum), _C._ptr(accum_abs), _C._ptr(denom), _C._ptr(scaling_raw), _C._ptr(opacity_raw), float(max_grad),
+                                   _C._ptr(abs_threshold), float(dense_threshold), float(min_opacity), int(big_threshold is not None),
+                                   float(big_threshold or 0.0), _C._ptr(ws), nbytes, _C._ptr(counts), _C._stream(dev))
+    if rc != 0:
+        raise RuntimeError(f"radegs_densify_plan failed ({rc})")
+    return ws, counts
+
+
+def densify_apply(workspace, P_out, params, exp_avg, exp_avg_sq, unit_normals):
+    """radegs_densify_apply: `params` the six parameter tensors in upstream's order (xyz, f_dc, f_rest, opacity, scaling, rotation),
+    `exp_avg` / `exp_avg_sq` six tensors or None each.  Returns three lists of new tensors with P_out rows (None where None came in)."""
+    P = params[0].shape[0]
+    dev = params[0].device
+    t = RadegsDensifyTensors()
+    outs = []
+    for j, group in enumerate((params, exp_avg, exp_avg_sq)):
+        res = []
+        for k, x in enumerate(group):
+            if x is None:
+                if j == 0:
+                    raise RuntimeError("densify_apply needs all six parameter tensors")
+                res.append(None)
+                continue
+            _rows(x, _DENSIFY_PARAMS[k][1], P)
+            if x.shape != params[k].shape:
+                raise RuntimeError(f"moment of `{_DENSIFY_PARAMS[k][1]}` does not have its parameter's shape")
+            o = torch.empty((P_out,) + tuple(x.shape[1:]), dtype=torch.float32, device=dev)
+            if x.numel() and o.numel():
+                t.inp[6 * j + k], t.out[6 * j + k] = x.data_ptr(), o.data_ptr()
+            res.append(o)
+        outs.append(res)
+    widths = [x[0].numel() if P else 0 for x in params]
+    if P and [widths[k] for k in (0, 1, 3, 4, 5)] != [3, 3, 1, 3, 4]:
+        raise RuntimeError("parameter shapes must be xyz (P,3), f_dc (P,1,3), f_rest (P,M,3), opacity (P,1), scaling (P,3), rotation (P,4)")
+    if P_out:
+        z = _rows(unit_normals, "unit_normals", P)
+        if tuple(z.shape) != (P, 3, 3):
+            raise RuntimeError("`unit_normals` must be (P,3,3)")
+        with torch.cuda.device(dev):
+            rc = _lib().radegs_densify_apply(P, P_out, widths[2], ctypes.byref(t), _C._ptr(z), _C._ptr(workspace), _C._stream(dev))
+        if rc != 0:
+            raise RuntimeError(f"radegs_densify_apply failed ({rc})")
+    return outs
+
+
+@torch.no_grad()
+def densify_and_prune(model, max_grad, min_opacity, extent, max_screen_size, unit_normals=None):
+    """GaussianModel.densify_and_prune: clone, split, prune and the final prune as one plan, ONE host read (the new row count) and one
+    pass that writes the six parameters and their twelve Adam moments at their final size; upstream rewrites them four times.
+    Returns upstream's tuple (cloned, split, pruned).  `unit_normals` [P,3,3]: the standard-normal draws upstream takes from
+    torch.normal (slot 0 the clone's, 1 / 2 the split children's, by source row); drawn with torch.randn when None.
+    As upstream, the `max_radii2D > max_screen_size` prune never fires (densification_postfix zeroes max_radii2D before the prune
+    reads it): `max_screen_size` only switches the world-size prune on.  `filter_3D` is left to the caller (train.py:196-199)."""
+    params = [getattr(model, a) for _, a in _DENSIFY_PARAMS]
+    P = params[0].shape[0]
+    dev = params[0].device
+    for (_, a), p in zip(_DENSIFY_PARAMS, params):
+        _rows(p, a, P)
+    if P == 0:
+        return 0, 0, 0
+    groups = {g["name"]: g for g in model.optimizer.param_groups if g.get("name") in dict(_DENSIFY_PARAMS)}
+    states = []
+    for (name, a), p in zip(_DENSIFY_PARAMS, params):
+        if name not in groups or len(groups[name]["params"]) != 1 or groups[name]["params"][0] is not p:
+            raise RuntimeError(f"optimizer group `{name}` must hold exactly the model's `{a}`")
+        states.append(model.optimizer.state.get(p, None) or None)
+    accum, accum_abs, denom = (_rows(getattr(model, n), n, P) for n in ("xyz_gradient_accum", "xyz_gradient_accum_abs", "denom"))
+    # Q as upstream computes it, on the device: no host read
+    grads = accum / denom
+    grads = torch.where(grads.isnan(), torch.zeros_like(grads), grads)                  # not `x[mask] = 0`: that is a nonzero() and a host wait
+    grads_abs = accum_abs / denom
+    grads_abs = torch.where(grads_abs.isnan(), torch.zeros_like(grads_abs), grads_abs)
+    ratio = (torch.norm(grads, dim=-1) >= max_grad).float().mean()
+    Q = torch.quantile(grads_abs.reshape(-1), 1 - ratio)
+    ws, counts = densify_plan(accum, accum_abs, denom, model._scaling, model._opacity, max_grad, Q, model.percent_dense * extent, min_opacity,
+                              0.1 * extent if max_screen_size else None)
+    P_out, cloned, split, pruned = counts.tolist()          # the one host read
+    if unit_normals is None:
+        unit_normals = torch.randn((P, 3, 3), dtype=torch.float32, device=dev)
+    new_p, new_m, new_v = densify_apply(ws, P_out, [p.data for p in params], [s["exp_avg"] if s else None for s in states],
+                                        [s["exp_avg_sq"] if s else None for s in states], unit_normals)
+    for k, (name, a) in enumerate(_DENSIFY_PARAMS):
+        group, old = groups[name], params[k]
+        new = torch.nn.Parameter(new_p[k].requires_grad_(True))
+        if states[k] is not None:
+            st = states[k]
+            st["exp_avg"], st["exp_avg_sq"] = new_m[k], new_v[k]
+            del model.optimizer.state[old]
+            model.optimizer.state[new] = st
+        group["params"][0] = new
+        setattr(model, a, new)
+    for n in _STATS:
+        setattr(model, n, torch.zeros((P_out, 1), dtype=torch.float32, device=dev))
+    model.max_radii2D = torch.zeros((P_out,), dtype=torch.float32, device=dev)
+    return cloned, split, pruned
+
+
+def patch_gaussian_model(cls):
+    """Installs the two functions above on the reference's GaussianModel class under upstream's method names and signatures, so that
+    train.py's `gaussians.add_densification_stats(viewspace_point_tensor, visibility_filter)` and
+    `gaussians.densify_and_prune(max_grad, min_opacity, extent, size_threshold)` run on the HIP kernels.  Returns `cls`."""
+    def _add_densification_stats(self, viewspace_point_tensor, update_filter):
+        return add_densification_stats(self, viewspace_point_tensor, update_filter)
+
+    def _densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size):
+        return densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size)
+
+    cls.add_densification_stats = _add_densification_stats
+    cls.densify_and_prune = _densify_and_prune
+    return cls
