@@ -20,10 +20,9 @@
 //     preprocess) rejects alpha < 1/255 pairs from the quadratic form alone; exp is evaluated
 //     only for surviving pairs, with the specified exp_spec() so that every thresholded decision
 //     matches the CPU oracle bit-for-bit.
-//   * Backward: per-lane partial gradients of one Gaussian are reduced with a butterfly that
-//     reduces all 16 (or 32) gradient components at once (15 + 2 cross-lane exchanges instead of
-//     16 x 6) and leaves component c in lane c, so ONE 16/25-lane global_atomic_add_f32
-//     instruction updates one 64-B accumulator line.
+//   * Backward: per-lane partial gradients of one Gaussian are reduced over all 16 (or 32) gradient
+//     components at once (row_reduce16), which leaves component c in lane c, so ONE 16/25-lane
+//     global_atomic_add_f32 instruction updates one 64-B accumulator line.
 //   * blockIdx -> tile mapping gives each XCD a contiguous band of tiles (neighbouring tiles
 //     share splat records -> per-XCD L2 reuse).
 // No MFMA: there is no dense contraction on this path.
@@ -327,7 +326,21 @@ __device__ __forceinline__ bool entry_may_touch(const float4 q0, const float4 q1
   return !(thr > 0.0f) && !(off && definite);
 }
 
-__device__ __forceinline__ int xcd_band_remap(int b, int n);
+// One lane stages one list entry: the 64-byte record (one cache line) of Gaussian g goes into LDS slot `slot`, and the answer is
+// whether the entry can touch the wave's pixel rectangle (entry_may_touch).
+__device__ __forceinline__ bool stage_record(const float4* splat_a, uint32_t g, float4* lds_a, int slot, float x_lo, float x_hi, float y_lo,
+                                             float y_hi) {
+  const float4* src = splat_a + 4 * (size_t)g;
+  const float4 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3];
+  lds_a[slot * 4 + 0] = q0; lds_a[slot * 4 + 1] = q1; lds_a[slot * 4 + 2] = q2; lds_a[slot * 4 + 3] = q3;
+  return entry_may_touch(q0, q1, x_lo, x_hi, y_lo, y_hi);
+}
+
+// blockIdx -> work item such that each XCD (block b runs on XCD b % 8) owns a contiguous band.
+__device__ __forceinline__ int xcd_band_remap(int b, int n) {
+  const int q = n >> 3, r = n & 7, xcd = b & 7, loc = b >> 3;
+  return xcd * q + (xcd < r ? xcd : r) + loc;
+}
 
 // ============================================================================ integrate ==
 // GaussianRasterizer.integrate (GOF-style point integration used by mesh extraction): for every query point that
@@ -466,10 +479,7 @@ __global__ void __launch_bounds__(64) integrate_kernel(const IntegrateArgs a) {
     bool rel_lane = false;
     if (k < n) {
       const uint32_t g = a.point_list[range.x + k];
-      const float4* src = a.splat_a + 4 * (size_t)g;
-      const float4 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3];
-      lds_a[lane * 4 + 0] = q0; lds_a[lane * 4 + 1] = q1; lds_a[lane * 4 + 2] = q2; lds_a[lane * 4 + 3] = q3;
-      rel_lane = entry_may_touch(q0, q1, reg_x0, reg_x1, reg_y0, reg_y1);
+      rel_lane = stage_record(a.splat_a, g, lds_a, lane, reg_x0, reg_x1, reg_y0, reg_y1);
     }
     uint64_t rel = __ballot(rel_lane);
     __syncthreads();
@@ -567,12 +577,9 @@ __global__ void __launch_bounds__(64) integrate_kernel(const IntegrateArgs a) {
         bool rel_lane = false;
         if (k < n) {
           const uint32_t g = a.point_list[range.x + k];
-          const float4* src = a.splat_a + 4 * (size_t)g;
-          const float4 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3];
-          lds_a[lane * 4 + 0] = q0; lds_a[lane * 4 + 1] = q1; lds_a[lane * 4 + 2] = q2; lds_a[lane * 4 + 3] = q3;
+          rel_lane = stage_record(a.splat_a, g, lds_a, lane, reg_x0, reg_x1, reg_y0, reg_y1);
           const float4* si = a.inte_rec + 2 * (size_t)g;
           lds_i[lane * 2 + 0] = si[0]; lds_i[lane * 2 + 1] = si[1];
-          rel_lane = entry_may_touch(q0, q1, reg_x0, reg_x1, reg_y0, reg_y1);
         }
         uint64_t rel = __ballot(rel_lane);
         __syncthreads();
@@ -644,12 +651,9 @@ __global__ void __launch_bounds__(64) integrate_kernel(const IntegrateArgs a) {
       bool rel_lane = false;
       if (k < n) {
         const uint32_t g = a.point_list[range.x + k];
-        const float4* src = a.splat_a + 4 * (size_t)g;
-        const float4 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3];
-        lds_a[lane * 4 + 0] = q0; lds_a[lane * 4 + 1] = q1; lds_a[lane * 4 + 2] = q2; lds_a[lane * 4 + 3] = q3;
+        rel_lane = stage_record(a.splat_a, g, lds_a, lane, reg_x0, reg_x1, reg_y0, reg_y1);
         const float4* si = a.inte_rec + 2 * (size_t)g;
         lds_i[lane * 2 + 0] = si[0]; lds_i[lane * 2 + 1] = si[1];
-        rel_lane = entry_may_touch(q0, q1, reg_x0, reg_x1, reg_y0, reg_y1);
       }
       uint64_t rel = __ballot(rel_lane);
       __syncthreads();
@@ -743,10 +747,54 @@ __device__ __forceinline__ void zero_unproduced_maps(const BlendFwdArgs& a, size
   }
 }
 
-// blockIdx -> work item such that each XCD (block b runs on XCD b % 8) owns a contiguous band.
-__device__ __forceinline__ int xcd_band_remap(int b, int n) {
-  const int q = n >> 3, r = n & 7, xcd = b & 7, loc = b >> 3;
-  return xcd * q + (xcd < r ? xcd : r) + loc;
+// One pixel's epilogue (forward.cu:631-692): the last and the median contributor, colour over the background, alpha, the maps the mode
+// produces, what the backward re-reads (accum_*, normal_length), zeros for the other maps.  T_final: the transmittance left behind the
+// last entry -- each formulation passes its own (see the two call sites).  Co / mCo are only read in coord mode.
+template <bool COORD, bool DEPTH>
+__device__ __forceinline__ void blend_fwd_epilogue(const BlendFwdArgs& a, int px, int py, float T_final, uint32_t last_c, uint32_t max_c,
+                                                   float Cr, float Cg, float Cb, float weight, const float (&Co)[3], const float (&mCo)[3],
+                                                   float Dep, float mDep, float Nx, float Ny, float Nz) {
+  constexpr bool NORMAL = COORD || DEPTH;
+  const int W = a.W, H = a.H;
+  const size_t HW = (size_t)H * W;
+  const size_t pix = (size_t)W * py + px;
+  const float pnx = ((float)px - W / 2.f) / a.focal_x;
+  const float pny = ((float)py - H / 2.f) / a.focal_y;
+  const float ln = sqrtf(pnx * pnx + pny * pny + 1);
+  a.n_contrib[pix] = last_c;
+  a.n_contrib[pix + HW] = max_c;
+  a.out_color[pix] = fmaf(T_final, a.bg[0], Cr);
+  a.out_color[HW + pix] = fmaf(T_final, a.bg[1], Cg);
+  a.out_color[2 * HW + pix] = fmaf(T_final, a.bg[2], Cb);
+  a.out_alpha[pix] = weight;
+  zero_unproduced_maps<COORD, DEPTH>(a, pix, HW);
+  if constexpr (COORD) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      a.out_coord[c * HW + pix] = last_c ? Co[c] / weight : 0.f;
+      a.accum_coord[c * HW + pix] = Co[c];
+      a.out_mcoord[c * HW + pix] = mCo[c];
+    }
+  }
+  if constexpr (DEPTH) {
+    const float depth_ln = Dep / ln;
+    a.accum_depth[pix] = depth_ln;
+    a.out_depth[pix] = last_c ? depth_ln / weight : 0.f;
+    a.out_mdepth[pix] = mDep / ln;
+  }
+  if constexpr (NORMAL) {
+    if (last_c) {
+      float len_n = sqrtf(Nx * Nx + Ny * Ny + Nz * Nz);
+      a.normal_length[pix] = len_n;
+      len_n = fmaxf(len_n, 1.0E-12F);
+      a.out_normal[pix] = Nx / len_n;
+      a.out_normal[HW + pix] = Ny / len_n;
+      a.out_normal[2 * HW + pix] = Nz / len_n;
+    } else {
+      a.normal_length[pix] = 1;
+      a.out_normal[pix] = 0; a.out_normal[HW + pix] = 0; a.out_normal[2 * HW + pix] = 0;
+    }
+  }
 }
 
 // One wave64 owns a 16 x (4*PPL) strip of the tile: lane -> column (lane & 15), rows (lane >> 4) + 4 s.
@@ -775,7 +823,6 @@ __global__ void __launch_bounds__(64) blend_fwd_kernel(const BlendFwdArgs a) {
   const int px = geo.px;
   const int py0 = geo.py_first;  // slot s -> row py0 + 4 s
   const int W = a.W, H = a.H;
-  const size_t HW = (size_t)H * W;
   const float pixfx = (float)px;
   // pixel rectangle owned by this wave (for batch culling)
   const float reg_x0 = geo.rx0, reg_x1 = geo.rx1, reg_y0 = geo.ry0, reg_y1 = geo.ry1;
@@ -818,14 +865,11 @@ __global__ void __launch_bounds__(64) blend_fwd_kernel(const BlendFwdArgs a) {
     bool rel_lane = false;
     if (k < n) {
       const uint32_t g = a.point_list[range.x + k];
-      const float4* src = a.splat_a + 4 * (size_t)g;
-      const float4 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3];
-      lds_a[lane * 4 + 0] = q0; lds_a[lane * 4 + 1] = q1; lds_a[lane * 4 + 2] = q2; lds_a[lane * 4 + 3] = q3;
+      rel_lane = stage_record(a.splat_a, g, lds_a, lane, reg_x0, reg_x1, reg_y0, reg_y1);
       if constexpr (COORD) {
         const float4* sb = a.splat_b + 3 * (size_t)g;
         lds_b[lane * 3 + 0] = sb[0]; lds_b[lane * 3 + 1] = sb[1]; lds_b[lane * 3 + 2] = sb[2];
       }
-      rel_lane = entry_may_touch(q0, q1, reg_x0, reg_x1, reg_y0, reg_y1);
     }
     uint64_t rel = __ballot(rel_lane);
     const int niter = (int)__popcll(rel);
@@ -868,11 +912,10 @@ __global__ void __launch_bounds__(64) blend_fwd_kernel(const BlendFwdArgs a) {
               Cr[s] = fmaf(C.x, aT, Cr[s]); Cg[s] = fmaf(C.y, aT, Cg[s]); Cb[s] = fmaf(C.z, aT, Cb[s]);
               const bool before_median = T[s] > 0.5f;
               if constexpr (COORD) {
-                const float c0 = fmaf(E0.y, dy, fmaf(E0.x, dx, E1.z));
-                const float c1 = fmaf(E0.w, dy, fmaf(E0.z, dx, E1.w));
-                const float c2 = fmaf(E1.y, dy, fmaf(E1.x, dx, E2.x));
-                Co[s][0] = fmaf(c0, aT, Co[s][0]); Co[s][1] = fmaf(c1, aT, Co[s][1]); Co[s][2] = fmaf(c2, aT, Co[s][2]);
-                if (before_median) { mCo[s][0] = c0; mCo[s][1] = c1; mCo[s][2] = c2; }
+                float c[3];
+                coord_planes(E0, E1, E2, dx, dy, c);
+                Co[s][0] = fmaf(c[0], aT, Co[s][0]); Co[s][1] = fmaf(c[1], aT, Co[s][1]); Co[s][2] = fmaf(c[2], aT, Co[s][2]);
+                if (before_median) { mCo[s][0] = c[0]; mCo[s][1] = c[1]; mCo[s][2] = c[2]; }
               }
               if constexpr (DEPTH) {
                 const float t = B.w + fmaf(C.w, dx, Dq.x * dy);
@@ -901,48 +944,13 @@ __global__ void __launch_bounds__(64) blend_fwd_kernel(const BlendFwdArgs a) {
     }
   }
 
-  // ---- epilogue (forward.cu:631-692) ----
-  const float pnx = (pixfx - W / 2.f) / a.focal_x;
+  // ---- epilogue ----
 #pragma unroll
   for (int s = 0; s < PPL; s++) {
     if (!inside[s]) continue;
-    const size_t pix = (size_t)W * (py0 + kStripRowStep * s) + px;
-    const float pny = (pixfy[s] - H / 2.f) / a.focal_y;
-    const float ln = sqrtf(pnx * pnx + pny * pny + 1);
-    a.n_contrib[pix] = last_c[s];
-    a.n_contrib[pix + HW] = max_c[s];
-    a.out_color[pix] = fmaf(T[s], a.bg[0], Cr[s]);
-    a.out_color[HW + pix] = fmaf(T[s], a.bg[1], Cg[s]);
-    a.out_color[2 * HW + pix] = fmaf(T[s], a.bg[2], Cb[s]);
-    a.out_alpha[pix] = weight[s];
-    zero_unproduced_maps<COORD, DEPTH>(a, pix, HW);
-    if constexpr (COORD) {
-#pragma unroll
-      for (int c = 0; c < 3; c++) {
-        a.out_coord[c * HW + pix] = last_c[s] ? Co[s][c] / weight[s] : 0.f;
-        a.accum_coord[c * HW + pix] = Co[s][c];
-        a.out_mcoord[c * HW + pix] = mCo[s][c];
-      }
-    }
-    if constexpr (DEPTH) {
-      const float depth_ln = Dep[s] / ln;
-      a.accum_depth[pix] = depth_ln;
-      a.out_depth[pix] = last_c[s] ? depth_ln / weight[s] : 0.f;
-      a.out_mdepth[pix] = mDep[s] / ln;
-    }
-    if constexpr (NORMAL) {
-      if (last_c[s]) {
-        float len_n = sqrtf(Nx[s] * Nx[s] + Ny[s] * Ny[s] + Nz[s] * Nz[s]);
-        a.normal_length[pix] = len_n;
-        len_n = fmaxf(len_n, 1.0E-12F);
-        a.out_normal[pix] = Nx[s] / len_n;
-        a.out_normal[HW + pix] = Ny[s] / len_n;
-        a.out_normal[2 * HW + pix] = Nz[s] / len_n;
-      } else {
-        a.normal_length[pix] = 1;
-        a.out_normal[pix] = 0; a.out_normal[HW + pix] = 0; a.out_normal[2 * HW + pix] = 0;
-      }
-    }
+    // final transmittance: T[s], the running product itself (the stream kernel keeps none and passes 1 - weight: rg_streams.inc)
+    blend_fwd_epilogue<COORD, DEPTH>(a, px, py0 + kStripRowStep * s, T[s], last_c[s], max_c[s], Cr[s], Cg[s], Cb[s], weight[s],
+                                     Co[COORD ? s : 0], mCo[COORD ? s : 0], Dep[s], mDep[s], Nx[s], Ny[s], Nz[s]);
   }
 }
 
@@ -969,49 +977,6 @@ struct BlendBwdArgs {
   uint32_t* stream_err;         // mapped host word: set when stream_tag says this buffer holds no entry streams (may be nullptr)
   const uint32_t* blk_base; const uint32_t* blk_consumed; const uint32_t* blk_chunks; const uint32_t* blk_order;   // sub-tile entry streams (rg_streams.inc)
 };
-
-// In: v[i] = this lane's partial sum of component i.  Out (return value): the wave-wide total of
-// component (lane & (N-1)).  Each butterfly stage halves the live components while doubling the
-// lanes summed: lanes whose stage bit is set keep the upper half of the components, the others the
-// lower half, and every lane hands the half it drops to a partner of the opposite class.  The four
-// in-row stages use DPP (no LDS crossbar): row_ror:8 (= xor 8), row_half_mirror (bit 2 flips,
-// bit 3 kept), quad_perm xor 2, quad_perm xor 1 -- together they span all 16 lanes of a row.
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float x) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xF, 0xF, false));
-}
-template <int HALF, int BIT, int CTRL>
-__device__ __forceinline__ void bfly_stage_dpp(float* v, int lane) {
-  const bool up = (lane >> BIT) & 1;
-#pragma unroll
-  for (int i = 0; i < HALF; i++) {
-    const float send = up ? v[i] : v[i + HALF];
-    const float keep = up ? v[i + HALF] : v[i];
-    v[i] = keep + dpp_mov<CTRL>(send);
-  }
-}
-template <int HALF, int BIT>
-__device__ __forceinline__ void bfly_stage_xor(float* v, int lane) {   // a stage that crosses the DPP rows (ds_bpermute)
-  const bool up = (lane >> BIT) & 1;
-#pragma unroll
-  for (int i = 0; i < HALF; i++) {
-    const float send = up ? v[i] : v[i + HALF];
-    const float keep = up ? v[i + HALF] : v[i];
-    v[i] = keep + __shfl_xor(send, 1 << BIT);
-  }
-}
-template <int N>
-__device__ __forceinline__ float wave_reduce_scatter(float (&v)[N], int lane) {
-  if constexpr (N == 32) bfly_stage_xor<16, 4>(v, lane);
-  bfly_stage_dpp<8, 3, 0x128>(v, lane);  // row_ror:8
-  bfly_stage_dpp<4, 2, 0x141>(v, lane);  // row_half_mirror
-  bfly_stage_dpp<2, 1, 0x4E>(v, lane);   // quad_perm [2,3,0,1]
-  bfly_stage_dpp<1, 0, 0xB1>(v, lane);   // quad_perm [1,0,3,2]
-  float r = v[0];
-  if constexpr (N == 16) r += __shfl_xor(r, 16);
-  r += __shfl_xor(r, 32);
-  return r;
-}
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 
@@ -1078,6 +1043,75 @@ __device__ __forceinline__ float row_reduce16(float (&v)[16], const RowReduceAdd
   return ((t0 + t1) + (t2 + t3)) + ((t4 + t5) + (t6 + t7));
 }
 
+// One pixel's cotangents as both blend backwards start from them (backward.cu:706-781): the transmittance behind the last entry, the
+// cotangent of alpha (dLa, with the normalised maps' 1/alpha^2 terms folded in), the background term tb, and the cotangents of colour
+// (dLc), depth and median depth (dLt, dLmt), normal (dLn), coord and median coord (dLco, dLmco), each already divided by what the
+// forward's epilogue divided by.  last_c: entries of the list the pixel consumed; max_cm1: 0-based position of its median contributor
+// (0xFFFFFFFF, "none", never matches).  Each kernel copies the fields into its own register layout.
+struct PixelCotangents {
+  float T, dLa, tb, dLc[3], dLt, dLmt, dLn[3], dLco[3], dLmco[3];
+  uint32_t last_c, max_cm1;
+};
+template <bool COORD, bool DEPTH>
+__device__ __forceinline__ PixelCotangents pixel_cotangents(const BlendBwdArgs& a, int px, int py) {
+  constexpr bool NORMAL = COORD || DEPTH;
+  const int W = a.W, H = a.H;
+  const size_t HW = (size_t)H * W;
+  PixelCotangents o;
+  const bool inside = px < W && py < H;
+  const size_t pix = inside ? (size_t)W * py + px : 0;
+  const float alpha_px = inside ? a.alphas[pix] : 0.f;
+  const float T_final = inside ? (1 - alpha_px) : 0.f;
+  const float w_final = alpha_px;
+  o.T = T_final;
+  o.last_c = inside ? a.n_contrib[pix] : 0u;
+  o.max_cm1 = (inside ? a.n_contrib[pix + HW] : 0u) - 1u;
+  o.dLt = 0.f; o.dLmt = 0.f;
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    o.dLc[c] = inside ? a.dL_dpix[c * HW + pix] : 0.f;
+    o.dLn[c] = 0.f; o.dLco[c] = 0.f; o.dLmco[c] = 0.f;
+  }
+  float dla = inside ? a.dL_dalpha[pix] : 0.f;
+  o.tb = -T_final * (a.bg[0] * o.dLc[0] + a.bg[1] * o.dLc[1] + a.bg[2] * o.dLc[2]);
+  // Pixels nothing blended into (alpha = 0) cannot pass a gradient to any Gaussian; their 1/alpha factors would be inf/NaN and
+  // poison the wave-wide sums through the multiplicative masks, so their geometry cotangents stay zero.
+  if (NORMAL && inside && o.last_c > 0) {
+    const float ww = w_final * w_final;
+    const float pnx = ((float)px - W / 2.f) / a.focal_x;
+    const float pny = ((float)py - H / 2.f) / a.focal_y;
+    const float ln = sqrtf(pnx * pnx + pny * pny + 1);
+    if constexpr (COORD) {
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        const float gw = a.dL_dcoord[c * HW + pix];
+        dla -= gw * a.accum_coord[c * HW + pix] / ww;
+        o.dLco[c] = gw / w_final;
+        o.dLmco[c] = a.dL_dmcoord[c * HW + pix];
+      }
+    }
+    if constexpr (DEPTH) {
+      const float gw = a.dL_ddepth[pix];
+      dla -= gw * a.accum_depth[pix] / ww;
+      o.dLt = gw / w_final / ln;
+      o.dLmt = a.dL_dmdepth[pix] / ln;
+    }
+    {
+      const float g0 = a.dL_dnormal[pix], g1 = a.dL_dnormal[HW + pix], g2 = a.dL_dnormal[2 * HW + pix];
+      const float n0 = a.normalmap[pix], n1 = a.normalmap[HW + pix], n2 = a.normalmap[2 * HW + pix];
+      const float nlen = a.normal_length[pix];
+      if (nlen < 1.0E-12F) {
+        o.dLn[0] = g0 / 1.0E-12F; o.dLn[1] = g1 / 1.0E-12F; o.dLn[2] = g2 / 1.0E-12F;
+      } else {
+        const float dt = g0 * n0 + g1 * n1 + g2 * n2;
+        o.dLn[0] = (g0 - dt * n0) / nlen; o.dLn[1] = (g1 - dt * n1) / nlen; o.dLn[2] = (g2 - dt * n2) / nlen;
+      }
+    }
+  }
+  o.dLa = dla;
+  return o;
+}
+
 // ------------------------------------------------------------------ blend, bwd (packed) ----
 // Second formulation of the same backward: the pixels of one lane are handled in PAIRS as 2-wide
 // fp32 vectors (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32 do two pixels per issue slot), and a
@@ -1100,7 +1134,7 @@ __global__ void __launch_bounds__(64, (COORD ? (PPL == 4 ? 1 : 2) : (PPL == 4 ? 
   __shared__ float4 lds_a[65 * 4];
   __shared__ float4 lds_b[COORD ? 64 * 3 : 1];
   __shared__ uint32_t lds_id[65];
-  __shared__ __attribute__((aligned(16))) float lds_red[4 * kRedRowFloats];   // row_reduce16's scratch (rg_streams.inc)
+  __shared__ __attribute__((aligned(16))) float lds_red[4 * kRedRowFloats];   // row_reduce16's scratch
 
   const int item = xcd_band_remap(blockIdx.x, gridDim.x);
   const int tile = item / WPT, sub = item - tile * WPT;
@@ -1110,7 +1144,6 @@ __global__ void __launch_bounds__(64, (COORD ? (PPL == 4 ? 1 : 2) : (PPL == 4 ? 
   const int px = geo.px;
   const int py0 = geo.py_first;
   const int W = a.W, H = a.H;
-  const size_t HW = (size_t)H * W;
   const float pixfx = (float)px;
   const float reg_x0 = geo.rx0, reg_x1 = geo.rx1, reg_y0 = geo.ry0, reg_y1 = geo.ry1;
   const uint2 range = a.ranges[tile];
@@ -1128,67 +1161,21 @@ __global__ void __launch_bounds__(64, (COORD ? (PPL == 4 ? 1 : 2) : (PPL == 4 ? 
   f2 dLco[COORD ? NP : 1][3], dLmco[COORD ? NP : 1][3];
   uint32_t last_c[PPL], max_cm1[PPL];
   uint32_t wave_last = 0;
-  const float pnx = (pixfx - W / 2.f) / a.focal_x;
 #pragma unroll
   for (int s = 0; s < PPL; s++) {
     const int q = s >> 1, e = s & 1;
     const int py = py0 + kStripRowStep * s;
     pixfy[q][e] = (float)py;
-    const bool inside = px < W && py < H;
-    const size_t pix = inside ? (size_t)W * py + px : 0;
-    const float alpha_px = inside ? a.alphas[pix] : 0.f;
-    const float T_final = inside ? (1 - alpha_px) : 0.f;
-    const float w_final = alpha_px;
-    T[q][e] = T_final;
-    last_c[s] = inside ? a.n_contrib[pix] : 0u;
-    max_cm1[s] = (inside ? a.n_contrib[pix + HW] : 0u) - 1u;
+    const PixelCotangents ct = pixel_cotangents<COORD, DEPTH>(a, px, py);
+    T[q][e] = ct.T; Q[q][e] = 0.f; dLa[q][e] = ct.dLa; tb[q][e] = ct.tb;
+    dLt[q][e] = ct.dLt; dLmt[q][e] = ct.dLmt;
+    last_c[s] = ct.last_c; max_cm1[s] = ct.max_cm1;
     wave_last = max(wave_last, last_c[s]);
-    Q[q][e] = 0.f;
-    dLt[q][e] = 0.f; dLmt[q][e] = 0.f;
-    float dl3[3];
 #pragma unroll
     for (int c = 0; c < 3; c++) {
-      dl3[c] = inside ? a.dL_dpix[c * HW + pix] : 0.f;
-      dLc[q][c][e] = dl3[c];
-      dLn[q][c][e] = 0.f;
-      if constexpr (COORD) { dLco[q][c][e] = 0.f; dLmco[q][c][e] = 0.f; }
+      dLc[q][c][e] = ct.dLc[c]; dLn[q][c][e] = ct.dLn[c];
+      if constexpr (COORD) { dLco[q][c][e] = ct.dLco[c]; dLmco[q][c][e] = ct.dLmco[c]; }
     }
-    float dla = inside ? a.dL_dalpha[pix] : 0.f;
-    tb[q][e] = -T_final * (a.bg[0] * dl3[0] + a.bg[1] * dl3[1] + a.bg[2] * dl3[2]);
-    // Pixels nothing blended into (alpha = 0) cannot pass a gradient to any Gaussian; their 1/alpha factors would be inf/NaN and
-    // poison the wave-wide sums through the multiplicative masks, so their geometry cotangents stay zero.
-    if (NORMAL && inside && last_c[s] > 0) {
-      const float ww = w_final * w_final;
-      const float pny = ((float)py - H / 2.f) / a.focal_y;
-      const float ln = sqrtf(pnx * pnx + pny * pny + 1);
-      if constexpr (COORD) {
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-          const float gw = a.dL_dcoord[c * HW + pix];
-          dla -= gw * a.accum_coord[c * HW + pix] / ww;
-          dLco[q][c][e] = gw / w_final;
-          dLmco[q][c][e] = a.dL_dmcoord[c * HW + pix];
-        }
-      }
-      if constexpr (DEPTH) {
-        const float gw = a.dL_ddepth[pix];
-        dla -= gw * a.accum_depth[pix] / ww;
-        dLt[q][e] = gw / w_final / ln;
-        dLmt[q][e] = a.dL_dmdepth[pix] / ln;
-      }
-      {
-        const float g0 = a.dL_dnormal[pix], g1 = a.dL_dnormal[HW + pix], g2 = a.dL_dnormal[2 * HW + pix];
-        const float n0 = a.normalmap[pix], n1 = a.normalmap[HW + pix], n2 = a.normalmap[2 * HW + pix];
-        const float nlen = a.normal_length[pix];
-        if (nlen < 1.0E-12F) {
-          dLn[q][0][e] = g0 / 1.0E-12F; dLn[q][1][e] = g1 / 1.0E-12F; dLn[q][2][e] = g2 / 1.0E-12F;
-        } else {
-          const float dt = g0 * n0 + g1 * n1 + g2 * n2;
-          dLn[q][0][e] = (g0 - dt * n0) / nlen; dLn[q][1][e] = (g1 - dt * n1) / nlen; dLn[q][2][e] = (g2 - dt * n2) / nlen;
-        }
-      }
-    }
-    dLa[q][e] = dla;
   }
 #pragma unroll
   for (int m = 1; m < 64; m <<= 1) wave_last = max(wave_last, (uint32_t)__shfl_xor((int)wave_last, m));
@@ -1202,14 +1189,11 @@ __global__ void __launch_bounds__(64, (COORD ? (PPL == 4 ? 1 : 2) : (PPL == 4 ? 
     if (e0 >= 0) {
       const uint32_t g = a.point_list[range.x + e0];
       lds_id[lane] = g;
-      const float4* src = a.splat_a + 4 * (size_t)g;
-      const float4 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3];
-      lds_a[lane * 4 + 0] = q0; lds_a[lane * 4 + 1] = q1; lds_a[lane * 4 + 2] = q2; lds_a[lane * 4 + 3] = q3;
+      rel_lane = stage_record(a.splat_a, g, lds_a, lane, reg_x0, reg_x1, reg_y0, reg_y1);
       if constexpr (COORD) {
         const float4* sb = a.splat_b + 3 * (size_t)g;
         lds_b[lane * 3 + 0] = sb[0]; lds_b[lane * 3 + 1] = sb[1]; lds_b[lane * 3 + 2] = sb[2];
       }
-      rel_lane = entry_may_touch(q0, q1, reg_x0, reg_x1, reg_y0, reg_y1);
     }
     uint64_t rel = __ballot(rel_lane);
     const int niter = (int)__popcll(rel);

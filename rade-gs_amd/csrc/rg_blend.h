@@ -24,8 +24,8 @@ namespace rg {
 // gives; subtracting the constant is exact, and the integer k sits in the low mantissa bits of the sum.  Bit-identical to the rintf /
 // (int32_t) form the oracle spells (tests/test_hostcheck.py compares the two over the whole argument range).
 constexpr float kExpMagic = 12582912.0f;
-RG_HD float exp_spec(float x) {
-  if (x < -87.0f) return 0.0f;
+// the polynomial and the scaling, for x >= -87 (the two entry points below differ only in what they do beneath that)
+RG_HD float exp_spec_core(float x) {
   const float tm = x * 1.44269504088896341f + kExpMagic;   // == kExpMagic + rintf(x * log2e): see kExpMagic
   const float kf = tm - kExpMagic;
   float r = fmaf(kf, -0.693359375f, x);
@@ -44,29 +44,11 @@ RG_HD float exp_spec(float x) {
   u.i += t.i << 23;   // bits(tm) = bits(kExpMagic) + k and bits(kExpMagic) << 23 == 0 (mod 2^32): k lands in the exponent field
   return u.f;
 }
+RG_HD float exp_spec(float x) { return x < -87.0f ? 0.0f : exp_spec_core(x); }
 
 // The same value as exp_spec(x) for x >= -87; below, exp_spec(-87) (~1.6e-38) instead of 0.  For callers that only use the result
 // through `op * exp < 1/255` (any op <= 1 fails it either way): straight-line code, no branch between two pixels' evaluations.
-RG_HD float exp_spec_floor(float x) {
-  x = fmaxf(x, -87.0f);
-  const float tm = x * 1.44269504088896341f + kExpMagic;
-  const float kf = tm - kExpMagic;
-  float r = fmaf(kf, -0.693359375f, x);
-  r = fmaf(kf, 2.12194440e-4f, r);
-  float p = 1.9875691500e-4f;
-  p = fmaf(p, r, 1.3981999507e-3f);
-  p = fmaf(p, r, 8.3334519073e-3f);
-  p = fmaf(p, r, 4.1665795894e-2f);
-  p = fmaf(p, r, 1.6666665459e-1f);
-  p = fmaf(p, r, 5.0000001201e-1f);
-  const float r2 = r * r;
-  const float y = fmaf(p, r2, r) + 1.0f;
-  union { float f; uint32_t i; } u, t;
-  u.f = y;
-  t.f = tm;
-  u.i += t.i << 23;   // bits(tm) = bits(kExpMagic) + k and bits(kExpMagic) << 23 == 0 (mod 2^32): k lands in the exponent field
-  return u.f;
-}
+RG_HD float exp_spec_floor(float x) { return exp_spec_core(fmaxf(x, -87.0f)); }
 
 // Conservative skip threshold: any power below it gives alpha < 1/255 under the exact rule
 // (margin 1e-3 in the exponent >> the 1e-6 relative error of exp_spec and of logf).  op <= 0
@@ -81,6 +63,15 @@ RG_HD float splat_power(float a_x, float b_xy, float cz, float dy) {
   const float v = b_xy * dy;
   // -0.5f*s is exact, so this single fma rounds exactly like (-0.5f*s) - v.
   return fmaf(-0.5f, s, -v);
+}
+
+// The three camera-plane values (coord map) of a splat at (dx, dy) from its mean: c[k] = cpx_k dx + cpy_k dy + vp_k, with the planes as
+// the splat_b record holds them -- E0 {cpx0, cpy0, cpx1, cpy1}, E1 {cpx2, cpy2, vp0, vp1}, E2 {vp2, ...}.  V4: any .x/.y/.z/.w vector.
+template <class V4>
+RG_HD void coord_planes(const V4& E0, const V4& E1, const V4& E2, float dx, float dy, float (&c)[3]) {
+  c[0] = fmaf(E0.y, dy, fmaf(E0.x, dx, E1.z));
+  c[1] = fmaf(E0.w, dy, fmaf(E0.z, dx, E1.w));
+  c[2] = fmaf(E1.y, dy, fmaf(E1.x, dx, E2.x));
 }
 
 // ---- which 8x4-pixel blocks of a 16x16 tile can a splat reach?  (block lists of the sub-tile entry streams, rg_streams.inc) ----

@@ -286,6 +286,44 @@ __device__ __forceinline__ void gather_rows_to_lds(const float4* __restrict__ sp
   for (int k = 0; k < 4; k++) lds[k * row_stride_v4 + e * 4 + qd] = V4{v[k].x, v[k].y, v[k].z, v[k].w};
 }
 
+// ---- set-up shared by the two stream kernels ----
+// A 16-lane row of wave `item` owns one 8x4 block -- any block of the neighbourhood (balance_blocks, in block_lists_kernel), the same
+// wave composition in the forward and the backward.  Lane l of the row holds pixel column px, rows py0 and py0 + 2.
+constexpr int kStreamRowStep = 2;   // rows between the two pixels of one lane
+struct StreamRow { uint32_t bid; int tile, blk, px, py0; };
+__device__ __forceinline__ StreamRow stream_row_geometry(const uint32_t* blk_order, int item, int grp, int l, int gx) {
+  StreamRow g;
+  g.bid = blk_order[4 * (size_t)item + grp];
+  g.tile = (int)(g.bid >> 3); g.blk = (int)(g.bid & 7u);
+  const int tile_x = g.tile % gx, tile_y = g.tile / gx;
+  const int brow = g.blk >> 1, bcol = g.blk & 1;
+  g.px = tile_x * 16 + bcol * 8 + (l & 7);
+  g.py0 = tile_y * 16 + brow * 4 + (l >> 3);
+  return g;
+}
+// Lane l's list word of round r -- {Gaussian id, position in the tile list} -- of a list of n entries; {0, kNoPos} past its end.
+// The backward, which asks one round ahead, ends with r = -1: as 0xFFFFFFFF its first position, 0xFFFFFFF0, lies past any list
+// (n < 2^31: the tile list's length is an int), so the one compare covers that end too.
+__device__ __forceinline__ uint2 load_list_word(const uint32_t* chunks, uint32_t r, int l, uint32_t n) {
+  return (r * 16u + (uint32_t)l < n) ? *reinterpret_cast<const uint2*>(chunks + (size_t)r * kChunkWords + 2 * l) : make_uint2(0u, kNoPos);
+}
+// Coord-map mode: the 48-byte camera-plane record of the lane's entry (all zeros otherwise, and for a lane without an entry).
+struct PlaneRec { float4 e0, e1, e2; };
+template <bool COORD>
+__device__ __forceinline__ PlaneRec gather_planes(const float4* splat_b, const uint2 rec) {
+  const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+  PlaneRec p = {z, z, z};
+  if constexpr (COORD) {
+    // loaded unconditionally (an idle lane reads record 0) and zeroed by selects: loads under a branch reach the staging code through a
+    // PHI that the register allocator parks in scratch -- a store, a full wait and a load per round
+    const bool live = rec.y != kNoPos;
+    const float4* sb = splat_b + 3 * (size_t)(live ? rec.x : 0u);
+    const float4 t0 = sb[0], t1 = sb[1], t2 = sb[2];
+    p.e0 = live ? t0 : z; p.e1 = live ? t1 : z; p.e2 = live ? t2 : z;
+  }
+  return p;
+}
+
 // ================================================================================ forward ==
 // Every round gathers its own records first and relies on the other waves of the SIMD to cover the latency (a software pipeline
 // through registers -- the records of round r+1 gathered while round r is blended -- costs ~20 VGPRs and measured 1-2 % slower).
@@ -302,14 +340,10 @@ __global__ void __launch_bounds__(64, COORD ? 1 : RADEGS_FWD_WAVES) blend_fwd_st
 
   const int item = xcd_band_remap(blockIdx.x, gridDim.x);
   const int lane = threadIdx.x, grp = lane >> 4, l = lane & 15;
-  const uint32_t bid = a.blk_order[4 * (size_t)item + grp];   // this row's block: any block of the neighbourhood (balance_blocks, in block_lists_kernel)
-  const int tile = (int)(bid >> 3), blk = (int)(bid & 7u);
-  const int tile_x = tile % a.gx, tile_y = tile / a.gx;
-  const int brow = blk >> 1, bcol = blk & 1;
-  const int px = tile_x * 16 + bcol * 8 + (l & 7);
-  const int py0 = tile_y * 16 + brow * 4 + (l >> 3);   // second pixel: 2 rows below
+  const StreamRow geo = stream_row_geometry(a.blk_order, item, grp, l, a.gx);
+  const uint32_t bid = geo.bid;
+  const int tile = geo.tile, blk = geo.blk, px = geo.px, py0 = geo.py0;
   const int W = a.W, H = a.H;
-  const size_t HW = (size_t)H * W;
   const float pixfx = (float)px;
 
   const uint2 range = a.ranges[tile];
@@ -328,7 +362,7 @@ __global__ void __launch_bounds__(64, COORD ? 1 : RADEGS_FWD_WAVES) blend_fwd_st
   bool inside[2];
 #pragma unroll
   for (int s = 0; s < 2; s++) {
-    const int py = py0 + 2 * s;
+    const int py = py0 + kStreamRowStep * s;
     pixfy[s] = (float)py;
     inside[s] = px < W && py < H;
     Tw[s] = inside[s] ? 1.0f : 0.0f; Cr[s] = Cg[s] = Cb[s] = 0.f; weight[s] = 0.f;
@@ -344,31 +378,16 @@ __global__ void __launch_bounds__(64, COORD ? 1 : RADEGS_FWD_WAVES) blend_fwd_st
     if (((bal >> (grp * 16)) & 0xFFFFull) == 0xFFFFull) n_g = 0u;
   }
 
-  float4 e0 = make_float4(0.f, 0.f, 0.f, 0.f), e1 = e0, e2 = e0;
-  auto load_rec = [&](uint32_t r) {
-    return (r * 16u + (uint32_t)l < n_g) ? *reinterpret_cast<const uint2*>(chunks + (size_t)r * kChunkWords + 2 * l) : make_uint2(0u, kNoPos);
-  };
-  auto gather_b = [&](const uint2 rec) {   // coord-map mode: the 48-byte camera-plane record, one lane per entry
-    if constexpr (COORD) {
-      // loaded unconditionally (an idle lane reads record 0) and zeroed by selects: loads under a branch reach the staging code through a
-      // PHI that the register allocator parks in scratch -- a store, a full wait and a load per round
-      const bool live = rec.y != kNoPos;
-      const float4* sb = a.splat_b + 3 * (size_t)(live ? rec.x : 0u);
-      const float4 t0 = sb[0], t1 = sb[1], t2 = sb[2];
-      const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-      e0 = live ? t0 : z; e1 = live ? t1 : z; e2 = live ? t2 : z;
-    }
-  };
   uint32_t nmax = row_uniform_max(n_g);
   const int goff = grp * kGrpSlots;
 
   for (uint32_t r = 0; r * 16u < nmax; r++) {
-    const uint2 rec = load_rec(r);
-    gather_b(rec);
+    const uint2 rec = load_list_word(chunks, r, l, n_g);
+    const PlaneRec pl = gather_planes<COORD>(a.splat_b, rec);
     __syncthreads();   // (one wave per workgroup: orders this round's LDS writes after the previous round's reads)
     gather_rows_to_lds(a.splat_a, rec.y != kNoPos ? rec.x : kNoId, lane, lds_a, kGrpSlots * 4);
     lds_con[grp * 16 + l] = rec.y + 1u;
-    if constexpr (COORD) { lds_b[(goff + l) * 3 + 0] = e0; lds_b[(goff + l) * 3 + 1] = e1; lds_b[(goff + l) * 3 + 2] = e2; }
+    if constexpr (COORD) { lds_b[(goff + l) * 3 + 0] = pl.e0; lds_b[(goff + l) * 3 + 1] = pl.e1; lds_b[(goff + l) * 3 + 2] = pl.e2; }
     __syncthreads();
     const int cnt = (int)min(16u, n_g - min(n_g, r * 16u));   // live entries of this row in this round
     const int trip = __builtin_amdgcn_readfirstlane((int)min(16u, nmax - r * 16u));   // wave-uniform, and on the scalar unit: the loop test costs no VALU slot
@@ -409,10 +428,9 @@ __global__ void __launch_bounds__(64, COORD ? 1 : RADEGS_FWD_WAVES) blend_fwd_st
           const float aT = alpha * Tw[s];
           Cr[s] = fmaf(C.x, aT, Cr[s]); Cg[s] = fmaf(C.y, aT, Cg[s]); Cb[s] = fmaf(C.z, aT, Cb[s]);
           if constexpr (COORD) {
-            const float c0 = fmaf(E0.y, dy, fmaf(E0.x, dx, E1.z));
-            const float c1 = fmaf(E0.w, dy, fmaf(E0.z, dx, E1.w));
-            const float c2 = fmaf(E1.y, dy, fmaf(E1.x, dx, E2.x));
-            Co[s][0] = fmaf(c0, aT, Co[s][0]); Co[s][1] = fmaf(c1, aT, Co[s][1]); Co[s][2] = fmaf(c2, aT, Co[s][2]);
+            float c[3];
+            coord_planes(E0, E1, E2, dx, dy, c);
+            Co[s][0] = fmaf(c[0], aT, Co[s][0]); Co[s][1] = fmaf(c[1], aT, Co[s][1]); Co[s][2] = fmaf(c[2], aT, Co[s][2]);
           }
           if constexpr (DEPTH) Dep[s] = fmaf(t_here, aT, Dep[s]);
           if constexpr (NORMAL) { Nx[s] = fmaf(Dq.y, aT, Nx[s]); Ny[s] = fmaf(Dq.z, aT, Ny[s]); Nz[s] = fmaf(Dq.w, aT, Nz[s]); }
@@ -428,10 +446,9 @@ __global__ void __launch_bounds__(64, COORD ? 1 : RADEGS_FWD_WAVES) blend_fwd_st
           const bool med = actt[s] && (Tw[s] > 0.5f);
           if constexpr (COORD) {
             const float dy = A.y - pixfy[s];
-            const float c0 = fmaf(E0.y, dy, fmaf(E0.x, dx, E1.z));
-            const float c1 = fmaf(E0.w, dy, fmaf(E0.z, dx, E1.w));
-            const float c2 = fmaf(E1.y, dy, fmaf(E1.x, dx, E2.x));
-            mCo[s][0] = med ? c0 : mCo[s][0]; mCo[s][1] = med ? c1 : mCo[s][1]; mCo[s][2] = med ? c2 : mCo[s][2];
+            float c[3];
+            coord_planes(E0, E1, E2, dx, dy, c);
+            mCo[s][0] = med ? c[0] : mCo[s][0]; mCo[s][1] = med ? c[1] : mCo[s][1]; mCo[s][2] = med ? c[2] : mCo[s][2];
           }
           if constexpr (DEPTH) mDep[s] = med ? t_dep[s] : mDep[s];
           max_c[s] = med ? contributor : max_c[s];
@@ -454,49 +471,13 @@ __global__ void __launch_bounds__(64, COORD ? 1 : RADEGS_FWD_WAVES) blend_fwd_st
   }
   if (l == 0 && n_tile) a.blk_consumed[(size_t)tile * kBlocksPerTile + blk] = n_g;
 
-  // ---- epilogue (forward.cu:631-692) ----
-  const float pnx = (pixfx - W / 2.f) / a.focal_x;
+  // ---- epilogue ----
 #pragma unroll
   for (int s = 0; s < 2; s++) {
     if (!inside[s]) continue;
-    const size_t pix = (size_t)W * (py0 + 2 * s) + px;
-    const float pny = (pixfy[s] - H / 2.f) / a.focal_y;
-    const float ln = sqrtf(pnx * pnx + pny * pny + 1);
-    a.n_contrib[pix] = last_c[s];
-    a.n_contrib[pix + HW] = max_c[s];
-    const float Tf = 1.0f - weight[s];
-    a.out_color[pix] = fmaf(Tf, a.bg[0], Cr[s]);
-    a.out_color[HW + pix] = fmaf(Tf, a.bg[1], Cg[s]);
-    a.out_color[2 * HW + pix] = fmaf(Tf, a.bg[2], Cb[s]);
-    a.out_alpha[pix] = weight[s];
-    zero_unproduced_maps<COORD, DEPTH>(a, pix, HW);
-    if constexpr (COORD) {
-#pragma unroll
-      for (int c = 0; c < 3; c++) {
-        a.out_coord[c * HW + pix] = last_c[s] ? Co[s][c] / weight[s] : 0.f;
-        a.accum_coord[c * HW + pix] = Co[s][c];
-        a.out_mcoord[c * HW + pix] = mCo[s][c];
-      }
-    }
-    if constexpr (DEPTH) {
-      const float depth_ln = Dep[s] / ln;
-      a.accum_depth[pix] = depth_ln;
-      a.out_depth[pix] = last_c[s] ? depth_ln / weight[s] : 0.f;
-      a.out_mdepth[pix] = mDep[s] / ln;
-    }
-    if constexpr (NORMAL) {
-      if (last_c[s]) {
-        float len_n = sqrtf(Nx[s] * Nx[s] + Ny[s] * Ny[s] + Nz[s] * Nz[s]);
-        a.normal_length[pix] = len_n;
-        len_n = fmaxf(len_n, 1.0E-12F);
-        a.out_normal[pix] = Nx[s] / len_n;
-        a.out_normal[HW + pix] = Ny[s] / len_n;
-        a.out_normal[2 * HW + pix] = Nz[s] / len_n;
-      } else {
-        a.normal_length[pix] = 1;
-        a.out_normal[pix] = 0; a.out_normal[HW + pix] = 0; a.out_normal[2 * HW + pix] = 0;
-      }
-    }
+    // final transmittance: 1 - weight[s] (see Tw above; the tile-wide kernel keeps the running product and passes that: radegs_kernels.hip)
+    blend_fwd_epilogue<COORD, DEPTH>(a, px, py0 + kStreamRowStep * s, 1.0f - weight[s], last_c[s], max_c[s], Cr[s], Cg[s], Cb[s], weight[s],
+                                     Co[COORD ? s : 0], mCo[COORD ? s : 0], Dep[s], mDep[s], Nx[s], Ny[s], Nz[s]);
   }
 }
 
@@ -548,14 +529,10 @@ __global__ void __launch_bounds__(64, COORD ? 3 : RADEGS_BWD_WAVES) blend_bwd_st
 
   const int item = xcd_band_remap(blockIdx.x, gridDim.x);
   const int lane = threadIdx.x, grp = lane >> 4, l = lane & 15;
-  const uint32_t bid = a.blk_order[4 * (size_t)item + grp];   // the same wave composition as the forward's
-  const int tile = (int)(bid >> 3), blk = (int)(bid & 7u);
-  const int tile_x = tile % a.gx, tile_y = tile / a.gx;
-  const int brow = blk >> 1, bcol = blk & 1;
-  const int px = tile_x * 16 + bcol * 8 + (l & 7);
-  const int py0 = tile_y * 16 + brow * 4 + (l >> 3);
+  const StreamRow geo = stream_row_geometry(a.blk_order, item, grp, l, a.gx);
+  const uint32_t bid = geo.bid;
+  const int tile = geo.tile, blk = geo.blk, px = geo.px, py0 = geo.py0;
   const int W = a.W, H = a.H;
-  const size_t HW = (size_t)H * W;
   const float pixfx = (float)px;
   const uint2 range = a.ranges[tile];
   const uint32_t n_tile = range.y - range.x;
@@ -565,84 +542,26 @@ __global__ void __launch_bounds__(64, COORD ? 3 : RADEGS_BWD_WAVES) blend_bwd_st
   if (nmax == 0u) return;
   const RowReduceAddr red = row_reduce_addr(lds_red, grp, l);
 
-  // ---- per-pixel prologue (backward.cu:706-781), as in blend_bwd_packed_kernel ----
+  // ---- per-pixel prologue ----
   float pixfy[2], T[2], Q[2], dLa[2], tb[2], dLc[2][3], dLt[2], dLmt[2], dLn[2][3];
   float dLco[COORD ? 2 : 1][3], dLmco[COORD ? 2 : 1][3];
   uint32_t max_cm1[2];
-  const float pnx = (pixfx - W / 2.f) / a.focal_x;
 #pragma unroll
   for (int s = 0; s < 2; s++) {
-    const int py = py0 + 2 * s;
+    const int py = py0 + kStreamRowStep * s;
     pixfy[s] = (float)py;
-    const bool inside = px < W && py < H;
-    const size_t pix = inside ? (size_t)W * py + px : 0;
-    const float alpha_px = inside ? a.alphas[pix] : 0.f;
-    const float T_final = inside ? (1 - alpha_px) : 0.f;
-    const float w_final = alpha_px;
-    T[s] = T_final;
-    const uint32_t last_c = inside ? a.n_contrib[pix] : 0u;
-    max_cm1[s] = (inside ? a.n_contrib[pix + HW] : 0u) - 1u;   // 0-based position; 0xFFFFFFFF (no median) never matches
-    Q[s] = 0.f;
-    dLt[s] = 0.f; dLmt[s] = 0.f;
+    const PixelCotangents ct = pixel_cotangents<COORD, DEPTH>(a, px, py);
+    T[s] = ct.T; Q[s] = 0.f; dLa[s] = ct.dLa; tb[s] = ct.tb;
+    dLt[s] = ct.dLt; dLmt[s] = ct.dLmt;
+    max_cm1[s] = ct.max_cm1;
 #pragma unroll
     for (int c = 0; c < 3; c++) {
-      dLc[s][c] = inside ? a.dL_dpix[c * HW + pix] : 0.f;
-      dLn[s][c] = 0.f;
-      if constexpr (COORD) { dLco[s][c] = 0.f; dLmco[s][c] = 0.f; }
+      dLc[s][c] = ct.dLc[c]; dLn[s][c] = ct.dLn[c];
+      if constexpr (COORD) { dLco[s][c] = ct.dLco[c]; dLmco[s][c] = ct.dLmco[c]; }
     }
-    float dla = inside ? a.dL_dalpha[pix] : 0.f;
-    tb[s] = -T_final * (a.bg[0] * dLc[s][0] + a.bg[1] * dLc[s][1] + a.bg[2] * dLc[s][2]);
-    if (NORMAL && inside && last_c > 0) {   // pixels nothing blended into pass no geometry gradient (their 1/alpha would be inf)
-      const float ww = w_final * w_final;
-      const float pny = ((float)py - H / 2.f) / a.focal_y;
-      const float ln = sqrtf(pnx * pnx + pny * pny + 1);
-      if constexpr (COORD) {
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-          const float gw = a.dL_dcoord[c * HW + pix];
-          dla -= gw * a.accum_coord[c * HW + pix] / ww;
-          dLco[s][c] = gw / w_final;
-          dLmco[s][c] = a.dL_dmcoord[c * HW + pix];
-        }
-      }
-      if constexpr (DEPTH) {
-        const float gw = a.dL_ddepth[pix];
-        dla -= gw * a.accum_depth[pix] / ww;
-        dLt[s] = gw / w_final / ln;
-        dLmt[s] = a.dL_dmdepth[pix] / ln;
-      }
-      {
-        const float g0 = a.dL_dnormal[pix], g1 = a.dL_dnormal[HW + pix], g2 = a.dL_dnormal[2 * HW + pix];
-        const float n0 = a.normalmap[pix], n1 = a.normalmap[HW + pix], n2 = a.normalmap[2 * HW + pix];
-        const float nlen = a.normal_length[pix];
-        if (nlen < 1.0E-12F) {
-          dLn[s][0] = g0 / 1.0E-12F; dLn[s][1] = g1 / 1.0E-12F; dLn[s][2] = g2 / 1.0E-12F;
-        } else {
-          const float dt = g0 * n0 + g1 * n1 + g2 * n2;
-          dLn[s][0] = (g0 - dt * n0) / nlen; dLn[s][1] = (g1 - dt * n1) / nlen; dLn[s][2] = (g2 - dt * n2) / nlen;
-        }
-      }
-    }
-    dLa[s] = dla;
   }
   const float cW = 0.5f * W, cH = 0.5f * H;
 
-  float4 e0 = make_float4(0.f, 0.f, 0.f, 0.f), e1 = e0, e2 = e0;
-  auto load_rec = [&](int r) {
-    return (r >= 0 && (uint32_t)r * 16u + (uint32_t)l < n_c) ? *reinterpret_cast<const uint2*>(chunks + (size_t)r * kChunkWords + 2 * l)
-                                                             : make_uint2(0u, kNoPos);
-  };
-  auto gather_b = [&](const uint2 rec) {   // coord-map mode: the 48-byte camera-plane record, one lane per entry
-    if constexpr (COORD) {
-      // loaded unconditionally (an idle lane reads record 0) and zeroed by selects: loads under a branch reach the staging code through a
-      // PHI that the register allocator parks in scratch -- a store, a full wait and a load per round
-      const bool live = rec.y != kNoPos;
-      const float4* sb = a.splat_b + 3 * (size_t)(live ? rec.x : 0u);
-      const float4 t0 = sb[0], t1 = sb[1], t2 = sb[2];
-      const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-      e0 = live ? t0 : z; e1 = live ? t1 : z; e2 = live ? t2 : z;
-    }
-  };
   const int rtop = (int)((nmax + 15u) >> 4) - 1;
   auto load_hist = [&](int r) { return (r >= 0 && (uint32_t)r * 16u < n_c) ? chunks[(size_t)r * kChunkWords + 32 + l] : 0u; };
   const int goff = grp * kGrpSlots;
@@ -651,13 +570,13 @@ __global__ void __launch_bounds__(64, COORD ? 3 : RADEGS_BWD_WAVES) blend_bwd_st
   // The NEXT round's list words (Gaussian id, position, contribution bits) are requested one round ahead, so that a round starts with
   // ONE memory latency (the record gather) instead of two dependent ones: behind the atomics' backlog in the memory pipe a load takes
   // its time (same-box A/B: 0.535 -> 0.524 ms; prefetching the records too costs 16 registers and loses: 0.557).
-  uint2 rec_nxt = load_rec(rtop);
+  uint2 rec_nxt = load_list_word(chunks, (uint32_t)rtop, l, n_c);
   uint32_t hist_nxt = load_hist(rtop);
   for (int r = rtop; r >= 0; r--) {
     const uint2 rec_cur = rec_nxt;
-    gather_b(rec_cur);
+    const PlaneRec pl = gather_planes<COORD>(a.splat_b, rec_cur);
     const uint32_t hist = hist_nxt;
-    rec_nxt = load_rec(r - 1); hist_nxt = load_hist(r - 1);
+    rec_nxt = load_list_word(chunks, (uint32_t)(r - 1), l, n_c); hist_nxt = load_hist(r - 1);
     __syncthreads();
     {  // stage the records as they lie in memory -- {mx,my,cx,cy} {cz,op,thr,ts} {r,g,b,rpx} {rpy,nx,ny,nz} -- four lanes per record
        // (gather_rows_to_lds), and next to them the entries' Gaussian ids and positions in the tile list
@@ -665,6 +584,7 @@ __global__ void __launch_bounds__(64, COORD ? 3 : RADEGS_BWD_WAVES) blend_bwd_st
       lds_pos[grp * 16 + l] = rec_cur.y;
       lds_id[grp * 16 + l] = rec_cur.x;
       if constexpr (COORD) {
+        const float4 e0 = pl.e0, e1 = pl.e1, e2 = pl.e2;
         lds_b[(goff + l) * 3 + 0] = v4f{e0.x, e0.y, e0.z, e0.w}; lds_b[(goff + l) * 3 + 1] = v4f{e1.x, e1.y, e1.z, e1.w};
         lds_b[(goff + l) * 3 + 2] = v4f{e2.x, e2.y, e2.z, e2.w};
       }
@@ -717,11 +637,11 @@ __global__ void __launch_bounds__(64, COORD ? 3 : RADEGS_BWD_WAVES) blend_bwd_st
         V = fmaf(C.y, dLc[s][0], V); V = fmaf(C.z, dLc[s][1], V); V = fmaf(C.w, dLc[s][2], V);
         float dco[3], dt_ = 0.f;
         if constexpr (COORD) {
-          const float cpx[3] = {E0.x, E0.z, E1.x}, cpy[3] = {E0.y, E0.w, E1.y}, vp[3] = {E1.z, E1.w, E2.x};
+          float cc[3];
+          coord_planes(E0, E1, E2, dx, dy, cc);
 #pragma unroll
           for (int c = 0; c < 3; c++) {
-            const float cc = fmaf(cpy[c], dy, fmaf(cpx[c], dx, vp[c]));
-            V = fmaf(cc, dLco[s][c], V);
+            V = fmaf(cc[c], dLco[s][c], V);
             dco[c] = dch * dLco[s][c];
           }
         }

@@ -77,6 +77,20 @@ BUDGET = [
     (("emit_instances_kernelILb1E",), 6, 0, 0),
     (("tile_ranges_kernelItE",), 8, 0, 0),
     (("integrate_kernel",), 5, 0, 16384),
+    # the tile-wide kernels (large splats: C5), template arguments <COORD, DEPTH, pixels per lane>: staged records (+ camera planes in
+    # coord mode); the backward adds the ids and row_reduce16's scratch
+    (("blend_fwd_kernelILb0ELb0ELi2EE",), 8, 0, 4160),
+    (("blend_fwd_kernelILb0ELb1ELi2EE",), 7, 0, 4160),
+    (("blend_fwd_kernelILb1ELb0ELi2EE",), 5, 0, 7232),
+    (("blend_fwd_kernelILb1ELb1ELi2EE",), 5, 0, 7232),
+    (("blend_bwd_packed_kernelILb0ELb0ELi2EE",), 7, 0, 6724),
+    (("blend_bwd_packed_kernelILb0ELb1ELi2EE",), 5, 0, 6724),
+    (("blend_bwd_packed_kernelILb1ELb0ELi2EE",), 4, 0, 9796),
+    (("blend_bwd_packed_kernelILb1ELb1ELi2EE",), 4, 0, 9796),
+    (("blend_bwd_packed_kernelILb0ELb0ELi4EE",), 4, 0, 6724),     # 4 pixels per lane: C5's backward
+    (("blend_bwd_packed_kernelILb0ELb1ELi4EE",), 3, 0, 6724),
+    (("blend_bwd_packed_kernelILb1ELb0ELi4EE",), 2, 0, 9796),
+    (("blend_bwd_packed_kernelILb1ELb1ELi4EE",), 2, 0, 9796),
 ]
 
 
