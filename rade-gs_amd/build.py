@@ -23,6 +23,10 @@ OUT_DIR = os.path.join(HERE, "diff_gaussian_rasterization")
 OBJ_DIR = os.path.join(HERE, "build")
 LIB = os.path.join(OUT_DIR, "libradegs_hip.so")
 CHECK_LIB = os.path.join(OUT_DIR, "libradegs_prims_check.so")   # test-only: rocPRIM cross-check of the hand-written sorts
+# test-only: C entry points over radegs_sort.hip's primitives with the instantiation override (tests/test_gpu_sort_scan.py); sortcheck.o +
+# radegs_sort.o in a shared object of its own, next to the rocPRIM cross-check -- never linked into the product, not package data
+SORT_CHECK_SRC = os.path.join(CSRC, "radegs_sort_check.hip")
+SORT_CHECK_LIB = os.path.join(OUT_DIR, "libradegs_sort_check.so")
 ARCH = "gfx950"   # the only target: kernels use gfx950's 160 KB LDS (radegs_sort.hip's 32-item scatter needs 70 KB per workgroup), its DPP /
                   # bank-mask forms and wave64 tilings -- changing this does not give a working gfx90a / gfx942 library
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-munsafe-fp-atomics",
@@ -71,6 +75,18 @@ def build(force=False, verbose=True):
                 subprocess.check_call(cmd)
             continue
         objs.append(obj)
+    check_obj = os.path.join(OBJ_DIR, "radegs_sort_check.o")
+    if force or _stale(check_obj, [SORT_CHECK_SRC, os.path.join(CSRC, "rg_prims.h"), os.path.abspath(__file__)]):
+        cmd = [hipcc] + FLAGS + ["-c", SORT_CHECK_SRC, "-o", check_obj]
+        if verbose:
+            print("[radegs build]", " ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+    sort_obj = os.path.join(OBJ_DIR, "radegs_sort.o")
+    if force or _stale(SORT_CHECK_LIB, [check_obj, sort_obj]):
+        cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", SORT_CHECK_LIB, check_obj, sort_obj]
+        if verbose:
+            print("[radegs build]", " ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
     if force or _stale(LIB, objs + [os.path.abspath(__file__)]):
         cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", LIB] + objs
         if verbose:

@@ -337,7 +337,9 @@ __global__ void __launch_bounds__(kSortThreads) gather_scan_kernel(const uint32_
 
 }  // namespace
 
-static int sort_items_per_thread(size_t n) {
+// items_override (rg_prims.h): 0 = the size rule below (and the env switch), 8 / 16 / 32 = that instantiation, anything else = -1 (an error)
+static int sort_items_per_thread(size_t n, int items_override) {
+  if (items_override != 0) return (items_override == 8 || items_override == 16 || items_override == 32) ? items_override : -1;
   static const int forced = [] { const char* e = getenv("RADEGS_SORT_ITEMS"); return e ? atoi(e) : 0; }();   // 8 / 16 / 32: measurements only
   if (forced == 8 || forced == 16 || forced == 32) return forced;
   // measured (C2 1 M / 3.9 M, C4 5 M / 19.6 M, C5 50 M items): 8 up to 3 M, 16 above, 32 only for tens of millions
@@ -357,11 +359,12 @@ size_t sort_temp_bytes(size_t n) {
 template <class K>
 static hipError_t radix_sort_pairs(void* temp, size_t temp_bytes, const K* keys_in, K* keys_out, const uint32_t* vals_in,
                                    uint32_t* vals_out, size_t n, int end_bit, hipStream_t stream, const uint32_t* n_dev,
-                                   uint32_t key_base = 0, int digit_bits = 8) {
+                                   int items_override, uint32_t key_base = 0, int digit_bits = 8) {
   if (n == 0) return hipSuccess;
   if (temp_bytes < sort_temp_bytes(n)) return hipErrorInvalidValue;
   if (n > 0xFFFFFFFFull - 65536) return hipErrorInvalidValue;
-  const int items = sort_items_per_thread(n);
+  const int items = sort_items_per_thread(n, items_override);
+  if (items < 0) return hipErrorInvalidValue;
   const uint32_t nblocks = (uint32_t)((n + (size_t)kSortThreads * items - 1) / ((size_t)kSortThreads * items));
   char* p = static_cast<char*>(temp);
   auto take = [&](size_t bytes) { char* r = p; p += (bytes + 255) & ~size_t(255); return r; };
@@ -407,28 +410,32 @@ static hipError_t radix_sort_pairs(void* temp, size_t temp_bytes, const K* keys_
 }
 
 hipError_t radix_sort_pairs_u32(void* temp, size_t temp_bytes, const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in,
-                                uint32_t* vals_out, size_t n, int end_bit, hipStream_t stream, const uint32_t* n_dev) {
-  return radix_sort_pairs<uint32_t>(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, n, end_bit, stream, n_dev);
+                                uint32_t* vals_out, size_t n, int end_bit, hipStream_t stream, const uint32_t* n_dev, int items_override) {
+  return radix_sort_pairs<uint32_t>(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, n, end_bit, stream, n_dev, items_override);
 }
 // Sorts on bits [0, 27) of (key - key_base) in THREE passes of 9-bit digits (512 bins).  For keys that are the float bits of values in
 // [bits^-1(key_base), ...) the caller guarantees (key - key_base) < 2^27 for every item whose order matters; other items land anywhere.
 hipError_t radix_sort_pairs_u32_27(void* temp, size_t temp_bytes, const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in,
-                                   uint32_t* vals_out, size_t n, uint32_t key_base, hipStream_t stream) {
-  return radix_sort_pairs<uint32_t>(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, n, 27, stream, nullptr, key_base, 9);
+                                   uint32_t* vals_out, size_t n, uint32_t key_base, hipStream_t stream, int items_override) {
+  return radix_sort_pairs<uint32_t>(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, n, 27, stream, nullptr, items_override, key_base, 9);
 }
 // the same sort over 16-bit keys (end_bit <= 16)
 hipError_t radix_sort_pairs_u16(void* temp, size_t temp_bytes, const uint16_t* keys_in, uint16_t* keys_out, const uint32_t* vals_in,
-                                uint32_t* vals_out, size_t n, int end_bit, hipStream_t stream, const uint32_t* n_dev) {
+                                uint32_t* vals_out, size_t n, int end_bit, hipStream_t stream, const uint32_t* n_dev, int items_override) {
   if (end_bit > 16) return hipErrorInvalidValue;
-  return radix_sort_pairs<uint16_t>(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, n, end_bit, stream, n_dev);
+  return radix_sort_pairs<uint16_t>(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, n, end_bit, stream, n_dev, items_override);
 }
 
 }  // namespace rg
 
 namespace rg {
-static int scan_items_per_thread(size_t n) { return n <= (size_t(2) << 20) ? 4 : kScanItemsMax; }
+// items_override (rg_prims.h): 0 = the size rule, 4 / 16 = that instantiation, anything else = -1 (an error)
+static int scan_items_per_thread(size_t n, int items_override) {
+  if (items_override != 0) return (items_override == 4 || items_override == kScanItemsMax) ? items_override : -1;
+  return n <= (size_t(2) << 20) ? 4 : kScanItemsMax;
+}
 size_t scan_temp_bytes(size_t n) {   // block sums (u32) + partial sums of squares (u64) per block, then the gathered copy
-  const size_t per_block = (size_t)kSortThreads * scan_items_per_thread(n);
+  const size_t per_block = (size_t)kSortThreads * 4;   // the smaller block: an upper bound for both instantiations at every n
   return ((n + per_block - 1) / per_block + 64) * (sizeof(uint32_t) + sizeof(unsigned long long)) + 1024 + n * sizeof(uint32_t);
 }
 
@@ -436,10 +443,11 @@ size_t scan_temp_bytes(size_t n) {   // block sums (u32) + partial sums of squar
 // packed_out != nullptr: `vals` are packed tile rectangles, the scan runs over their tile counts and packed_out[i] receives
 // vals[idx[i]] (n words).
 hipError_t inclusive_scan_gather_u32(void* temp, size_t temp_bytes, const uint32_t* vals, const uint32_t* idx, uint32_t* out, size_t n,
-                                     hipStream_t stream, uint32_t* packed_out, unsigned long long* sq_sum) {
+                                     hipStream_t stream, uint32_t* packed_out, unsigned long long* sq_sum, int items_override) {
   if (n == 0) return hipSuccess;
   if (temp_bytes < scan_temp_bytes(n)) return hipErrorInvalidValue;
-  const int items = scan_items_per_thread(n);
+  const int items = scan_items_per_thread(n, items_override);
+  if (items < 0) return hipErrorInvalidValue;
   const uint32_t nblocks = (uint32_t)((n + (size_t)kSortThreads * items - 1) / ((size_t)kSortThreads * items));
   const uint32_t nb64 = (nblocks + 64) & ~63u;
   unsigned long long* sq_part = static_cast<unsigned long long*>(temp);                // [nb64] (8-byte aligned: first in the buffer)

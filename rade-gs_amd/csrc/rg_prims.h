@@ -23,15 +23,17 @@ typedef hipError_t (*prims_sort_by_tile_fn)(void* temp, size_t temp_bytes, const
                                             const uint32_t* vals_in, uint32_t* vals_out, size_t R, int tile_bits, hipStream_t stream);
 
 // ---- hand-written primitives (radegs_sort.hip) ----
+// items_override: 0 = the size rule (and RADEGS_SORT_ITEMS); 8 / 16 / 32 (sorts), 4 / 16 (scan) pick the instantiation at any n -- used only by
+// the primitive tests (radegs_sort_check.hip -> libradegs_sort_check.so); the *_temp_bytes bounds hold for every allowed value.
 size_t sort_temp_bytes(size_t n);
 size_t scan_temp_bytes(size_t n);
 hipError_t radix_sort_pairs_u32(void* temp, size_t temp_bytes, const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in,
-                                uint32_t* vals_out, size_t n, int end_bit, hipStream_t stream, const uint32_t* n_dev = nullptr);
+                                uint32_t* vals_out, size_t n, int end_bit, hipStream_t stream, const uint32_t* n_dev = nullptr, int items_override = 0);
 hipError_t radix_sort_pairs_u32_27(void* temp, size_t temp_bytes, const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in,
-                                   uint32_t* vals_out, size_t n, uint32_t key_base, hipStream_t stream);
+                                   uint32_t* vals_out, size_t n, uint32_t key_base, hipStream_t stream, int items_override = 0);
 hipError_t radix_sort_pairs_u16(void* temp, size_t temp_bytes, const uint16_t* keys_in, uint16_t* keys_out, const uint32_t* vals_in,
-                                uint32_t* vals_out, size_t n, int end_bit, hipStream_t stream, const uint32_t* n_dev = nullptr);
+                                uint32_t* vals_out, size_t n, int end_bit, hipStream_t stream, const uint32_t* n_dev = nullptr, int items_override = 0);
 hipError_t inclusive_scan_gather_u32(void* temp, size_t temp_bytes, const uint32_t* vals, const uint32_t* idx, uint32_t* out, size_t n,
-                                     hipStream_t stream, uint32_t* packed_out = nullptr, unsigned long long* sq_sum = nullptr);
+                                     hipStream_t stream, uint32_t* packed_out = nullptr, unsigned long long* sq_sum = nullptr, int items_override = 0);
 
 }  // namespace rg

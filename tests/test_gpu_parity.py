@@ -408,6 +408,43 @@ def test_handwritten_sort_matches_device_library():
     assert outs[0] == outs[1], outs
 
 
+def test_forced_sort_instantiations_give_the_same_lists():
+    """The 16- and 32-items-per-thread sort kernels, which the size rule picks only above 3 M and 32 M items, forced onto the same
+    scene (RADEGS_SORT_ITEMS, read once per process, hence the subprocesses): point_list and ranges identical to the rule's 8-item
+    kernels.  Two forwards in a row under RADEGS_SPECULATE=1: the second tile sort runs at a predicted capacity with the count read on
+    the device (n_dev).  The primitives on their own: tests/test_gpu_sort_scan.py."""
+    import os
+    import subprocess
+    import sys
+    code = (
+        "import sys, hashlib, numpy as np, torch\n"
+        "sys.path[:0] = [%r, %r, %r]\n"
+        "import diff_gaussian_rasterization._C as C\n"
+        "from gpu_util import HipRun\n"
+        "from synth_scene import make_scene\n"
+        "s = make_scene(150000, 640, 360, sh_degree=1, mu_px=2.5, seed=77, require_depth=True)\n"
+        "C.binning_stats(reset=True)\n"
+        "for it in range(2):\n"
+        "    h = HipRun(s, 'cuda:0'); st = h.forward_native(); torch.cuda.synchronize()\n"
+        "    pl = h.export('point_list', torch.int32, st[0]); rg = h.export('ranges', torch.int32, 2 * 40 * 23)\n"
+        "    print('HASH', it, st[0], hashlib.sha1(pl.tobytes() + rg.tobytes()).hexdigest())\n"
+        "print('SPEC', C.binning_stats())\n"
+    ) % tuple(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), p) for p in ("", "rade-gs_amd", "tests"))
+    outs = []
+    for items in (None, "16", "32"):      # one process after the other
+        env = dict(os.environ, RADEGS_SPECULATE="1")
+        env.pop("RADEGS_SORT_ITEMS", None)
+        if items:
+            env["RADEGS_SORT_ITEMS"] = items
+        r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = r.stdout.splitlines()
+        assert [l for l in lines if l.startswith("SPEC")] == ["SPEC (1, 0)"], lines     # the second forward was speculative and was not redone
+        outs.append([l for l in lines if l.startswith("HASH")])
+    assert len(outs[0]) == 2 and outs[0][0].split()[2:] == outs[0][1].split()[2:], outs[0]
+    assert outs[0] == outs[1] == outs[2], outs
+
+
 def test_depths_beyond_the_three_pass_sort_window(monkeypatch):
     """The depth sort runs three 9-bit passes over (key - bits(0.2f)), valid while every visible depth is below 13 107; the per-Gaussian
     kernel flags a key outside that window and the forward is redone with the four-pass sort (rg_launch.inc).  A scene scaled 3 000x
