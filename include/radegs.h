@@ -244,7 +244,14 @@ size_t radegs_binning_bytes(int R);
  * (device memory, dst_bytes large enough).  Names: "point_list" u32[R], "ranges" u32[2*tiles],
  * "n_contrib" u32[2*H*W], "tiles_touched" u32[P], "splat_a" f32[P,16], "splat_b" f32[P,12],
  * "clamped" u8[P] (bits 0..2: SH channel clamped at 0; bit 3: the eigen-solver converged), "depth_key" u32[P], "blk_count" /
- * "blk_consumed" u32[8*tiles] (entry streams).  Returns bytes copied or a negative error. */
+ * "blk_consumed" u32[8*tiles] (entry streams), "rect" u32[P] (packed tile rectangle x0 | y0<<8 | w<<16 | h<<24),
+ * "tile_keys_sorted" u32[R] (the binning buffer's sorted tile keys: 32-bit keys only, e.g. with the block mask in the top byte; and
+ * only after a forward whose binning buffer was sized for exactly R instances, RADEGS_SPECULATE=0: the array's offset depends on the capacity),
+ * and after a forward that wrote entry streams "blk_base" / "blk_order" u32[8*tiles], "stream_meta" u32[4] (tag 0x53545247, chunks the
+ * lists need, unused, overflow flag) and "blk_chunks": round chunks of 48 words from chunk 0 on -- the LAST array of the image state, so
+ * this function cannot know where the buffer ends: it copies exactly dst_bytes, and the caller, who asks for stream_meta[1] * 48 words,
+ * must check radegs_image_bytes(width, height) - 256 + dst_bytes against the size of its image buffer (_C.debug_export does).
+ * Returns bytes copied or a negative error. */
 long long radegs_debug_export(const char* name, int P, int R, int width, int height, int require_coord, const void* geom_buffer,
                               const void* binning_buffer, const void* image_buffer, void* dst, size_t dst_bytes, void* stream);
 

@@ -27,6 +27,10 @@ CHECK_LIB = os.path.join(OUT_DIR, "libradegs_prims_check.so")   # test-only: roc
 # radegs_sort.o in a shared object of its own, next to the rocPRIM cross-check -- never linked into the product, not package data
 SORT_CHECK_SRC = os.path.join(CSRC, "radegs_sort_check.hip")
 SORT_CHECK_LIB = os.path.join(OUT_DIR, "libradegs_sort_check.so")
+# test-only: the device build of rg_blend.h's decision pieces behind C entry points (tests/test_gpu_stream_lists.py); same FLAGS as the
+# product, a shared object of its own -- never linked into the product, not package data
+BLEND_CHECK_SRC = os.path.join(CSRC, "radegs_blend_check.hip")
+BLEND_CHECK_LIB = os.path.join(OUT_DIR, "libradegs_blend_check.so")
 ARCH = "gfx950"   # the only target: kernels use gfx950's 160 KB LDS (radegs_sort.hip's 32-item scatter needs 70 KB per workgroup), its DPP /
                   # bank-mask forms and wave64 tilings -- changing this does not give a working gfx90a / gfx942 library
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-munsafe-fp-atomics",
@@ -84,6 +88,17 @@ def build(force=False, verbose=True):
     sort_obj = os.path.join(OBJ_DIR, "radegs_sort.o")
     if force or _stale(SORT_CHECK_LIB, [check_obj, sort_obj]):
         cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", SORT_CHECK_LIB, check_obj, sort_obj]
+        if verbose:
+            print("[radegs build]", " ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+    blend_obj = os.path.join(OBJ_DIR, "radegs_blend_check.o")
+    if force or _stale(blend_obj, [BLEND_CHECK_SRC, os.path.join(CSRC, "rg_blend.h"), os.path.join(CSRC, "rg_math.h"), os.path.abspath(__file__)]):
+        cmd = [hipcc] + FLAGS + ["-c", BLEND_CHECK_SRC, "-o", blend_obj]
+        if verbose:
+            print("[radegs build]", " ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+    if force or _stale(BLEND_CHECK_LIB, [blend_obj]):
+        cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", BLEND_CHECK_LIB, blend_obj]
         if verbose:
             print("[radegs build]", " ".join(cmd), flush=True)
         subprocess.check_call(cmd)

@@ -205,11 +205,7 @@ __global__ void __launch_bounds__(256) emit_instances_kernel(int P, const uint32
     const int w_own = x1 - x0;
     EllipseSetup e_own;
     e_own.kind = 0; e_own.cy = 0.f; e_own.det = 0.f; e_own.cxM = 0.f; e_own.icx = 0.f; e_own.hx = 0.f; e_own.hy = 0.f; e_own.tstar = 0.f; e_own.eps = 0.f;
-    if (ntiles) {
-      const float U = fmaxf(fabsf((float)(x0 * 16) - q0.x), fabsf((float)(x1 * 16 - 1) - q0.x));
-      const float V = fmaxf(fabsf((float)(y0 * 16) - q0.y), fabsf((float)(y1 * 16 - 1) - q0.y));
-      e_own = ellipse_setup(q0.x, q0.y, q0.z, q0.w, q1.x, q1.z, U, V);
-    }
+    if (ntiles) e_own = ellipse_setup_rect(q0.x, q0.y, q0.z, q0.w, q1.x, q1.z, x0, y0, x1, y1);
     for (uint32_t base = 0; base < total; base += 64) {
       const uint32_t t = base + (uint32_t)lane;
       int g = 0;                                   // largest lane k with excl_k <= t (excl is non-decreasing, excl_0 = 0)
@@ -227,13 +223,11 @@ __global__ void __launch_bounds__(256) emit_instances_kernel(int P, const uint32
       e.icx = __shfl(e_own.icx, g); e.hx = __shfl(e_own.hx, g); e.hy = __shfl(e_own.hy, g); e.tstar = __shfl(e_own.tstar, g);
       e.eps = __shfl(e_own.eps, g);
       if (t < total) {
-        // row-major position in the splat's rectangle: local = ty * w + tx (local < 2^24: exact in float; the quotient is corrected by one)
-        uint32_t ty = (uint32_t)((float)local * __builtin_amdgcn_rcpf((float)g_w));
-        int tx = (int)local - (int)(ty * (uint32_t)g_w);
-        if (tx < 0) { ty--; tx += g_w; } else if (tx >= g_w) { ty++; tx -= g_w; }
+        // row-major position in the splat's rectangle: local = ty * w + tx (rg_blend.h)
+        RG_RECT_TILE_OF(local, g_w, tx, ty)
         const uint32_t pos = g_off + local;
         if (pos < cap) {
-          const uint32_t mask = ellipse_tile_mask(e, (float)((g_x0 + tx) * 16) - g_mx, (float)((g_y0 + (int)ty) * 16) - g_my) << kMaskShift;
+          const uint32_t mask = ellipse_rect_tile_mask(e, g_mx, g_my, g_x0, g_y0, tx, (int)ty) << kMaskShift;
           const uint32_t tile = (uint32_t)((g_y0 + (int)ty) * gx + (g_x0 + tx));
           if (key16) tile_keys16[pos] = (uint16_t)tile; else tile_keys[pos] = tile | (mask_in_key ? mask : 0u);
           vals[pos] = mask_in_key ? g_idx : (g_idx | mask);

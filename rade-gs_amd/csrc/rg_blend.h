@@ -156,5 +156,23 @@ RG_HD uint32_t ellipse_block_mask(float mx, float my, float cx, float cy, float 
   const float U = fmaxf(fabsf(ua), fabsf(ua + 15.f)), V = fmaxf(fabsf(va0), fabsf(va0 + 15.f));
   return ellipse_tile_mask(ellipse_setup(mx, my, cx, cy, cz, thr, U, V), ua, va0);
 }
+// The same question asked once per splat for its whole tile rectangle [x0, x1) x [y0, y1) (tile units), as emit_instances_kernel<true> asks it
+// (the device check shim, radegs_blend_check.hip, runs these lines too): the set-up with U, V from the rectangle's outermost pixel centres, ...
+RG_HD EllipseSetup ellipse_setup_rect(float mx, float my, float cx, float cy, float cz, float thr, int x0, int y0, int x1, int y1) {
+  const float U = fmaxf(fabsf((float)(x0 * 16) - mx), fabsf((float)(x1 * 16 - 1) - mx));
+  const float V = fmaxf(fabsf((float)(y0 * 16) - my), fabsf((float)(y1 * 16 - 1) - my));
+  return ellipse_setup(mx, my, cx, cy, cz, thr, U, V);
+}
+// ... the tile (tx, ty) inside the rectangle of its row-major position local = ty * w + tx (local < 2^24: exact in float; the quotient by the
+// approximate reciprocal is off by at most one and corrected) -- a macro that declares `int tx; uint32_t ty;`, because as an inlined function
+// these lines changed the emission kernel's register allocation and instruction count --, ...
+#define RG_RECT_TILE_OF(local, w, tx, ty)                                   \
+  uint32_t ty = (uint32_t)((float)(local) * RG_RCP_APPROX((float)(w)));     \
+  int tx = (int)(local) - (int)(ty * (uint32_t)(w));                        \
+  if (tx < 0) { ty--; tx += (w); } else if (tx >= (w)) { ty++; tx -= (w); }
+// ... and that tile's mask.
+RG_HD uint32_t ellipse_rect_tile_mask(const EllipseSetup& e, float mx, float my, int x0, int y0, int tx, int ty) {
+  return ellipse_tile_mask(e, (float)((x0 + tx) * 16) - mx, (float)((y0 + ty) * 16) - my);
+}
 
 }  // namespace rg

@@ -1052,6 +1052,14 @@ long long radegs_debug_export(const char* name, int P, int R, int width, int hei
   else if (n == "depth_key") { src = gs.depth_key; bytes = (size_t)P * 4; }
   else if (n == "blk_count") { src = is.blk_count; bytes = tiles * kBlocksPerTile * 4; }        // entry streams (valid after a stream forward)
   else if (n == "blk_consumed") { src = is.blk_consumed; bytes = tiles * kBlocksPerTile * 4; }
+  else if (n == "blk_base") { src = is.blk_base; bytes = tiles * kBlocksPerTile * 4; }
+  else if (n == "blk_order") { src = is.blk_order; bytes = tiles * kBlocksPerTile * 4; }
+  else if (n == "stream_meta") { src = is.stream_tag; bytes = 16; }
+  // the last array of the image state: its base does not depend on the capacity the forward allocated, and this function cannot know that
+  // capacity -- the caller asks for stream_meta[1] * 48 words and answers for the buffer's size itself (radegs_image_bytes(w, h) - 256 + those)
+  else if (n == "blk_chunks") { src = is.blk_chunks; bytes = dst_bytes; }
+  else if (n == "tile_keys_sorted") { src = bs.tile_keys_sorted; bytes = (size_t)R * 4; }
+  else if (n == "rect") { src = gs.rect; bytes = (size_t)P * 4; }
   else return fail(RADEGS_ERR_INVALID_ARG, "unknown array name");
   if (bytes > dst_bytes) return fail(RADEGS_ERR_INVALID_ARG, "destination too small");
   if (bytes == 0) return 0;

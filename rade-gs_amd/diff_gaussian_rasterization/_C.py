@@ -623,6 +623,13 @@ def debug_export(name, dtype, numel, P, R, W, H, require_coord, geomBuffer, binn
     L = library()
     dev = geomBuffer.device
     dst = torch.empty(numel, dtype=dtype, device=dev)
+    if name == "blk_chunks":
+        # the last array of the image state, copied at the size asked for: it starts where a state without stream storage ends, less
+        # the layout's 256 bytes of tail padding (csrc/rg_layout.h: Carver::total)
+        end = int(L.radegs_image_bytes(int(W), int(H))) - 256 + dst.numel() * dst.element_size()
+        have = imageBuffer.numel() * imageBuffer.element_size()
+        if end > have:
+            raise RuntimeError(f"debug_export: blk_chunks of {dst.numel() * dst.element_size()} bytes would end at byte {end} of an image state of {have}")
     with torch.cuda.device(dev):
         n = L.radegs_debug_export(name.encode(), int(P), int(R), int(W), int(H), int(bool(require_coord)),
                                   ctypes.c_void_p(geomBuffer.data_ptr()) if geomBuffer.numel() else None,

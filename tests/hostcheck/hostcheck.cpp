@@ -161,6 +161,52 @@ void hc_block_masks_rect(int n, const float* rec, int tx0, int ty0, int tx1, int
   }
 }
 
+// Brute-force truth for a list of (record, tile origin) pairs, from records as the device stores them: rec = records of `stride` floats whose
+// words 0..5 are mx, my, cx, cy, cz, op (an exported splat_a record: stride 16, word 5 = op, word 6 = thr), pair i uses record gid[i] (record
+// i when gid is null) against the 16x16 tile whose first pixel is (ox[i], oy[i]).  The per-pixel rule is hc_block_masks' own.
+void hc_truth_masks(int n, const float* rec, int stride, const unsigned* gid, const float* ox, const float* oy, unsigned* out) {
+  for (int i = 0; i < n; i++) {
+    const float* r = rec + (size_t)stride * (gid ? gid[i] : (unsigned)i);
+    const float mx = r[0], my = r[1], cx = r[2], cy = r[3], cz = r[4], op = r[5];
+    unsigned truth = 0;
+    for (int b = 0; b < 8; b++) {
+      bool any = false;
+      for (int py = 0; py < 4 && !any; py++)
+        for (int px = 0; px < 8 && !any; px++) {
+          const float dx = mx - (ox[i] + (float)((b & 1) * 8 + px)), dy = my - (oy[i] + (float)((b >> 1) * 4 + py));
+          const float power = splat_power((cx * dx) * dx, cy * dx, cz, dy);
+          if (power > 0.0f) continue;
+          if (!(fminf(0.99f, op * exp_spec(power)) < 1.0f / 255.0f)) any = true;
+        }
+      if (any) truth |= 1u << b;
+    }
+    out[i] = truth;
+  }
+}
+
+// The host ellipse_* mask in the emission's call pattern with a rectangle PER SPLAT: rec [n][stride] with words 0..4 = mx, my, cx, cy, cz and
+// word 6 = thr (taken as stored, not recomputed); rect [n][4] = x0, y0, x1, y1 in tiles; off [n] = first output position of each splat;
+// out: one mask per (splat, tile), rows outer -- the tile recovered from its row-major number as the emission recovers it.
+void hc_masks_rect_each(int n, const float* rec, int stride, const int* rect, const unsigned* off, unsigned* out) {
+  for (int i = 0; i < n; i++) {
+    const float* r = rec + (size_t)stride * i;
+    const int x0 = rect[4 * i], y0 = rect[4 * i + 1], x1 = rect[4 * i + 2], y1 = rect[4 * i + 3];
+    const int w = x1 - x0;
+    const EllipseSetup e = ellipse_setup_rect(r[0], r[1], r[2], r[3], r[4], r[6], x0, y0, x1, y1);
+    for (unsigned local = 0; local < (unsigned)(w * (y1 - y0)); local++) {
+      RG_RECT_TILE_OF(local, w, tx, ty)
+      out[off[i] + local] = ellipse_rect_tile_mask(e, r[0], r[1], x0, y0, tx, (int)ty);
+    }
+  }
+}
+
+void hc_exp_spec_vec(long long n, const float* x, float* out_spec, float* out_floor) {
+  for (long long i = 0; i < n; i++) { out_spec[i] = exp_spec(x[i]); out_floor[i] = exp_spec_floor(x[i]); }
+}
+void hc_skip_threshold_vec(int n, const float* op, float* thr) {
+  for (int i = 0; i < n; i++) thr[i] = skip_threshold(op[i]);
+}
+
 float hc_exp_spec(float x) { return exp_spec(x); }
 // The specification as the oracle spells it (rintf + integer conversion); exp_spec / exp_spec_floor (rg_blend.h) reach k through a
 // magic-number addition instead.  Counts the bit patterns in [lo_bits, hi_bits] (step `stride`) on which either differs from it.

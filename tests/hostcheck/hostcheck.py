@@ -2,6 +2,7 @@
 compiled for the CPU) -- see hostcheck.cpp."""
 import ctypes
 import os
+import shutil
 import subprocess
 
 import numpy as np
@@ -14,6 +15,8 @@ _LIB = None
 def build(force=False):
     so = os.path.join(_HERE, "libhostcheck.so")
     deps = [os.path.join(_HERE, "hostcheck.cpp")] + [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith(".h")]
+    if os.path.exists(so) and not force and shutil.which("g++") is None:
+        return so   # a machine without a compiler (the GPU box) uses the library that was built where there is one
     if force or not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-mfma",
                                "-Wno-unknown-pragmas", "-I", _CSRC, "-shared", "-o", so, os.path.join(_HERE, "hostcheck.cpp")])
@@ -113,3 +116,45 @@ def block_masks_rect(rec, tx0, ty0, tx1, ty1):
     out = np.zeros((rec.shape[0], tiles, 2), np.uint32)
     lib().hc_block_masks_rect(ctypes.c_int(rec.shape[0]), _p(rec), ctypes.c_int(tx0), ctypes.c_int(ty0), ctypes.c_int(tx1), ctypes.c_int(ty1), _p(out))
     return out[:, :, 0], out[:, :, 1]
+
+
+def _u(a):
+    return None if a is None else np.ascontiguousarray(np.asarray(a).astype(np.uint32, copy=False))
+
+
+def truth_masks(rec, gid, ox, oy):
+    """Brute-force truth (the kernels' per-pixel rule) for pairs (record gid[i] of rec [*, stride], tile with first pixel (ox[i], oy[i]));
+    gid None: record i.  Words 0..5 of a record = mx, my, cx, cy, cz, op (an exported splat_a record as it is).  -> uint32 [n]."""
+    rec = _f(rec)
+    ox, oy = _f(ox), _f(oy)
+    gid = _u(gid)
+    out = np.zeros(ox.shape[0], np.uint32)
+    lib().hc_truth_masks(ctypes.c_int(ox.shape[0]), _p(rec), ctypes.c_int(rec.shape[1]), _p(gid), _p(ox), _p(oy), _p(out))
+    return out
+
+
+def masks_rect_each(rec, rect):
+    """The host-compiled ellipse_* mask in the emission's call pattern, one rectangle per splat: rec [n, stride >= 7] with words 0..4 = mx, my, cx,
+    cy, cz and word 6 = thr; rect [n, 4] = x0, y0, x1, y1 (tiles) -> (mask uint32 [sum of tiles], rows outer; off [n] first position of each splat)."""
+    rec = _f(rec)
+    rect = np.ascontiguousarray(rect, dtype=np.int32)
+    cnt = ((rect[:, 2] - rect[:, 0]) * (rect[:, 3] - rect[:, 1])).astype(np.int64)
+    off = np.concatenate([[0], np.cumsum(cnt)[:-1]]).astype(np.uint32) if len(cnt) else np.zeros(0, np.uint32)
+    out = np.zeros(int(cnt.sum()), np.uint32)
+    lib().hc_masks_rect_each(ctypes.c_int(rec.shape[0]), _p(rec), ctypes.c_int(rec.shape[1]), _p(rect), _p(off), _p(out))
+    return out, off
+
+
+def exp_spec_vec(x):
+    """(exp_spec(x), exp_spec_floor(x)) of the host build, float32 arrays."""
+    x = _f(x).ravel()
+    a, b = np.zeros_like(x), np.zeros_like(x)
+    lib().hc_exp_spec_vec(ctypes.c_longlong(x.shape[0]), _p(x), _p(a), _p(b))
+    return a, b
+
+
+def skip_threshold_vec(op):
+    op = _f(op).ravel()
+    out = np.zeros_like(op)
+    lib().hc_skip_threshold_vec(ctypes.c_int(op.shape[0]), _p(op), _p(out))
+    return out

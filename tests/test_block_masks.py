@@ -20,17 +20,26 @@ def _conics(n, rng, sig_lo, sig_hi, aspect_hi, filt):
     return (d / det).astype(np.float32), (-b / det).astype(np.float32), (a / det).astype(np.float32)   # conic = inverse
 
 
-@pytest.mark.parametrize("name,sig_lo,sig_hi,aspect_hi,filt", [("small", 0.3, 6.0, 4.0, 0.3), ("large", 4.0, 300.0, 8.0, 0.3),
-                                                                ("needles", 0.5, 200.0, 3000.0, 0.0), ("mixed", 0.2, 60.0, 50.0, 0.1)])
-def test_block_mask_never_drops_a_reachable_block(name, sig_lo, sig_hi, aspect_hi, filt):
-    rng = np.random.default_rng({"small": 1, "large": 2, "needles": 3, "mixed": 4}[name])
-    n = 120000
+FAMILIES = {"small": (1, 0.3, 6.0, 4.0, 0.3), "large": (2, 4.0, 300.0, 8.0, 0.3), "needles": (3, 0.5, 200.0, 3000.0, 0.0),
+            "mixed": (4, 0.2, 60.0, 50.0, 0.1)}   # name -> seed, sig_lo, sig_hi, aspect_hi, filt
+
+
+def _family(name, n=120000):
+    """-> (mx, my, cx, cy, cz, op, tx0, ty0) of one family (shared with tests/test_gpu_stream_lists.py: the same records on the device)"""
+    seed, sig_lo, sig_hi, aspect_hi, filt = FAMILIES[name]
+    rng = np.random.default_rng(seed)
     cx, cy, cz = _conics(n, rng, sig_lo, sig_hi, aspect_hi, filt)
     tx0, ty0 = 16.0 * rng.integers(0, 240), 16.0 * rng.integers(0, 135)
     reach = 3.0 * np.sqrt(np.maximum(1.0 / np.minimum(cx, cz), 1.0))     # means up to ~3 sigma-ish outside the tile as well as inside
     mx = (tx0 + rng.uniform(-1.0, 1.0, n) * (8 + reach) + 7.5).astype(np.float32)
     my = (ty0 + rng.uniform(-1.0, 1.0, n) * (8 + reach) + 7.5).astype(np.float32)
     op = np.exp(rng.uniform(np.log(1.0 / 300.0), 0.0, n)).astype(np.float32)
+    return mx, my, cx, cy, cz, op, tx0, ty0
+
+
+@pytest.mark.parametrize("name,sig_lo,sig_hi,aspect_hi,filt", [(k,) + v[1:] for k, v in FAMILIES.items()])
+def test_block_mask_never_drops_a_reachable_block(name, sig_lo, sig_hi, aspect_hi, filt):
+    mx, my, cx, cy, cz, op, tx0, ty0 = _family(name)
     mask, truth = hc.block_masks(np.stack([mx, my, cx, cy, cz, op], 1), tx0, ty0)
     missed = truth & ~mask
     assert not missed.any(), (name, int((missed != 0).sum()), np.stack([mx, my, cx, cy, cz, op], 1)[missed != 0][:5])
@@ -40,28 +49,40 @@ def test_block_mask_never_drops_a_reachable_block(name, sig_lo, sig_hi, aspect_h
         assert kept <= 1.25 * needed + 100    # and it still culls: at most 25 % above the exact answer on ordinary splats
 
 
+EDGE_RECORDS = np.array([[8, 8, 1, 0, 1, 1.0 / 400.0],            # opacity below 1/255: nothing can blend
+                         [8, 8, np.nan, 0, 1, 0.5],                # NaN conic: keep everything (the exact rule decides)
+                         [8, 8, 1, 2, 1, 0.5],                     # indefinite conic: keep everything
+                         [8, 8, 0.0, 0, 1, 0.5],                   # degenerate: keep everything
+                         [-500, -500, 1, 0, 1, 0.9],               # far away small splat: nothing
+                         [3.2, 1.7, 4, 0, 4, 0.9]], np.float32)    # tiny splat inside block 0 only
+EDGE_MASKS = [0, 255, 255, 255, 0, 1]
+
+
 def test_block_mask_edge_cases():
-    rec = np.array([[8, 8, 1, 0, 1, 1.0 / 400.0],            # opacity below 1/255: nothing can blend
-                    [8, 8, np.nan, 0, 1, 0.5],                # NaN conic: keep everything (the exact rule decides)
-                    [8, 8, 1, 2, 1, 0.5],                     # indefinite conic: keep everything
-                    [8, 8, 0.0, 0, 1, 0.5],                   # degenerate: keep everything
-                    [-500, -500, 1, 0, 1, 0.9],               # far away small splat: nothing
-                    [3.2, 1.7, 4, 0, 4, 0.9]], np.float32)    # tiny splat inside block 0 only
-    mask, truth = hc.block_masks(rec, 0.0, 0.0)
-    assert list(mask) == [0, 255, 255, 255, 0, 1] and int(truth[5]) == 1 and int(truth[0]) == 0 and int(truth[4]) == 0
+    mask, truth = hc.block_masks(EDGE_RECORDS, 0.0, 0.0)
+    assert list(mask) == EDGE_MASKS and int(truth[5]) == 1 and int(truth[0]) == 0 and int(truth[4]) == 0
 
 
-@pytest.mark.parametrize("sig_lo,sig_hi,aspect_hi", [(0.5, 8.0, 6.0), (3.0, 40.0, 30.0)])
-def test_block_masks_as_the_emission_asks(sig_lo, sig_hi, aspect_hi):
-    """One set-up per splat for its whole 3x4-tile rectangle (slack from the rectangle's extent), slab extents shared by the tiles
-    of a tile row -- the call pattern of emit_instances_kernel<true>."""
+EMISSION_SETS = [(0.5, 8.0, 6.0), (3.0, 40.0, 30.0)]   # sig_lo, sig_hi, aspect_hi
+EMISSION_RECT = (50, 20, 53, 24)
+
+
+def _emission_set(sig_lo, sig_hi, aspect_hi, n=15000):
     rng = np.random.default_rng(7)
-    n = 15000
     cx, cy, cz = _conics(n, rng, sig_lo, sig_hi, aspect_hi, 0.3)
-    tx0, ty0, tx1, ty1 = 50, 20, 53, 24
+    tx0, ty0, tx1, ty1 = EMISSION_RECT
     mx = rng.uniform(tx0 * 16 - 20, tx1 * 16 + 20, n).astype(np.float32)
     my = rng.uniform(ty0 * 16 - 20, ty1 * 16 + 20, n).astype(np.float32)
     op = np.exp(rng.uniform(np.log(1.0 / 300.0), 0.0, n)).astype(np.float32)
+    return mx, my, cx, cy, cz, op
+
+
+@pytest.mark.parametrize("sig_lo,sig_hi,aspect_hi", EMISSION_SETS)
+def test_block_masks_as_the_emission_asks(sig_lo, sig_hi, aspect_hi):
+    """One set-up per splat for its whole 3x4-tile rectangle (slack from the rectangle's extent), slab extents shared by the tiles
+    of a tile row -- the call pattern of emit_instances_kernel<true>."""
+    mx, my, cx, cy, cz, op = _emission_set(sig_lo, sig_hi, aspect_hi)
+    tx0, ty0, tx1, ty1 = EMISSION_RECT
     mask, truth = hc.block_masks_rect(np.stack([mx, my, cx, cy, cz, op], 1), tx0, ty0, tx1, ty1)
     assert not (truth & ~mask).any()
     kept = int(np.unpackbits(mask.astype(np.uint8)).sum()), int(np.unpackbits(truth.astype(np.uint8)).sum())
