@@ -47,6 +47,7 @@ extern "C" {
 #define RADEGS_ERR_NO_DEVICE (-4)
 #define RADEGS_ERR_STATE (-5)   /* an earlier radegs_backward on this thread and device was handed an image buffer that does not hold what
                                    its forward wrote (reused or overwritten state): that call's gradients are invalid */
+#define RADEGS_ERR_TOO_LARGE (-6)   /* radegs_tetmesh_*: a size beyond what the 32-bit sort / scan primitives address */
 
 /* Allocator callback: return a DEVICE pointer to at least `nbytes` bytes (256-B aligned), or
  * NULL on failure.  Mirrors the resize lambdas of DGR/rasterize_points.cu:27-33. */
@@ -423,6 +424,63 @@ int radegs_densify_plan(int P, const float* accum, const float* accum_abs, const
                         void* stream);
 int radegs_densify_apply(int P, int P_out, int rest_floats, const RadegsDensifyTensors* tensors, const float* unit_normals /* [P,3,3] */,
                          const void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Mesh extraction: the steps of mesh_extract_tetrahedra.py around radegs_integrate.  All pointers:
+ * device; float32 unless typed otherwise.  Every call returns 0 or a negative RADEGS_ERR_*, enqueues on `stream` (a
+ * hipStream_t, NULL = the default stream) and neither synchronises nor reads anything back.  Sizes of 0 are legal and
+ * launch nothing.
+ *
+ * Marching tetrahedra (utils/tetmesh.py:97-138, one chunk) is plan + emit around the one host read it needs:
+ *   radegs_tetmesh_plan   occ = sdf > 0; a tet is crossing when 0 < sum(occ) < 4; a mesh vertex is one distinct edge
+ *       (min, max) whose ends differ in occ, numbered in ascending lexicographic (min, max) order.  tets: [T,4] int32,
+ *       16-byte aligned, indices in [0, V) (a tet with an index outside is treated as not crossing).  counts2 (device):
+ *       {n_verts, n_faces}.  workspace: radegs_tetmesh_plan_bytes(V, T) bytes, 16-byte aligned, kept untouched until
+ *       emit has run; it is sized for the worst case of 4 crossing edges per tet (about 180 bytes per tet).
+ *       RADEGS_ERR_TOO_LARGE when 5 T >= 2^32 - 65 536: that bound keeps the crossing-edge instances (at most 4 T) and
+ *       the scanned flags inside what the 32-bit primitives address.  V is an int, so V < 2^31.
+ *   radegs_tetmesh_emit   n_verts / n_faces: counts2 as read back.  interp_v[v] = (min, max); end_points / end_sdf /
+ *       end_scales are vertices / sdf / scales gathered at interp_v (bit-exact copies).  faces: all one-triangle tets in
+ *       tet order, then all two-triangle tets in tet order, rows from upstream's 16 x 6 triangle table.
+ *       Deviation: above 32 Mi tets upstream works in chunks and its FACE order becomes chunk by chunk; this is always
+ *       the single-chunk order (same vertices, same order; same face set).
+ * radegs_tetra_points: GaussianModel.get_tetra_points (scene/gaussian_model.py:400-429).  scales3: the 3D-filtered
+ *   scales; rotation_raw: [P,4], normalised here; it, out_points and out_scale 16-byte aligned.  out_points: the eight corners of the +-3 sigma box
+ *   of Gaussian i at rows 8 i .. 8 i + 7 (binary counting, x most significant: (-,-,-), (-,-,+), ... (+,+,+)), the
+ *   centres at rows 8 P ..; out_scale: 3 * max(scales3) per row of out_points.
+ * radegs_cull_alpha_accumulate: one view of evaluage_cull_alpha (mesh_extract_tetrahedra.py:42-54).  point_coordinate
+ *   [PN,2] is pixel coordinates as radegs_integrate writes them and is NOT modified; mask [H,W] is sampled bilinearly
+ *   (align_corners = False, zero padding) after multiplication by gt_mask and masks_extra ([H,W] or NULL each); where the
+ *   sample is > 0.5: final_sdf = min(final_sdf, alpha_integrated), weight += 1.
+ * radegs_cull_alpha_finish: sdf_out = weight > 0 ? 0.5 - final_sdf : -100.
+ * radegs_tetmesh_bisect: one step of the binary search (mesh_extract_tetrahedra.py:93-102) in place; mid_sdf was
+ *   evaluated at (left + right) / 2; where mid_sdf and left_sdf have the same strict sign the left end moves, else
+ *   (mid_sdf == 0 included) the right end; mid_pts_out: (left + right) / 2 of the new bracket.
+ * radegs_tetmesh_filter_plan / _apply: keep vertex v when |l0 - r0| <= scale_l + scale_r on the INITIAL end points
+ *   [NV,2,3] and end scales [NV,2]; keep a face when all three of its vertices are kept; kept vertices stay in order and
+ *   faces are renumbered (trimesh's update_vertices followed by update_faces).  counts2 (device): {vertices kept,
+ *   faces kept}.  workspace: radegs_tetmesh_filter_plan_bytes(NV, NF), 16-byte aligned, untouched until apply has run.
+ *   points [NV,3]: the vertex positions to filter (the bisection's result).
+ * --------------------------------------------------------------------------------------------------------------- */
+size_t radegs_tetmesh_plan_bytes(int V, long long T);
+int radegs_tetmesh_plan(int V, long long T, const int* tets /* [T,4] */, const float* sdf /* [V] */, void* workspace, size_t workspace_bytes,
+                        long long* counts2, void* stream);
+int radegs_tetmesh_emit(int V, long long T, const int* tets, const float* sdf, const float* vertices /* [V,3] */, const float* scales /* [V] */,
+                        const void* workspace, long long n_verts, long long n_faces, float* end_points /* [NV,2,3] */, float* end_sdf /* [NV,2] */,
+                        float* end_scales /* [NV,2] */, long long* faces /* [NF,3] */, long long* interp_v /* [NV,2] */, void* stream);
+int radegs_tetra_points(int P, const float* xyz, const float* scales3, const float* rotation_raw, float* out_points /* [9P,3] */,
+                        float* out_scale /* [9P] */, void* stream);
+int radegs_cull_alpha_accumulate(long long PN, const float* alpha_integrated, const float* point_coordinate, const float* mask,
+                                 const float* gt_mask, const float* masks_extra, int W, int H, float* final_sdf, int* weight, void* stream);
+int radegs_cull_alpha_finish(long long PN, const float* final_sdf, const int* weight, float* sdf_out, void* stream);
+int radegs_tetmesh_bisect(long long N, float* left_pts, float* right_pts, float* left_sdf, float* right_sdf, const float* mid_sdf,
+                          float* mid_pts_out, void* stream);
+size_t radegs_tetmesh_filter_plan_bytes(long long NV, long long NF);
+int radegs_tetmesh_filter_plan(long long NV, long long NF, const float* end_points, const float* end_scales, const long long* faces,
+                               void* workspace, size_t workspace_bytes, long long* counts2, void* stream);
+int radegs_tetmesh_filter_apply(long long NV, long long NF, const float* points, const long long* faces, const void* workspace,
+                                long long nv_out, long long nf_out, float* out_vertices /* [nv_out,3] */, long long* out_faces /* [nf_out,3] */,
+                                void* stream);
 
 #ifdef __cplusplus
 }

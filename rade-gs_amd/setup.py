@@ -5,7 +5,7 @@
 
 Installs the package the reference's callers import (`diff_gaussian_rasterization`: GaussianRasterizationSettings, GaussianRasterizer),
 `simple_knn` (distCUDA2) and the fused steps either side of the rasterizer (graphics_utils, loss_utils, gaussian_model_ops, fused_adam,
-view_parallel).  The native library is built by build.py, the same recipe `__graft_entry__.build()` runs; there is no CPU fallback."""
+view_parallel, tetmesh).  The native library is built by build.py, the same recipe `__graft_entry__.build()` runs; there is no CPU fallback."""
 import importlib.util
 import os
 
@@ -43,7 +43,7 @@ setup(
     version="0.6.0",
     description="MI355X-native differentiable Gaussian-splat rasterizer behind RaDe-GS's diff_gaussian_rasterization API (HIP, gfx950)",
     packages=["diff_gaussian_rasterization", "simple_knn"],
-    py_modules=["graphics_utils", "loss_utils", "gaussian_model_ops", "fused_adam", "view_parallel", "synth_scene"],
+    py_modules=["graphics_utils", "loss_utils", "gaussian_model_ops", "fused_adam", "view_parallel", "synth_scene", "tetmesh"],
     package_data={"diff_gaussian_rasterization": ["libradegs_hip.so", "_C_torch*.so"]},
     include_package_data=True,
     python_requires=">=3.8",
