@@ -482,6 +482,70 @@ int radegs_tetmesh_filter_apply(long long NV, long long NF, const float* points,
                                 long long nv_out, long long nf_out, float* out_vertices /* [nv_out,3] */, long long* out_faces /* [nf_out,3] */,
                                 void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Mesh evaluation: evaluate_dtu_mesh.py's cull and dtu_eval/eval.py's Chamfer distance.  The same
+ * conventions as above: device pointers unless marked (host), 0 or a negative RADEGS_ERR_*, work enqueued on `stream`,
+ * nothing read back, sizes of 0 legal.  eval.py's geometry is fp64 here as there; the cull is fp32 as upstream's.
+ *
+ * radegs_mesheval_sample_count / _emit (eval.py:50-71): per triangle v1, v2, l1, l2, area2 = |v1 x v2|; dropped unless
+ *   area2 > 0; thr = density sqrt(l1 l2 / area2), n = floor(l / thr); samples at k = ((i + .5) / n1, (j + .5) / n2),
+ *   i <= n1, j <= n2, k0 + k1 < 1 evaluated as two fp64 divisions and one addition; q = (v1 k0 + v2 k1) + p0; order:
+ *   triangles in input order, i major, j minor.  counts [F]; totals2 (device): {number of samples as 64 bits, number of
+ *   triangles whose n exceeds 30 000 (their count is 0: refuse the mesh)}.  workspace: radegs_mesheval_sample_bytes(F),
+ *   16-byte aligned, untouched until emit has run.  M: totals2[0] as read back; out [M,3].  A face with an index
+ *   outside [0, V) yields no samples.
+ * radegs_mesheval_grid_build: the uniform grid over `points` [N,3]: cell = floor((p - origin) / cell) wrapped into a
+ *   32-bit key (11, 11, 10 bits for x, y, z), the cloud sorted by key (stable) and gathered.  origin3 (host).  The
+ *   workspace (radegs_mesheval_grid_bytes(N), 16-byte aligned) IS the grid: hand it, with the same N, origin3 and
+ *   cell, to the two consumers below.  Cells one key period apart alias; every candidate is decided by its distance.
+ * radegs_mesheval_thin_rounds (eval.py:86-94): `rounds` rounds of the thinning over a grid with cell >= radius.  state
+ *   [N] by point index: 0 undecided, 1 kept, 2 removed; start from zeros and *undecided = N.  A round removes an
+ *   undecided point when a lower-index point within d^2 <= radius^2 is kept and keeps it when all of those are
+ *   removed (d^2 = (dx^2 + dy^2) + dz^2).  Call until *undecided reads 0: state == 1 is then the mask eval.py's loop
+ *   leaves.  No bound on the number of rounds is implied: a chain of N points needs N.
+ * radegs_mesheval_nearest (eval.py:119-134): per query the distance and index of the nearest grid point if the distance
+ *   is < max_dist, else inf and -1; equal distances: the lower index.  ceil(max_dist / cell) must not exceed 511.
+ * radegs_mesheval_sum_below: out2 = {sum of dist < max_dist, their number}, in a fixed order (repeatable bit for bit).
+ * radegs_mesheval_obs_mask (eval.py:102-110): box10 (host) = lo[3], hi[3] (inbound: lo <= p < hi), BB0[3], Res; dims3
+ *   (host): the volume's shape; volume: uint8 [d0,d1,d2] row-major.  g = rint((p - BB0) / Res), half to even.  Three
+ *   masks of length N: inbound; inbound & g inside the volume; that & volume[g] != 0.
+ * radegs_mesheval_above_plane (eval.py:128-130): ((P0 x + P1 y) + P2 z) + P3 > 0; plane4 (host).
+ * radegs_mesheval_dilate: binary dilation of mask != 0 [H,W] by the disk x^2 + y^2 <= radius^2, zero outside.
+ * radegs_mesheval_cull_vertices (evaluate_dtu_mesh.py:111-133): flags[v] = 1 iff for every camera the vertex projects
+ *   outside (-1, 1) or onto a set pixel of that camera's mask (nearest, align_corners = True, half to even).
+ *   RadegsCullCamera.m: rows 0-2 of K w2c; masks: all cameras' uint8 masks in one buffer, mask_offset into it.
+ * radegs_tetmesh_filter_plan_flags: radegs_tetmesh_filter_plan on ready vertex flags (0 / 1) instead of end points;
+ *   radegs_tetmesh_filter_apply follows it the same way.
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct RadegsCullCamera {
+  float m[12];
+  int W, H;
+  long long mask_offset;
+} RadegsCullCamera;
+
+size_t radegs_mesheval_sample_bytes(long long F);
+int radegs_mesheval_sample_count(long long V, long long F, const double* vertices /* [V,3] */, const long long* faces /* [F,3] */, double density,
+                                 void* workspace, size_t workspace_bytes, int* counts /* [F] */, unsigned long long* totals2, void* stream);
+int radegs_mesheval_sample_emit(long long V, long long F, const double* vertices, const long long* faces, double density, const void* workspace,
+                                long long M, double* out /* [M,3] */, void* stream);
+size_t radegs_mesheval_grid_bytes(long long N);
+int radegs_mesheval_grid_build(long long N, const double* points /* [N,3] */, const double* origin3, double cell, void* workspace,
+                               size_t workspace_bytes, void* stream);
+int radegs_mesheval_thin_rounds(long long N, const void* grid_workspace, const double* origin3, double cell, double radius, int rounds,
+                                unsigned char* state /* [N] */, unsigned* undecided, void* stream);
+int radegs_mesheval_nearest(long long N, const void* grid_workspace, const double* origin3, double cell, long long Q,
+                            const double* queries /* [Q,3] */, double max_dist, double* dist /* [Q] */, long long* index /* [Q] */, void* stream);
+size_t radegs_mesheval_sum_bytes(void);
+int radegs_mesheval_sum_below(long long Q, const double* dist, double max_dist, void* workspace, size_t workspace_bytes, double* out2, void* stream);
+int radegs_mesheval_obs_mask(long long N, const double* points, const double* box10, const int* dims3, const unsigned char* volume,
+                             unsigned char* inbound, unsigned char* grid_inbound, unsigned char* in_obs, void* stream);
+int radegs_mesheval_above_plane(long long N, const double* points, const double* plane4, unsigned char* above, void* stream);
+int radegs_mesheval_dilate(int W, int H, const unsigned char* mask, int radius, unsigned char* out, void* stream);
+int radegs_mesheval_cull_vertices(long long NV, const float* vertices /* [NV,3] */, int ncam, const RadegsCullCamera* cameras,
+                                  const unsigned char* masks, unsigned* flags /* [NV] */, void* stream);
+int radegs_tetmesh_filter_plan_flags(long long NV, long long NF, const unsigned* vertex_flags, const long long* faces, void* workspace,
+                                     size_t workspace_bytes, long long* counts2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

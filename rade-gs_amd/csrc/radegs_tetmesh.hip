@@ -484,6 +484,26 @@ int radegs_tetmesh_filter_plan(long long NV, long long NF, const float* end_poin
   return rgt::last();
 }
 
+int radegs_tetmesh_filter_plan_flags(long long NV, long long NF, const unsigned* vertex_flags, const long long* faces, void* workspace,
+                                     size_t workspace_bytes, long long* counts2, void* stream_v) {
+  if (NV < 0 || NF < 0 || !counts2) return RADEGS_ERR_INVALID_ARG;
+  if (!rgt::filter_sizes_ok(NV, NF)) return RADEGS_ERR_TOO_LARGE;
+  hipStream_t s = static_cast<hipStream_t>(stream_v);
+  if (NV == 0) return hipMemsetAsync(counts2, 0, 2 * sizeof(long long), s) == hipSuccess ? 0 : RADEGS_ERR_HIP;
+  if (!vertex_flags || (NF && !faces) || !workspace || workspace_bytes < radegs_tetmesh_filter_plan_bytes(NV, NF) ||
+      (reinterpret_cast<uintptr_t>(workspace) & 15))
+    return RADEGS_ERR_INVALID_ARG;
+  uint32_t *flags, *incl;
+  void* temp;
+  size_t temp_bytes;
+  rgt::filter_carve(NV, NF, workspace, &flags, &incl, &temp, &temp_bytes);
+  if (hipMemcpyAsync(flags, vertex_flags, (size_t)NV * sizeof(uint32_t), hipMemcpyDeviceToDevice, s) != hipSuccess) return RADEGS_ERR_HIP;
+  if (NF) hipLaunchKernelGGL(rgt::keep_face_kernel, dim3(rgt::blocks_of((size_t)NF)), dim3(256), 0, s, NV, NF, faces, flags);
+  if (rg::inclusive_scan_gather_u32(temp, temp_bytes, flags, nullptr, incl, (size_t)(NV + NF), s) != hipSuccess) return RADEGS_ERR_HIP;
+  hipLaunchKernelGGL(rgt::filter_counts_kernel, dim3(1), dim3(1), 0, s, NV, NF, incl, counts2);
+  return rgt::last();
+}
+
 int radegs_tetmesh_filter_apply(long long NV, long long NF, const float* points, const long long* faces, const void* workspace, long long nv_out,
                                 long long nf_out, float* out_vertices, long long* out_faces, void* stream) {
   if (NV < 0 || NF < 0 || nv_out < 0 || nf_out < 0 || nv_out > NV || nf_out > NF) return RADEGS_ERR_INVALID_ARG;

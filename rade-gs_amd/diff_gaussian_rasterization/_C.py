@@ -92,7 +92,12 @@ EXPORTED_SYMBOLS = ("radegs_forward", "radegs_backward", "radegs_backward_from_s
                     # mesh extraction (bound in tetmesh.py)
                     "radegs_tetmesh_plan_bytes", "radegs_tetmesh_plan", "radegs_tetmesh_emit", "radegs_tetra_points",
                     "radegs_cull_alpha_accumulate", "radegs_cull_alpha_finish", "radegs_tetmesh_bisect", "radegs_tetmesh_filter_plan_bytes",
-                    "radegs_tetmesh_filter_plan", "radegs_tetmesh_filter_apply")
+                    "radegs_tetmesh_filter_plan", "radegs_tetmesh_filter_apply",
+                    # mesh evaluation (bound in mesh_eval.py)
+                    "radegs_mesheval_sample_bytes", "radegs_mesheval_sample_count", "radegs_mesheval_sample_emit", "radegs_mesheval_grid_bytes",
+                    "radegs_mesheval_grid_build", "radegs_mesheval_thin_rounds", "radegs_mesheval_nearest", "radegs_mesheval_sum_bytes",
+                    "radegs_mesheval_sum_below", "radegs_mesheval_obs_mask", "radegs_mesheval_above_plane", "radegs_mesheval_dilate",
+                    "radegs_mesheval_cull_vertices", "radegs_tetmesh_filter_plan_flags")
 
 _lib = None
 # test hook: when True, the per-Gaussian accumulation scratch of the last backward is kept in LAST_ACC
