@@ -176,6 +176,26 @@ typedef struct RadegsBwdArgs {
 
 /* `accum_alloc` provides the per-Gaussian accumulation scratch (64 or 128 B per Gaussian). */
 int radegs_backward(const RadegsBwdArgs* args, radegs_alloc_fn accum_alloc, void* accum_user, void* stream);
+/* radegs_backward with a FIXED summation order: the same gradients up to fp32 rounding, and the same BITS on every run with the same inputs,
+ * the same build of this library and the same device model.  (radegs_backward adds each tile's wave totals to the Gaussian's record with
+ * atomics, in the order the scheduler happens to run the tiles.)  Here the tile-wide blend backward runs with one wave per tile and
+ * STORES every (tile, entry) total as the partial record of that entry's position r in the tile-ordered instance list; a stable sort of
+ * (point_list[r], r) then gives every Gaussian its positions in ascending r -- tile order, then depth order -- and one group of lanes per
+ * Gaussian adds its partial records in that order, sequentially, from 0.0f.  The order depends on the instance list alone.  The per-Gaussian
+ * half, keep_sums, drgb_ready and grad_chunks / grads_ready work as in radegs_backward; acc_reuse keeps its contract too (the scratch of
+ * `accum_alloc` comes back all zeros), though this call never needs the zeros: every record of it is written before it is read.
+ * Entry streams are never replayed (the tile-wide backward is valid after either forward).  Not promised: the bits of radegs_backward,
+ * or the same bits from another build.
+ * `scratch`: device memory of at least radegs_backward_ordered_scratch_bytes(P, R, require_coord) bytes, 256-byte aligned, contents
+ * irrelevant, free for reuse once `stream` has passed the call.  With r256(x) = x rounded up to a multiple of 256 and REC = 32 with
+ * require_coord, else 16, that is
+ *     r256(R * REC * 4)  +  2 * r256(R * 4)  +  r256(sort_temp(R))
+ * where sort_temp(R) = 2 * (4 R + 256) + 2048 * (ceil(R / 2048) + 1) + 3072 is the radix sort's temporary: the partial records
+ * dominate, 64 B per instance (128 B with the coord map), about 0.5 GB at 8 M instances.  A scratch that is NULL with R > 0, or too small,
+ * is refused with RADEGS_ERR_INVALID_ARG before anything is queued.  R == 0 needs no scratch. */
+size_t radegs_backward_ordered_scratch_bytes(int P, int R, int require_coord);
+int radegs_backward_ordered(const RadegsBwdArgs* args, radegs_alloc_fn accum_alloc, void* accum_user, void* scratch, size_t scratch_bytes,
+                            void* stream);
 /* The SECOND half of radegs_backward on caller-supplied per-Gaussian sums (inspection / parity hook, like radegs_debug_export): the
  * per-Gaussian backward (computeCov2DCUDA + preprocessCUDA backward, DGR/cuda_rasterizer/backward.cu:145-628) runs over `sums` instead
  * of over what the blend backward accumulated.  sums: device [P][16] floats ([P][32] with require_coord) in the order

@@ -126,9 +126,10 @@ static Switches switches() { std::lock_guard<std::mutex> l(g_sw_mu); return swit
 
 // ---- optional per-stage timing with HIP events on the launch stream (bench.py's roofline leg) ----
 enum Stage { ST_PRE_FWD = 0, ST_SORT_DEPTH, ST_SCAN, ST_EMIT, ST_SORT_TILE, ST_RANGES, ST_BLEND_FWD, ST_ACC_ZERO, ST_BLEND_BWD,
-             ST_PRE_BWD, ST_BLOCK_LISTS, ST_COUNT };
+             ST_PRE_BWD, ST_BLOCK_LISTS, ST_ORDERED_SORT, ST_ORDERED_SUMS, ST_COUNT };
 static const char* kStageNames[ST_COUNT] = {"preprocess_fwd", "sort_depth", "scan", "emit_instances", "sort_tile", "tile_ranges",
-                                            "blend_fwd", "acc_zero", "blend_bwd", "preprocess_bwd", "block_lists"};
+                                            "blend_fwd", "acc_zero", "blend_bwd", "preprocess_bwd", "block_lists", "ordered_sort",
+                                            "ordered_sums"};
 struct ProfRec { int stage; hipEvent_t a, b; };
 // atomics: autograd runs every device's backward on its own worker thread, and the switches are flipped from the main thread
 static std::atomic<bool> g_prof_on{false};
@@ -787,7 +788,30 @@ static int queue_preprocess_bwd(const RadegsBwdArgs* A, const GeomState& gs, con
   return 0;
 }
 
-int radegs_backward(const RadegsBwdArgs* A, radegs_alloc_fn accum_alloc, void* accum_user, void* stream_v) {
+// The scratch of radegs_backward_ordered, carved at 256-byte steps: one partial record per position of point_list, the positions sorted by
+// Gaussian (keys and positions), the sort's temporary.
+struct OrderedScratch {
+  float* part; uint32_t* keys; uint32_t* pos; void* sort_temp; size_t part_bytes, sort_bytes, total;
+  static OrderedScratch carve(void* base, size_t R, bool coord) {
+    OrderedScratch o;
+    char* p = static_cast<char*>(base);
+    size_t used = 0;
+    auto take = [&](size_t bytes) { char* r = p ? p + used : nullptr; used += (bytes + 255) & ~size_t(255); return r; };
+    o.part_bytes = R * (size_t)acc_record_floats(coord) * sizeof(float);
+    o.sort_bytes = sort_temp_bytes(R);
+    o.part = reinterpret_cast<float*>(take(o.part_bytes));
+    o.keys = reinterpret_cast<uint32_t*>(take(R * sizeof(uint32_t)));
+    o.pos = reinterpret_cast<uint32_t*>(take(R * sizeof(uint32_t)));
+    o.sort_temp = take(o.sort_bytes);
+    o.total = used;
+    return o;
+  }
+};
+
+// radegs_backward (ordered = false) and radegs_backward_ordered (ordered = true): they differ in how the blend backward's wave totals
+// reach the per-Gaussian records, nowhere else.
+static int backward_impl(const RadegsBwdArgs* A, radegs_alloc_fn accum_alloc, void* accum_user, bool ordered, void* scratch, size_t scratch_bytes,
+                         void* stream_v) {
   if (!A || !accum_alloc) return fail(RADEGS_ERR_INVALID_ARG, "null argument");
   if (A->struct_size != sizeof(RadegsBwdArgs)) return fail(RADEGS_ERR_INVALID_ARG, "RadegsBwdArgs.struct_size does not match this library's include/radegs.h");
   if (A->P == 0) return 0;
@@ -800,6 +824,12 @@ int radegs_backward(const RadegsBwdArgs* A, radegs_alloc_fn accum_alloc, void* a
   const bool dbg = A->debug != 0;
   const bool coord = A->require_coord != 0, depth = A->require_depth != 0;
   const int P = A->P, W = A->width, H = A->height, R = A->R;
+  OrderedScratch os{};
+  if (ordered && R > 0) {
+    if (!scratch) return fail(RADEGS_ERR_INVALID_ARG, "radegs_backward_ordered: scratch is NULL with R > 0");
+    os = OrderedScratch::carve(scratch, (size_t)R, coord);
+    if (scratch_bytes < os.total) return fail(RADEGS_ERR_INVALID_ARG, "radegs_backward_ordered: scratch smaller than radegs_backward_ordered_scratch_bytes(P, R, require_coord)");
+  }
   int devid = 0;
   (void)hipGetDevice(&devid);
   {
@@ -818,7 +848,10 @@ int radegs_backward(const RadegsBwdArgs* A, radegs_alloc_fn accum_alloc, void* a
   if (!acc) return fail(RADEGS_ERR_ALLOC, "accumulator allocation failed");
   int acc_raw = 0;
   const bool acc_reuse = A->acc_reuse != 0 && !A->keep_sums;   // the caller's scratch is zero and wants to stay so (include/radegs.h)
-  if (!acc_reuse) {
+  if (ordered && R > 0) {   // ordered_sums_kernel writes every record of acc; what needs zeros is the partial records the blend leaves out
+    StageTimer tm(ST_ACC_ZERO, stream);
+    RG_HIP(hipMemsetAsync(os.part, 0, os.part_bytes, stream));
+  } else if (!acc_reuse) {
     StageTimer tm(ST_ACC_ZERO, stream);
     RG_HIP(hipMemsetAsync(acc, 0, abytes, stream));
   }
@@ -833,7 +866,7 @@ int radegs_backward(const RadegsBwdArgs* A, radegs_alloc_fn accum_alloc, void* a
     ba.n_contrib = is.n_contrib; ba.accum_coord = is.accum_coord; ba.accum_depth = is.accum_depth; ba.normal_length = is.normal_length;
     ba.dL_dpix = A->dL_dpix; ba.dL_dcoord = A->dL_dpix_coord; ba.dL_dmcoord = A->dL_dpix_mcoord; ba.dL_ddepth = A->dL_dpix_depth;
     ba.dL_dmdepth = A->dL_dpix_mdepth; ba.dL_dalpha = A->dL_dalphas; ba.dL_dnormal = A->dL_dpix_normal;
-    ba.acc = acc; ba.P = P;
+    ba.acc = ordered ? os.part : acc; ba.P = P;
     ba.blk_base = is.blk_base; ba.blk_consumed = is.blk_consumed; ba.blk_chunks = is.blk_chunks; ba.blk_order = is.blk_order; ba.stream_tag = is.stream_tag;
     {
       PinnedCount& pin = pinned_for(devid);
@@ -850,7 +883,9 @@ int radegs_backward(const RadegsBwdArgs* A, radegs_alloc_fn accum_alloc, void* a
     // tile-wide backward -- valid after either forward -- takes over)
     constexpr uint64_t kStreamBwdMaxAccBytes = 0xFFFFFFFFull;
     const bool acc_fits = (uint64_t)A->P * (uint64_t)((coord ? 32 : 16) * sizeof(float)) <= kStreamBwdMaxAccBytes;
-    if (image_has_streams(A->image_buffer) && sw.streams_bwd && acc_fits) {
+    if (ordered) {   // the tile-wide backward, one wave per tile ("valid after either forward" below): one partial record per list position
+      dispatch(coord, depth, [&](auto c, auto d) { hipLaunchKernelGGL((blend_bwd_ordered_kernel<c, d>), dim3(ntiles), dim3(64), 0, stream, ba); });
+    } else if (image_has_streams(A->image_buffer) && sw.streams_bwd && acc_fits) {
       dispatch(coord, depth, [&](auto c, auto d) { hipLaunchKernelGGL((blend_bwd_streams_kernel<c, d>), dim3(ntiles * 2), dim3(64), 0, stream, ba); });
     } else {
       // one wave per 16x8 strip (2 pixels per lane); one wave per tile (4 per lane) once every entry covers the tile anyway: within 1 %
@@ -864,6 +899,19 @@ int radegs_backward(const RadegsBwdArgs* A, radegs_alloc_fn accum_alloc, void* a
     }
     RG_LAUNCH_CHECK("blend_bwd_kernel", dbg, stream);
   }
+  if (ordered && R > 0) {
+    {   // stable sort of (point_list[r], r): every Gaussian's positions end up consecutive and ascending
+      StageTimer tm(ST_ORDERED_SORT, stream);
+      int bits = 1;
+      while (bits < 32 && (1ull << bits) < (unsigned long long)P) bits++;
+      RG_HIP(radix_sort_pairs_u32(os.sort_temp, os.sort_bytes, bs.point_list, os.keys, nullptr, os.pos, (size_t)R, bits, stream));
+    }
+    StageTimer tm(ST_ORDERED_SUMS, stream);
+    const unsigned nb = (unsigned)(((size_t)P * rec + 255) / 256);
+    if (coord) hipLaunchKernelGGL((ordered_sums_kernel<32>), dim3(nb), dim3(256), 0, stream, P, (uint32_t)R, os.keys, os.pos, os.part, acc);
+    else hipLaunchKernelGGL((ordered_sums_kernel<16>), dim3(nb), dim3(256), 0, stream, P, (uint32_t)R, os.keys, os.pos, os.part, acc);
+    RG_LAUNCH_CHECK("ordered_sums_kernel", dbg, stream);
+  }
   bool drgb_done = false;
   if (A->dL_drgb_clamped && A->drgb_ready) {   // the rows the factored exchange all-gathers leave one kernel early (include/radegs.h)
     hipLaunchKernelGGL(drgb_clamped_kernel, dim3((P + 255) / 256), dim3(256), 0, stream, P, A->radii, gs.clamped, acc, rec, A->dL_drgb_clamped);
@@ -872,6 +920,19 @@ int radegs_backward(const RadegsBwdArgs* A, radegs_alloc_fn accum_alloc, void* a
     drgb_done = true;
   }
   return queue_preprocess_bwd(A, gs, cam, acc, rec, false, drgb_done, dbg, stream, true, acc_raw ? (A->keep_sums ? 2 : 1) : 0, acc_reuse);
+}
+
+int radegs_backward(const RadegsBwdArgs* A, radegs_alloc_fn accum_alloc, void* accum_user, void* stream_v) {
+  return backward_impl(A, accum_alloc, accum_user, false, nullptr, 0, stream_v);
+}
+
+size_t radegs_backward_ordered_scratch_bytes(int /*P*/, int R, int require_coord) {
+  return OrderedScratch::carve(nullptr, (size_t)(R > 0 ? R : 0), require_coord != 0).total;
+}
+
+int radegs_backward_ordered(const RadegsBwdArgs* A, radegs_alloc_fn accum_alloc, void* accum_user, void* scratch, size_t scratch_bytes,
+                            void* stream_v) {
+  return backward_impl(A, accum_alloc, accum_user, true, scratch, scratch_bytes, stream_v);
 }
 
 int radegs_backward_from_sums(const RadegsBwdArgs* A, const float* sums, void* stream_v) {

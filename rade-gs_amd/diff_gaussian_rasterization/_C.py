@@ -78,7 +78,7 @@ class RadegsIntegrateArgs(ctypes.Structure):
 
 
 # every symbol include/radegs.h declares
-EXPORTED_SYMBOLS = ("radegs_forward", "radegs_backward", "radegs_backward_from_sums", "radegs_mark_visible", "radegs_integrate", "radegs_sh_grad_from_views", "radegs_geometry_bytes", "radegs_image_bytes",
+EXPORTED_SYMBOLS = ("radegs_forward", "radegs_backward", "radegs_backward_ordered", "radegs_backward_ordered_scratch_bytes", "radegs_backward_from_sums", "radegs_mark_visible", "radegs_integrate", "radegs_sh_grad_from_views", "radegs_geometry_bytes", "radegs_image_bytes",
                     "radegs_binning_bytes", "radegs_debug_export", "radegs_forget_image", "radegs_last_error", "radegs_version", "radegs_profile_enable",
                     "radegs_profile_select", "radegs_profile_stride", "radegs_binning_stats", "radegs_reload_env", "radegs_last_forward_used_streams", "radegs_profile_num_stages", "radegs_profile_stage_name", "radegs_profile_collect",
                     # fused pre/post steps (bound in graphics_utils.py / gaussian_model_ops.py)
@@ -108,6 +108,12 @@ KEEP_ACC = False
 OPACITY_GRAD_INTENDED = os.environ.get("RADEGS_OPACITY_GRAD", "").lower() == "intended"
 LAST_ACC = None
 LAST_POINT_STATE = None
+# RADEGS_DETERMINISTIC=1 (read here and again by reload_env(), like the library's own RADEGS_* switches) or set_deterministic_backward(True):
+# rasterize_gaussians_backward calls radegs_backward_ordered -- per-Gaussian sums in a fixed order, bit-identical gradients run to run
+# (include/radegs.h).  torch.use_deterministic_algorithms is NOT consulted: following it would change what existing callers get.
+DETERMINISTIC = os.environ.get("RADEGS_DETERMINISTIC", "0") == "1"
+# with KEEP_ACC, after an ordered backward: (partial records as a float32 view [R, 16 | 32], R) -- one record per position of point_list
+LAST_PARTIALS = None
 # Optional allocator for the 8 gradient tensors of the backward: callable(name, shape, dtype, device) -> tensor
 # or None.  A data-parallel caller points it at slices of ONE flat bucket so that the gradient all-reduce needs no
 # gather copy (rade-gs_amd/view_parallel.GradBucket).  Default: plain torch.empty.
@@ -129,6 +135,15 @@ def set_grad_allocator(device, fn):
             _GRAD_ALLOCATORS.pop(idx, None)
         else:
             _GRAD_ALLOCATORS[idx] = fn
+
+
+def set_deterministic_backward(flag):
+    """Switch the fixed-order backward on or off for this process (see DETERMINISTIC); returns the previous value.  reload_env() sets it
+    from the environment again."""
+    global DETERMINISTIC
+    prev = DETERMINISTIC
+    DETERMINISTIC = bool(flag)
+    return prev
 
 
 def _grad_allocator_for(dev):
@@ -160,6 +175,11 @@ def library():
                                      ctypes.c_void_p, ctypes.c_void_p]
         L.radegs_backward.restype = ctypes.c_int
         L.radegs_backward.argtypes = [ctypes.POINTER(RadegsBwdArgs), _ALLOC_FN, ctypes.c_void_p, ctypes.c_void_p]
+        L.radegs_backward_ordered.restype = ctypes.c_int
+        L.radegs_backward_ordered.argtypes = [ctypes.POINTER(RadegsBwdArgs), _ALLOC_FN, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                              ctypes.c_void_p]
+        L.radegs_backward_ordered_scratch_bytes.restype = ctypes.c_size_t
+        L.radegs_backward_ordered_scratch_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
         L.radegs_backward_from_sums.restype = ctypes.c_int
         L.radegs_backward_from_sums.argtypes = [ctypes.POINTER(RadegsBwdArgs), ctypes.c_void_p, ctypes.c_void_p]
         L.radegs_integrate.restype = ctypes.c_int
@@ -324,6 +344,40 @@ def _acc_scratch(key, nbytes, device):
     return t
 
 
+_ORDERED_SCRATCH = {}   # (device index, stream handle) -> uint8 tensor of the ordered backward (partial records, sorted positions); only grows
+
+
+def _ordered_scratch(key, nbytes, device):
+    """The ordered backward's scratch of this (device, stream): contents irrelevant between calls, grown when a call needs more; at most 8."""
+    t = _ORDERED_SCRATCH.get(key)
+    if t is None or t.numel() < nbytes:
+        if t is None and len(_ORDERED_SCRATCH) >= 8:
+            _ORDERED_SCRATCH.clear()
+        del t
+        _ORDERED_SCRATCH.pop(key, None)    # let go of the smaller one before its replacement is allocated
+        t = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+        _ORDERED_SCRATCH[key] = t
+    return t
+
+
+def _backward_ordered(L, a, acc, P, R, require_coord, dev, akey):
+    """radegs_backward_ordered over the prepared arguments `a` and the accumulator holder `acc` (acc_reuse = 0: a fresh accumulator per call,
+    every record of it written by the call); returns rc."""
+    global LAST_PARTIALS
+    assert a.acc_reuse == 0
+    nbytes = int(L.radegs_backward_ordered_scratch_bytes(P, int(R), int(bool(require_coord))))
+    with _ACC_LOCK:    # one scratch per (device, stream): two host threads queueing on ONE stream must not interleave over it
+        scratch = _ordered_scratch(akey, nbytes, dev) if R > 0 else None
+        with torch.cuda.device(dev):
+            rc = L.radegs_backward_ordered(ctypes.byref(a), acc.cb, None, _ptr(scratch), nbytes if scratch is not None else 0, _stream(dev))
+        acc.release()
+        if KEEP_ACC and rc == 0 and acc.error is None:
+            rec = 32 if require_coord else 16
+            part = torch.empty((0, rec), dtype=torch.float32, device=dev) if scratch is None else scratch[:int(R) * rec * 4].view(torch.float32).view(int(R), rec).clone()
+            LAST_PARTIALS = (part, int(R))
+    return rc
+
+
 def _zero_maps(channels, H, W, device):
     """All-zero maps for the outputs a call does not produce (the reference returns torch.full(0) maps whatever the flags,
     rasterize_points.cu:71-77): FRESH memory every call, like the reference -- ONE zero-filled allocation (one ~6 us fill at 1080p
@@ -455,7 +509,8 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
         akey = (dev.index if dev.index is not None else torch.cuda.current_device(), int(torch.cuda.current_stream(dev).cuda_stream))
         # (above ACC_REUSE_MAX_BYTES the clearing stores cost the per-Gaussian kernel more than the fill they replace: C4, 5 M Gaussians with
         # the coord map = 640 MB, same-box A/B: preprocess_bwd +0.13 ms against a 0.08-ms fill)
-        acc_cached = None if (KEEP_ACC or _POISON or not ACC_REUSE or abytes > ACC_REUSE_MAX_BYTES) else _acc_scratch(akey, abytes, dev)
+        ordered = DETERMINISTIC     # read once: another thread may flip the switch while this call runs
+        acc_cached = None if (ordered or KEEP_ACC or _POISON or not ACC_REUSE or abytes > ACC_REUSE_MAX_BYTES) else _acc_scratch(akey, abytes, dev)
         acc = _Resizable(dev) if acc_cached is None else _Fixed(acc_cached)
         ready_cb, ready_err = None, []
         owner = getattr(grad_alloc, "__self__", None)
@@ -489,22 +544,25 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                           ctypes.cast(ready_cb, ctypes.c_void_p) if ready_cb is not None else None, None,
                           nchunks, ctypes.cast(chunks_cb, ctypes.c_void_p) if chunks_cb is not None else None, None,
                           int(bool(KEEP_ACC)), int(acc_cached is not None))
-        if acc_cached is not None:
-            _ACC_LOCK.acquire()
-        try:
-            with torch.cuda.device(dev):
-                rc = L.radegs_backward(ctypes.byref(a), acc.cb, None, _stream(dev))
-            acc.release()
-            if acc_cached is not None and (rc != 0 or acc.error is not None or ready_err):
-                _ACC_SCRATCH.pop(akey, None)   # the scratch is in an unknown state: the next call starts from a fresh one
-        finally:
+        if ordered:
+            rc = _backward_ordered(L, a, acc, P, R, require_coord, dev, akey)
+        else:
             if acc_cached is not None:
-                _ACC_LOCK.release()
+                _ACC_LOCK.acquire()
+            try:
+                with torch.cuda.device(dev):
+                    rc = L.radegs_backward(ctypes.byref(a), acc.cb, None, _stream(dev))
+                acc.release()
+                if acc_cached is not None and (rc != 0 or acc.error is not None or ready_err):
+                    _ACC_SCRATCH.pop(akey, None)   # the scratch is in an unknown state: the next call starts from a fresh one
+            finally:
+                if acc_cached is not None:
+                    _ACC_LOCK.release()
         if acc.error is not None:
             raise acc.error
         if ready_err:
             raise ready_err[0]
-        _check(rc, "radegs_backward")
+        _check(rc, "radegs_backward_ordered" if ordered else "radegs_backward")
         if KEEP_ACC:
             global LAST_ACC
             LAST_ACC = acc.tensor.view(torch.float32)
@@ -658,7 +716,10 @@ def binning_stats(reset=False):
 
 
 def reload_env():
-    """Have the library read its RADEGS_* environment switches again (it reads them once, at first use)."""
+    """Have the library read its RADEGS_* environment switches again (it reads them once, at first use); RADEGS_DETERMINISTIC, which this
+    module reads, with them."""
+    global DETERMINISTIC
+    DETERMINISTIC = os.environ.get("RADEGS_DETERMINISTIC", "0") == "1"
     library().radegs_reload_env()
 
 

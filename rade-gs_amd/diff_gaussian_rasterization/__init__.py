@@ -10,6 +10,7 @@ function :44-169); the native side is the hand-written HIP library behind `_C`
 (include/radegs.h).  Put `rade-gs_amd/` on PYTHONPATH (or `pip install -e rade-gs_amd`) and
 train.py / render.py run unchanged.
 """
+import contextlib
 from typing import NamedTuple
 
 import torch
@@ -24,7 +25,28 @@ if os.environ.get("RADEGS_BINDING", "ctypes") == "torch":
 else:
     from . import _C                 # the default: ctypes over the same C ABI (adds the view-parallel hooks and the test inspection calls)
 
-__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians"]
+__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "set_deterministic_backward",
+           "deterministic_backward"]
+
+
+def set_deterministic_backward(flag):
+    """True: the backward adds every Gaussian's per-tile sums in a fixed order (tile order, then depth order) instead of with atomics, so
+    the same inputs give the same BITS on every run -- same library build, same device model (RADEGS_DETERMINISTIC=1 in
+    the environment is the same switch).  Slower, and 64 B (128 B with the coord map) of scratch per rendered instance.  Returns the
+    previous value.  torch.use_deterministic_algorithms is not consulted.  ctypes binding only."""
+    if not hasattr(_C, "set_deterministic_backward"):
+        raise RuntimeError("the deterministic backward is not available through RADEGS_BINDING=torch")
+    return _C.set_deterministic_backward(flag)
+
+
+@contextlib.contextmanager
+def deterministic_backward(flag=True):
+    """with deterministic_backward(): ...  -- set_deterministic_backward(flag) for the block; the previous value comes back afterwards."""
+    prev = set_deterministic_backward(flag)
+    try:
+        yield
+    finally:
+        set_deterministic_backward(prev)
 
 
 class GaussianRasterizationSettings(NamedTuple):
