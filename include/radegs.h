@@ -205,7 +205,9 @@ int radegs_backward_ordered(const RadegsBwdArgs* args, radegs_alloc_fn accum_all
  * to the gradients is thereby taken out of a comparison: fed with the reference's own sums, every returned gradient must equal the
  * reference's (tests/test_gpu_vs_compiled_reference.py).  Of `args`, geom_buffer, radii, means3D, scales + rotations (or cov3D_precomp),
  * shs (when given), the three camera pointers and the gradient outputs are read -- all must be valid device pointers (NULL is refused);
- * `sums` must be 16-byte aligned (the records are read as 16-byte pieces).  Nothing is allocated. */
+ * `sums` must be 16-byte aligned (the records are read as 16-byte pieces).  Nothing is allocated.  dL_drgb_clamped, drgb_ready and
+ * grad_chunks / grads_ready work as in radegs_backward (so that tests reach those launch modes over known sums); keep_sums and
+ * acc_reuse are ignored: `sums` is only read. */
 int radegs_backward_from_sums(const RadegsBwdArgs* args, const float* sums, void* stream);
 
 /* dL_dsh[P,M,3] = scale * sum_v basis(normalize(means3D - campos[v])) (x) drgb_clamped[v]   (rows beyond (D+1)^2 zero).

@@ -951,7 +951,17 @@ int radegs_backward_from_sums(const RadegsBwdArgs* A, const float* sums, void* s
   const CamArgs cam = make_cam(A->viewmatrix, A->projmatrix, A->cam_pos, A->width, A->height, A->tan_fovx, A->tan_fovy, A->kernel_size,
                                A->scale_modifier);
   GeomState gs = GeomState::carve(A->geom_buffer, (size_t)A->P, coord, 0);
-  return queue_preprocess_bwd(A, gs, cam, sums, acc_record_floats(coord), true, false, A->debug != 0, stream);
+  const int rec = acc_record_floats(coord);
+  const bool dbg = A->debug != 0;
+  // the hand-off hooks of radegs_backward, over `sums` (tests reach the separate dL_drgb_clamped kernel and the chunked launches this way)
+  bool drgb_done = false;
+  if (A->dL_drgb_clamped && A->drgb_ready) {
+    hipLaunchKernelGGL(drgb_clamped_kernel, dim3((A->P + 255) / 256), dim3(256), 0, stream, A->P, A->radii, gs.clamped, sums, rec, A->dL_drgb_clamped);
+    RG_LAUNCH_CHECK("drgb_clamped_kernel", dbg, stream);
+    A->drgb_ready(A->drgb_ready_user);
+    drgb_done = true;
+  }
+  return queue_preprocess_bwd(A, gs, cam, sums, rec, true, drgb_done, dbg, stream, true);
 }
 
 int radegs_integrate(const RadegsIntegrateArgs* A, radegs_alloc_fn geom_alloc, void* geom_user, radegs_alloc_fn binning_alloc,

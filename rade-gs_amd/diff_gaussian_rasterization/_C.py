@@ -573,10 +573,17 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
 
 
 def backward_from_sums(sums, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx,
-                       tan_fovy, kernel_size, image_height, image_width, sh, degree, campos, geomBuffer, require_coord):
+                       tan_fovy, kernel_size, image_height, image_width, sh, degree, campos, geomBuffer, require_coord, *,
+                       grad_chunks=0, grads_ready=None, want_drgb=False, drgb_ready=None, keep_sums=False):
     """Test hook (radegs_backward_from_sums, include/radegs.h): the per-Gaussian half of the backward over caller-supplied per-Gaussian
     sums [P, 16 | 32] (the reference's render-kernel sums, its constant factors included).  Returns the 8-tuple of
-    rasterize_gaussians_backward."""
+    rasterize_gaussians_backward.
+
+    The keyword arguments reach the launch modes of RadegsBwdArgs: grad_chunks >= 2 with grads_ready = callable(first, count): that many
+    launches over consecutive ranges of Gaussians, the callable called on the host after each one; want_drgb: a NaN-filled (P,3)
+    dL_drgb_clamped is allocated and returned as a NINTH element; drgb_ready = callable(): dL_drgb_clamped is written by its own kernel
+    and the callable is called once that kernel is queued (implies want_drgb); keep_sums goes into the structure as it is (the library
+    only reads `sums`).  An exception raised by a callable is re-raised after the native call has returned."""
     _require_gpu(means3D, "means3D")
     L = library()
     dev = means3D.device
@@ -593,19 +600,42 @@ def backward_from_sums(sums, means3D, radii, colors, scales, rotations, scale_mo
     sc, rot, cov = _f32(scales, "scales"), _f32(rotations, "rotations"), _f32(cov3D_precomp, "cov3D_precomp")
     vm, pm, cp, shs = _f32(viewmatrix, "viewmatrix"), _f32(projmatrix, "projmatrix"), _f32(campos, "campos"), _f32(sh, "shs")
     rad, gb = radii.contiguous(), geomBuffer.contiguous()
+    want_drgb = bool(want_drgb) or drgb_ready is not None
+    drgb = torch.full((P, 3), float("nan"), **fo) if want_drgb else None
+    cb_err = []
+    ready_cb = chunks_cb = None
+    if drgb_ready is not None:
+        def _ready(_user):
+            try:
+                drgb_ready()
+            except Exception as ex:  # noqa: BLE001 -- must not unwind through the C frame
+                cb_err.append(ex)
+        ready_cb = _READY_FN(_ready)
+    if grads_ready is not None:
+        def _chunk(_user, first, count):
+            try:
+                grads_ready(int(first), int(count))
+            except Exception as ex:  # noqa: BLE001 -- must not unwind through the C frame
+                cb_err.append(ex)
+        chunks_cb = _GRADS_READY_FN(_chunk)
     a = RadegsBwdArgs(ctypes.sizeof(RadegsBwdArgs), P, int(degree), M, 0, int(image_width), int(image_height), None, _ptr(m3), _ptr(shs), _ptr(col), None, _ptr(sc), _ptr(rot),
                       _ptr(cov), _ptr(vm), _ptr(pm), _ptr(cp), float(scale_modifier), float(tan_fovx), float(tan_fovy), float(kernel_size),
                       _ptr(rad), None, _ptr(gb), None, None, None, None, None, None, None, None, None,
                       _ptr(dL_dmeans2D), _ptr(dL_dcolors), _ptr(dL_dopacity), _ptr(dL_dmeans3D), _ptr(dL_dcov3D),
-                      _ptr(dL_dsh) if M else None, _ptr(dL_dscales), _ptr(dL_drotations), int(bool(require_coord)), 0, 0, None,
-                      int(bool(OPACITY_GRAD_INTENDED)), None, None, 0, None, None, 0, 0)
+                      _ptr(dL_dsh) if M else None, _ptr(dL_dscales), _ptr(dL_drotations), int(bool(require_coord)), 0, 0, _ptr(drgb),
+                      int(bool(OPACITY_GRAD_INTENDED)), ctypes.cast(ready_cb, ctypes.c_void_p) if ready_cb is not None else None, None,
+                      int(grad_chunks), ctypes.cast(chunks_cb, ctypes.c_void_p) if chunks_cb is not None else None, None,
+                      int(bool(keep_sums)), 0)
     with torch.cuda.device(dev):
         rc = L.radegs_backward_from_sums(ctypes.byref(a), _ptr(sm), _stream(dev))
+    if cb_err:
+        raise cb_err[0]
     _check(rc, "radegs_backward_from_sums")
     if sc is None:
         dL_dscales.zero_()
         dL_drotations.zero_()
-    return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, (dL_dsh if M else None), dL_dscales, dL_drotations
+    out = (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, (dL_dsh if M else None), dL_dscales, dL_drotations)
+    return out + (drgb,) if want_drgb else out
 
 
 def sh_grad_from_views(means3D, campos_all, drgb_all, degree, M, scale=1.0, out=None):

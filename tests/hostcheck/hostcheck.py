@@ -46,7 +46,7 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
-def preprocess_fwd(scene, colors=None, cov3D=None, use_sh=True):
+def preprocess_fwd(scene, colors=None, cov3D=None, use_sh=True, scale_modifier=1.0):
     s = scene
     P = s.means3D.shape[0]
     means, scales, rots, opac = _f(s.means3D), _f(s.scales), _f(s.rotations), _f(s.opacities)
@@ -62,7 +62,7 @@ def preprocess_fwd(scene, colors=None, cov3D=None, use_sh=True):
     L.hc_preprocess_fwd(ctypes.c_int(P), ctypes.c_int(s.sh_degree), ctypes.c_int(M), _p(means), _p(scales), _p(rots), _p(cov3D),
                         _p(opac), _p(shs), _p(colors), _p(_f(s.viewmatrix)), _p(_f(s.projmatrix)), _p(_f(s.campos)),
                         ctypes.c_int(s.W), ctypes.c_int(s.H), ctypes.c_float(s.tanfovx), ctypes.c_float(s.tanfovy),
-                        ctypes.c_float(s.kernel_size), ctypes.c_float(1.0), _p(out_f), _p(out_i))
+                        ctypes.c_float(s.kernel_size), ctypes.c_float(scale_modifier), _p(out_f), _p(out_i))
     return out_f, out_i
 
 
@@ -79,7 +79,7 @@ def preprocess_inte(scene):
     return out_f, out_i
 
 
-def preprocess_bwd(scene, radii, clamped, op_combined, acc, use_sh=True, cov3D=None):
+def preprocess_bwd(scene, radii, clamped, op_combined, acc, use_sh=True, cov3D=None, scale_modifier=1.0):
     s = scene
     P = s.means3D.shape[0]
     means, scales, rots = _f(s.means3D), _f(s.scales), _f(s.rotations)
@@ -96,7 +96,7 @@ def preprocess_bwd(scene, radii, clamped, op_combined, acc, use_sh=True, cov3D=N
     L.hc_preprocess_bwd(ctypes.c_int(P), ctypes.c_int(s.sh_degree), ctypes.c_int(M), _p(means), _p(scales), _p(rots), _p(cov3D),
                         _p(shs), _p(radii), _p(clamped), _p(_f(op_combined)), _p(_f(s.viewmatrix)), _p(_f(s.projmatrix)),
                         _p(_f(s.campos)), ctypes.c_int(s.W), ctypes.c_int(s.H), ctypes.c_float(s.tanfovx),
-                        ctypes.c_float(s.tanfovy), ctypes.c_float(s.kernel_size), ctypes.c_float(1.0), _p(_f(acc)), _p(out),
+                        ctypes.c_float(s.tanfovy), ctypes.c_float(s.kernel_size), ctypes.c_float(scale_modifier), _p(_f(acc)), _p(out),
                         _p(dsh) if shs is not None else None)
     return out, dsh
 
