@@ -568,6 +568,42 @@ int radegs_mesheval_cull_vertices(long long NV, const float* vertices /* [NV,3] 
 int radegs_tetmesh_filter_plan_flags(long long NV, long long NF, const unsigned* vertex_flags, const long long* faces, void* workspace,
                                      size_t workspace_bytes, long long* counts2, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Decoupled appearance loss: train.py:37-58 L1_loss_appearance over scene/appearance_network.py.
+ * The trunk (conv1 and the four pixel-shuffle blocks, at most half resolution) stays with the caller; these entry
+ * points are everything at full resolution.  Conventions as above: device pointers, float32, 0 or a negative
+ * RADEGS_ERR_*, work enqueued on `stream`, nothing read back; every argument is checked before anything is queued.
+ *
+ * Crop: H = orig_height / 32 * 32, W likewise, top = orig_height / 2 - H / 2, left likewise; orig_height and
+ * orig_width in [32, 32768].  image / gt: [3,orig_height,orig_width].
+ *
+ * radegs_appearance_downsample_forward: down [3,H/32,W/32] = bilinear resize of the crop, align_corners=True, with
+ *   torch's index arithmetic (source coordinate = dst * (in-1)/(out-1) in fp32, scale 0 when out == 1).
+ * radegs_appearance_downsample_backward: grad_image [3,orig_height,orig_width], written completely (zero where no
+ *   output reads).
+ * radegs_appearance_head_forward: feat [16,H/2,W/2] (feat_height / feat_width must be exactly H/2, W/2);
+ *   W2 [16,16,3,3], b2 [16], W3 [3,16,3,3], b3 [3].  loss[0] = mean |sigmoid(conv3(relu(conv2(bilinear x2 (feat)))))
+ *   * crop(image) - crop(gt)|, both convolutions zero-padded at the crop border.  `transformed` (optional,
+ *   [3,H,W]) receives the product before the difference: the inference branch.  Writes nothing else of full
+ *   resolution.  scratch: radegs_appearance_head_scratch_bytes(.., 0) bytes, 16-byte aligned.
+ * radegs_appearance_head_backward: grad_loss: one device float.  Writes grad_feat [16,H/2,W/2], grad_image
+ *   [3,orig_height,orig_width] (completely: zero outside the crop; the path through `down` is not included),
+ *   grad_W2, grad_b2, grad_W3, grad_b3.  scratch: radegs_appearance_head_scratch_bytes(.., 1) bytes; it holds the
+ *   one full-resolution intermediate, the gradient at conv2's pre-activation [16,H,W].
+ * No float atomics: two calls on the same inputs return the same bits.  The scratch query returns 0 for a size
+ * the calls would refuse.
+ * --------------------------------------------------------------------------------------------------------------- */
+int radegs_appearance_downsample_forward(int orig_height, int orig_width, const float* image, float* down, void* stream);
+int radegs_appearance_downsample_backward(int orig_height, int orig_width, const float* grad_down, float* grad_image, void* stream);
+size_t radegs_appearance_head_scratch_bytes(int orig_height, int orig_width, int backward);
+int radegs_appearance_head_forward(int orig_height, int orig_width, int feat_height, int feat_width, const float* feat, const float* image, const float* gt,
+                                   const float* W2, const float* b2, const float* W3, const float* b3, void* scratch, size_t scratch_bytes,
+                                   float* loss, float* transformed, void* stream);
+int radegs_appearance_head_backward(int orig_height, int orig_width, int feat_height, int feat_width, const float* feat, const float* image, const float* gt,
+                                    const float* W2, const float* b2, const float* W3, const float* b3, const float* grad_loss, void* scratch,
+                                    size_t scratch_bytes, float* grad_feat, float* grad_image, float* grad_W2, float* grad_b2, float* grad_W3,
+                                    float* grad_b3, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -48,10 +48,11 @@ UNITS = {
     "radegs_knn": ["radegs_knn.hip", "rg_prims.h", os.path.join("..", "..", "include", "radegs.h")],
     "radegs_tetmesh": ["radegs_tetmesh.hip", "rg_prims.h", os.path.join("..", "..", "include", "radegs.h")],
     "radegs_mesheval": ["radegs_mesheval.hip", "rg_prims.h", os.path.join("..", "..", "include", "radegs.h")],
+    "radegs_appearance": ["radegs_appearance.hip", os.path.join("..", "..", "include", "radegs.h")],
 }
 # Units outside the rasterizer's decision chain have no bit-exactness contract with the oracle: let them contract to fma.
 UNIT_FLAGS = {"radegs_normals": ["-ffp-contract=fast"], "radegs_filter3d": ["-ffp-contract=fast"],
-              "radegs_photometric": ["-ffp-contract=fast"]}
+              "radegs_photometric": ["-ffp-contract=fast"], "radegs_appearance": ["-ffp-contract=fast"]}
 
 
 def _stale(target, deps):

@@ -89,6 +89,9 @@ EXPORTED_SYMBOLS = ("radegs_forward", "radegs_backward", "radegs_backward_ordere
                     "radegs_photometric_forward", "radegs_photometric_backward", "radegs_adam_step", "radegs_knn_scratch_bytes",
                     "radegs_knn_mean_dist2", "radegs_densify_stats", "radegs_densify_stats_reduced", "radegs_densify_plan_bytes",
                     "radegs_densify_plan", "radegs_densify_apply",
+                    # decoupled appearance loss (bound in loss_utils.py)
+                    "radegs_appearance_downsample_forward", "radegs_appearance_downsample_backward", "radegs_appearance_head_scratch_bytes",
+                    "radegs_appearance_head_forward", "radegs_appearance_head_backward",
                     # mesh extraction (bound in tetmesh.py)
                     "radegs_tetmesh_plan_bytes", "radegs_tetmesh_plan", "radegs_tetmesh_emit", "radegs_tetra_points",
                     "radegs_cull_alpha_accumulate", "radegs_cull_alpha_finish", "radegs_tetmesh_bisect", "radegs_tetmesh_filter_plan_bytes",

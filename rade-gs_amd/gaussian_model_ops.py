@@ -298,10 +298,14 @@ def densify_and_prune(model, max_grad, min_opacity, extent, max_screen_size, uni
     return cloned, split, pruned
 
 
-def patch_gaussian_model(cls):
+def patch_gaussian_model(cls, appearance_network=False):
     """Installs the two functions above on the reference's GaussianModel class under upstream's method names and signatures, so that
     train.py's `gaussians.add_densification_stats(viewspace_point_tensor, visibility_filter)` and
-    `gaussians.densify_and_prune(max_grad, min_opacity, extent, size_threshold)` run on the HIP kernels.  Returns `cls`."""
+    `gaussians.densify_and_prune(max_grad, min_opacity, extent, size_threshold)` run on the HIP kernels.  Returns `cls`.
+
+    appearance_network=True also wraps `training_setup`: after upstream's own has built the optimizer,
+    `self.appearance_network` is replaced by appearance_network.AppearanceNetwork.adopt(...) of it -- the same Parameter objects, so the
+    optimizer group keeps pointing at live parameters."""
     def _add_densification_stats(self, viewspace_point_tensor, update_filter):
         return add_densification_stats(self, viewspace_point_tensor, update_filter)
 
@@ -310,4 +314,14 @@ def patch_gaussian_model(cls):
 
     cls.add_densification_stats = _add_densification_stats
     cls.densify_and_prune = _densify_and_prune
+    if appearance_network:
+        from appearance_network import AppearanceNetwork
+        upstream_setup = cls.training_setup
+
+        def _training_setup(self, *args, **kwargs):
+            out = upstream_setup(self, *args, **kwargs)
+            self.appearance_network = AppearanceNetwork.adopt(self.appearance_network)
+            return out
+
+        cls.training_setup = _training_setup
     return cls
