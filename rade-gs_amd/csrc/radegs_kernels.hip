@@ -336,378 +336,7 @@ __device__ __forceinline__ int xcd_band_remap(int b, int n) {
   return xcd * q + (xcd < r ? xcd : r) + loc;
 }
 
-// ============================================================================ integrate ==
-// GaussianRasterizer.integrate (GOF-style point integration used by mesh extraction): for every query point that
-// projects into the image, the opacity accumulated along its pixel's ray up to the point.
-//   preprocessPointsCUDA  DGR/cuda_rasterizer/forward.cu:855-900   -> points_preprocess_kernel
-//   createWithKeys + SortPairs + identifyTileRanges (rasterizer_impl.cu:114-145,784-806)
-//                                                                   -> per-PIXEL counting sort (count / scan / scatter)
-//   integrateCUDA         forward.cu:938-1372                       -> integrate_kernel
-// Re-design: the reference bins points per 16x16 tile and lets every pixel thread scan its tile's whole point list to
-// find its own points (two per-thread local arrays of 2048 + 5x256 entries).  A point belongs to exactly one pixel
-// (floor of its projection) and points do not interact, so they are binned per pixel here: each lane gets the [start,end)
-// range of its own points, the 2048-entry "contributed" list is replaced by replaying the 5-sample transmittance test
-// (identical arithmetic => identical decisions), and no per-thread scratch arrays exist at all.
-struct PointsPreArgs {
-  int PN; const float* points3D; const float* view; float focal_x, focal_y; int W, H;
-  float2* p2d; float* pdepth; uint32_t* ppix; uint32_t* pix_count;
-  float* out_alpha_integrated; float* out_color_integrated; float* out_coordinate2d; float* out_sdf;
-};
-
-// initial values of rasterize_points.cu:312-320
-__device__ __forceinline__ void point_outputs_init(const PointsPreArgs& a, int i) {
-  a.out_alpha_integrated[i] = 1.0f;
-  a.out_color_integrated[3 * (size_t)i] = 0.f; a.out_color_integrated[3 * (size_t)i + 1] = 0.f; a.out_color_integrated[3 * (size_t)i + 2] = 0.f;
-  a.out_coordinate2d[2 * (size_t)i] = 0.f; a.out_coordinate2d[2 * (size_t)i + 1] = 0.f;
-  a.out_sdf[i] = -1000.0f;
-}
-__global__ void __launch_bounds__(256) points_init_kernel(const PointsPreArgs a) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < a.PN) point_outputs_init(a, i);
-}
-
-__global__ void __launch_bounds__(256) points_preprocess_kernel(const PointsPreArgs a) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= a.PN) return;
-  point_outputs_init(a, i);
-  a.ppix[i] = 0xFFFFFFFFu;
-  const float* p = a.points3D + 3 * (size_t)i;
-  const v3 pv = xform43(mk3(p[0], p[1], p[2]), a.view);
-  if (pv.z <= 0.2f) return;
-  const float ix = (float)((double)(a.focal_x * pv.x / (pv.z + 0.0000001f)) + a.W / 2.);
-  const float iy = (float)((double)(a.focal_y * pv.y / (pv.z + 0.0000001f)) + a.H / 2.);
-  if (ix < 0 || ix >= a.W || iy < 0 || iy >= a.H) return;
-  a.pdepth[i] = sqrtf(pv.x * pv.x + pv.y * pv.y + pv.z * pv.z);
-  a.p2d[i] = make_float2(ix, iy);
-  const uint32_t pix = (uint32_t)f2i_sat(floorf(iy)) * (uint32_t)a.W + (uint32_t)f2i_sat(floorf(ix));
-  a.ppix[i] = pix;
-  atomicAdd(&a.pix_count[pix], 1u);
-}
-
-// slot = incl[pix] - (old remaining count): distinct slots inside the pixel's range, no second cursor array
-__global__ void __launch_bounds__(256) points_scatter_kernel(int PN, const uint32_t* ppix, uint32_t* pix_count, const uint32_t* pix_incl,
-                                                            uint32_t* pt_sorted) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= PN) return;
-  const uint32_t pix = ppix[i];
-  if (pix == 0xFFFFFFFFu) return;
-  const uint32_t rem = atomicSub(&pix_count[pix], 1u);
-  pt_sorted[pix_incl[pix] - rem] = (uint32_t)i;
-}
-
-struct IntegrateArgs {
-  const uint2* ranges; const uint32_t* point_list; const float4* splat_a; const float4* inte_rec;
-  int W, H, gx; const float* bg;
-  const uint32_t* pix_incl; const uint32_t* pt_sorted; const float2* p2d; const float* pdepth;
-  float* out9; float* final_T; uint32_t* n_contrib;
-  float* out_alpha_integrated; float* out_color_integrated; float* out_coordinate2d; float* out_sdf;
-};
-
-constexpr int kMaxContributors = 512 * 4;  // MAX_NUM_CONTRIBUTORS * 4, auxiliary.h:27 / forward.cu:1003
-constexpr int kPointsPerPass = 4;
-
-// The 5-sample (centre + 4 corners) transmittance test of forward.cu:1043-1110 for one list entry; updates cT and
-// reports which samples passed.  Returns true when any did ("used").
-struct FiveSample { float alpha0, depth0, depth_max; bool pass0; };
-__device__ __forceinline__ bool five_sample(const float4 A, const float4 B, float rpx, float rpy, float pixfx, float pixfy, float cT[5],
-                                            FiveSample& o) {
-  const float offx[5] = {0.0f, -0.5f, 0.5f, -0.5f, 0.5f}, offy[5] = {0.0f, -0.5f, -0.5f, 0.5f, 0.5f};
-  bool used = false;
-  o.pass0 = false;
-  o.depth_max = -INFINITY;
-#pragma unroll
-  for (int c = 0; c < 5; c++) {
-    const float dx = A.x - pixfx - offx[c], dy = A.y - pixfy - offy[c];
-    const float depth = B.w + (rpx * dx + rpy * dy);
-    const float power = -0.5f * (A.z * dx * dx + B.x * dy * dy) - A.w * dx * dy;
-    if (power > 0.0f || power < B.z) continue;  // B.z: conservative exponent threshold for alpha < 1/255
-    const float alpha = fminf(0.99f, B.y * exp_spec(power));
-    if (alpha < 1.0f / 255.0f) continue;
-    const float test_T = cT[c] * (1 - alpha);
-    if (test_T < 0.0001f) continue;
-    if (c == 0) { o.pass0 = true; o.alpha0 = alpha; o.depth0 = depth; }
-    o.depth_max = fmaxf(o.depth_max, depth);
-    cT[c] = test_T;
-    used = true;
-  }
-  return used;
-}
-
-// Phase 2 walks the tile list again for every batch of 4 query points of a pixel and needs, per (pixel, entry), only WHETHER the
-// 5-sample test of phase 1 let the entry through ("used": the reference keeps those ids in a 2048-entry per-thread array,
-// forward.cu:1003,1121).  Round 1 replayed the test -- five specified exponentials per pair and pass; since round 4 phase 1 leaves one
-// bit per (pixel, entry) in wave-private LDS (64 bits per lane and batch of 64 entries, 12 batches = 6 KB) and phase 2 reads it:
-// the same decisions by construction, no exponential at all in phase 2.  Tiles with more than 768 entries replay as before.
-constexpr int kUsedBatches = 12;   // 16: 5.26 ms on C2 with 4 M points, 12 / 10: 4.87 (LDS per wave decides the occupancy; + 3 KB of per-pixel staging for the point-major phase 2)
-
-__global__ void __launch_bounds__(64) integrate_kernel(const IntegrateArgs a) {
-  __shared__ float4 lds_a[64 * 4];
-  __shared__ float4 lds_i[64 * 2];
-  __shared__ unsigned long long lds_used[kUsedBatches * 64];
-  const int item = xcd_band_remap(blockIdx.x, gridDim.x);
-  const int tile = item >> 2, sub = item & 3;
-  const int tile_x = tile % a.gx, tile_y = tile / a.gx;
-  const int lane = threadIdx.x, lx = lane & 15, lr = lane >> 4;
-  const int px = tile_x * 16 + lx, py = tile_y * 16 + sub * 4 + lr;
-  const int W = a.W, H = a.H;
-  const size_t HW = (size_t)H * W;
-  const bool inside = px < W && py < H;
-  const size_t pix = (size_t)py * W + px;
-  const float pixfx = (float)px + 0.5f, pixfy = (float)py + 0.5f;
-  // sample positions of this wave's strip (pixel centres +- 0.5) for the batch cull
-  const float reg_x0 = (float)(tile_x * 16), reg_x1 = reg_x0 + 16.0f;
-  const float reg_y0 = (float)(tile_y * 16 + sub * 4), reg_y1 = reg_y0 + 4.0f;
-  const uint2 range = a.ranges[tile];
-  const int n = (int)(range.y - range.x);
-
-  // ---------------------------------------------------------------- phase 1: the image ----
-  float cT[5] = {1.f, 1.f, 1.f, 1.f, 1.f};  // cT[0] is the pixel's T
-  float C0 = 0.f, C1 = 0.f, C2 = 0.f, C3 = 0.f, C4 = 0.f, C6 = 0.f, C7 = 0.f;
-  float mid_dc = 0.f, mid_px = 0.f, mid_py = 0.f, mid_mx = 0.f, mid_my = 0.f;
-  uint32_t last_c = 0, n_local = 0;
-  bool done = !inside;
-  for (int base = 0; base < n; base += 64) {
-    if (__all(done)) break;
-    __syncthreads();
-    const int k = base + lane;
-    bool rel_lane = false;
-    if (k < n) {
-      const uint32_t g = a.point_list[range.x + k];
-      rel_lane = stage_record(a.splat_a, g, lds_a, lane, reg_x0, reg_x1, reg_y0, reg_y1);
-    }
-    uint64_t rel = __ballot(rel_lane);
-    __syncthreads();
-    unsigned long long used_bits = 0ull;
-    while (rel != 0) {
-      const int j = __builtin_ctzll(rel);
-      rel &= rel - 1;
-      if (done) continue;
-      const float4 A = lds_a[j * 4 + 0], B = lds_a[j * 4 + 1], Cc = lds_a[j * 4 + 2], D = lds_a[j * 4 + 3];
-      const float T = cT[0];
-      FiveSample f;
-      if (!five_sample(A, B, Cc.w, D.x, pixfx, pixfy, cT, f)) continue;
-      used_bits |= 1ull << j;
-      if (f.pass0) {
-        C0 += Cc.x * f.alpha0 * T; C1 += Cc.y * f.alpha0 * T; C2 += Cc.z * f.alpha0 * T;
-      }
-      if (f.depth_max > C6) C6 = f.depth_max;
-      if (f.pass0) {
-        C7 += f.alpha0 * T;
-        C3 += f.depth0 * f.alpha0 * T;
-        if (T > 0.5f) { C4 = f.depth0; mid_dc = B.w; mid_px = Cc.w; mid_py = D.x; mid_mx = A.x; mid_my = A.y; }
-      }
-      last_c = (uint32_t)(base + j + 1);
-      n_local += 1;
-      if (n_local >= (uint32_t)kMaxContributors) done = true;  // the reference stops this pixel here (forward.cu:1121-1125)
-    }
-    if ((base >> 6) < kUsedBatches) lds_used[(base >> 6) * 64 + lane] = used_bits;
-  }
-  const bool cached = n <= kUsedBatches * 64;   // wave-uniform: every batch of this tile has its bits (else phase 2 replays the test)
-  const float T = cT[0];
-  float col0 = 0.f, col1 = 0.f, col2 = 0.f;
-  if (inside) {
-    col0 = C0 + T * a.bg[0]; col1 = C1 + T * a.bg[1]; col2 = C2 + T * a.bg[2];
-    a.final_T[pix] = T;
-    a.n_contrib[pix] = last_c;
-    a.out9[0 * HW + pix] = col0; a.out9[1 * HW + pix] = col1; a.out9[2 * HW + pix] = col2;
-    a.out9[3 * HW + pix] = C3; a.out9[4 * HW + pix] = C4; a.out9[6 * HW + pix] = C6; a.out9[7 * HW + pix] = C7;
-  }
-
-  // --------------------------------------------------- phase 2: this pixel's query points ----
-  uint32_t cur = 0, pe = 0;
-  if (inside) {
-    cur = pix == 0 ? 0u : a.pix_incl[pix - 1];
-    pe = a.pix_incl[pix];
-    a.out9[8 * HW + pix] = (float)(pe - cur);
-  }
-  if (cached) {
-    // ---- point-major phase 2 (round 4): one query point per LANE.  The per-pixel form below gives every pixel-lane four point slots
-    // per walk of the list; a pixel holds 1.6 points on average (C2, 4 M points) and an entry is used by a quarter of a strip's pixels,
-    // so ~one lane-slot in ten does work.  Here the strip's points (sorted by pixel: four runs of pt_sorted) are dealt to the lanes 64 at
-    // a time; a point-lane reads ITS pixel's used bits and per-pixel results from LDS and carries one point through the walk.
-    __shared__ float lds_pix[64 * 8];      // per pixel of the strip: colour (3), median plane (depth, px, py, mx, my)
-    __shared__ uint32_t lds_off[64 + 1];   // exclusive scan of the pixels' point counts
-    __shared__ uint32_t lds_first[64];     // first index of the pixel's points in pt_sorted
-    __shared__ uint32_t lds_last[64];      // the pixel's last contributor (bound of its walk)
-    const uint32_t cnt = pe - cur;
-    uint32_t incl = cnt;                   // inclusive wave scan of the counts
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t y = (uint32_t)__shfl_up((int)incl, d);
-      if (lane >= d) incl += y;
-    }
-    const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-    __syncthreads();
-    lds_off[lane] = incl - cnt;
-    if (lane == 63) lds_off[64] = total;
-    lds_first[lane] = cur;
-    lds_last[lane] = last_c;
-    lds_pix[lane * 8 + 0] = col0; lds_pix[lane * 8 + 1] = col1; lds_pix[lane * 8 + 2] = col2;
-    lds_pix[lane * 8 + 3] = mid_dc; lds_pix[lane * 8 + 4] = mid_px; lds_pix[lane * 8 + 5] = mid_py;
-    lds_pix[lane * 8 + 6] = mid_mx; lds_pix[lane * 8 + 7] = mid_my;
-    __syncthreads();
-    for (uint32_t r0 = 0; r0 < total; r0 += 64) {
-      const uint32_t q = r0 + (uint32_t)lane;
-      const bool have = q < total;
-      // the pixel this point belongs to: the last p with off[p] <= q (binary search over the 64 offsets)
-      int p = 0;
-      if (have) {
-#pragma unroll
-        for (int step = 32; step > 0; step >>= 1)
-          if (lds_off[p + step] <= q) p += step;
-      }
-      uint32_t pid1 = 0;
-      float qx1 = 0.f, qy1 = 0.f, qd1 = 0.f, pa1 = 0.f, pT1 = 1.f;
-      if (have) {
-        pid1 = a.pt_sorted[lds_first[p] + (q - lds_off[p])];
-        const float2 qq = a.p2d[pid1];
-        qx1 = qq.x; qy1 = qq.y; qd1 = a.pdepth[pid1];
-      }
-      const uint32_t my_last = have ? lds_last[p] : 0u;
-      for (int base = 0; base < n; base += 64) {
-        if (__all((uint32_t)base >= my_last)) break;
-        __syncthreads();
-        const int k = base + lane;
-        bool rel_lane = false;
-        if (k < n) {
-          const uint32_t g = a.point_list[range.x + k];
-          rel_lane = stage_record(a.splat_a, g, lds_a, lane, reg_x0, reg_x1, reg_y0, reg_y1);
-          const float4* si = a.inte_rec + 2 * (size_t)g;
-          lds_i[lane * 2 + 0] = si[0]; lds_i[lane * 2 + 1] = si[1];
-        }
-        uint64_t rel = __ballot(rel_lane);
-        __syncthreads();
-        const unsigned long long my_bits = have ? lds_used[(base >> 6) * 64 + p] : 0ull;
-        while (rel != 0) {
-          const int j = __builtin_ctzll(rel);
-          rel &= rel - 1;
-          const bool mine = ((my_bits >> j) & 1ull) != 0ull;     // phase 1's decision for (this point's pixel, entry)
-          if (!__any(mine)) continue;
-          if (!mine) continue;
-          const float4 A = lds_a[j * 4 + 0], B = lds_a[j * 4 + 1], Cc = lds_a[j * 4 + 2], D = lds_a[j * 4 + 3];
-          const float4 I0 = lds_i[j * 2 + 0], I1 = lds_i[j * 2 + 1];
-          const m3 inv = mk33(I0.x, I0.y, I0.z, I0.y, I0.w, I1.x, I0.z, I1.x, I1.y);
-          const bool cond = I1.z != 0.0f;
-          const float dx = A.x - qx1, dy = A.y - qy1;
-          const float depth = B.w + (Cc.w * dx + D.x * dy);
-          float alpha;
-          if (cond) {
-            const v3 du = mk3(dx, dy, B.w - fminf(qd1, depth));
-            const float power = -0.5f * dot(du, mul(inv, du));
-            alpha = fminf(0.99f, B.y * exp_spec(fminf(power, 80.0f)));
-          } else if (qd1 < depth) {
-            alpha = 0.f;
-          } else {
-            const v3 du = mk3(dx, dy, B.w);
-            const float power = -0.5f * dot(du, mul(inv, du));
-            alpha = fminf(0.99f, B.y * exp_spec(fminf(power, 80.0f)));
-          }
-          if (alpha < 1.0f / 255.0f) continue;
-          const float test_T = pT1 * (1 - alpha);
-          pa1 += alpha * pT1;
-          pT1 = test_T;
-        }
-      }
-      if (have) {
-        const size_t qi = pid1;
-        const float* pp = lds_pix + p * 8;
-        a.out_alpha_integrated[qi] = pa1;
-        a.out_color_integrated[3 * qi] = pp[0]; a.out_color_integrated[3 * qi + 1] = pp[1]; a.out_color_integrated[3 * qi + 2] = pp[2];
-        a.out_coordinate2d[2 * qi] = qx1; a.out_coordinate2d[2 * qi + 1] = qy1;
-        if (qd1 > 0) {
-          const float dx = pp[6] - qx1, dy = pp[7] - qy1;
-          const float depth = pp[3] + (pp[4] * dx + pp[5] * dy);
-          a.out_sdf[qi] = depth - qd1;
-        }
-      }
-    }
-    return;
-  }
-  while (__any(cur < pe)) {
-    const int np = (int)min((uint32_t)kPointsPerPass, pe - cur);
-    uint32_t pid[kPointsPerPass];
-    float qx[kPointsPerPass], qy[kPointsPerPass], qd[kPointsPerPass], pa[kPointsPerPass], pT[kPointsPerPass];
-#pragma unroll
-    for (int i = 0; i < kPointsPerPass; i++) {
-      pid[i] = 0; qx[i] = qy[i] = qd[i] = 0.f; pa[i] = 0.f; pT[i] = 1.f;
-      if (i < np) {
-        pid[i] = a.pt_sorted[cur + i];
-        const float2 q = a.p2d[pid[i]];
-        qx[i] = q.x; qy[i] = q.y; qd[i] = a.pdepth[pid[i]];
-      }
-    }
-    float rT[5] = {1.f, 1.f, 1.f, 1.f, 1.f};
-    const uint32_t my_last = np > 0 ? last_c : 0u;
-    for (int base = 0; base < n; base += 64) {
-      if (__all((uint32_t)base >= my_last)) break;
-      __syncthreads();
-      const int k = base + lane;
-      bool rel_lane = false;
-      if (k < n) {
-        const uint32_t g = a.point_list[range.x + k];
-        rel_lane = stage_record(a.splat_a, g, lds_a, lane, reg_x0, reg_x1, reg_y0, reg_y1);
-        const float4* si = a.inte_rec + 2 * (size_t)g;
-        lds_i[lane * 2 + 0] = si[0]; lds_i[lane * 2 + 1] = si[1];
-      }
-      uint64_t rel = __ballot(rel_lane);
-      __syncthreads();
-      const unsigned long long my_bits = cached ? lds_used[(base >> 6) * 64 + lane] : 0ull;
-      while (rel != 0) {
-        const int j = __builtin_ctzll(rel);
-        rel &= rel - 1;
-        if (cached) {                                   // phase 1's decision for this (pixel, entry)
-          const bool mine = np > 0 && ((my_bits >> j) & 1ull) != 0ull;
-          if (!__any(mine)) continue;
-          if (!mine) continue;
-        } else if ((uint32_t)(base + j + 1) > my_last) continue;
-        const float4 A = lds_a[j * 4 + 0], B = lds_a[j * 4 + 1], Cc = lds_a[j * 4 + 2], D = lds_a[j * 4 + 3];
-        if (!cached) {
-          FiveSample f;
-          if (!five_sample(A, B, Cc.w, D.x, pixfx, pixfy, rT, f)) continue;
-        }
-        const float4 I0 = lds_i[j * 2 + 0], I1 = lds_i[j * 2 + 1];
-        const m3 inv = mk33(I0.x, I0.y, I0.z, I0.y, I0.w, I1.x, I0.z, I1.x, I1.y);
-        const bool cond = I1.z != 0.0f;
-#pragma unroll
-        for (int i = 0; i < kPointsPerPass; i++) {
-          if (i >= np) continue;
-          const float dx = A.x - qx[i], dy = A.y - qy[i];
-          const float depth = B.w + (Cc.w * dx + D.x * dy);
-          float alpha;
-          if (cond) {
-            const v3 du = mk3(dx, dy, B.w - fminf(qd[i], depth));
-            const float power = -0.5f * dot(du, mul(inv, du));
-            alpha = fminf(0.99f, B.y * exp_spec(fminf(power, 80.0f)));
-          } else if (qd[i] < depth) {
-            alpha = 0.f;
-          } else {
-            const v3 du = mk3(dx, dy, B.w);
-            const float power = -0.5f * dot(du, mul(inv, du));
-            alpha = fminf(0.99f, B.y * exp_spec(fminf(power, 80.0f)));
-          }
-          if (alpha < 1.0f / 255.0f) continue;
-          const float test_T = pT[i] * (1 - alpha);
-          pa[i] += alpha * pT[i];
-          pT[i] = test_T;
-        }
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < kPointsPerPass; i++) {
-      if (i >= np) continue;
-      const size_t q = pid[i];
-      a.out_alpha_integrated[q] = pa[i];
-      a.out_color_integrated[3 * q] = col0; a.out_color_integrated[3 * q + 1] = col1; a.out_color_integrated[3 * q + 2] = col2;
-      a.out_coordinate2d[2 * q] = qx[i]; a.out_coordinate2d[2 * q + 1] = qy[i];
-      if (qd[i] > 0) {
-        const float dx = mid_mx - qx[i], dy = mid_my - qy[i];
-        const float depth = mid_dc + (mid_px * dx + mid_py * dy);
-        a.out_sdf[q] = depth - qd[i];
-      }
-    }
-    cur += (uint32_t)np;
-  }
-}
+#include "rg_integrate.inc"   // GaussianRasterizer.integrate: the query-point kernels and integrate_kernel
 
 // =========================================================================== blend, fwd ==
 struct BlendFwdArgs {

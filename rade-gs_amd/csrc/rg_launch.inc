@@ -964,6 +964,27 @@ int radegs_backward_from_sums(const RadegsBwdArgs* A, const float* sums, void* s
   return queue_preprocess_bwd(A, gs, cam, sums, rec, true, drgb_done, dbg, stream, true);
 }
 
+// The query points of radegs_integrate: project, count per pixel, scan, scatter (a counting sort on the pixel index).  Also clears the
+// image state's two n_contrib planes (integrate_kernel writes plane 0 only).
+static int queue_points(const RadegsIntegrateArgs* A, const CamArgs& cam, const PointState& ps, uint32_t* n_contrib, bool dbg, hipStream_t stream) {
+  const int PN = A->PN, W = A->width, H = A->height;
+  const size_t HW = (size_t)W * H;
+  RG_HIP(hipMemsetAsync(ps.pix_count, 0, HW * sizeof(uint32_t), stream));
+  RG_HIP(hipMemsetAsync(n_contrib, 0, 2 * HW * sizeof(uint32_t), stream));
+  PointsPreArgs pp;
+  pp.PN = PN; pp.points3D = A->points3D; pp.view = A->viewmatrix; pp.focal_x = cam.focal_x; pp.focal_y = cam.focal_y; pp.W = W; pp.H = H;
+  pp.p2d = reinterpret_cast<float2*>(ps.p2d); pp.pdepth = ps.pdepth; pp.ppix = ps.ppix; pp.pix_count = ps.pix_count;
+  pp.out_alpha_integrated = A->out_alpha_integrated; pp.out_color_integrated = A->out_color_integrated;
+  pp.out_coordinate2d = A->out_coordinate2d; pp.out_sdf = A->out_sdf;
+  hipLaunchKernelGGL(points_preprocess_kernel, dim3((PN + 255) / 256), dim3(256), 0, stream, pp);
+  RG_LAUNCH_CHECK("points_preprocess_kernel", dbg, stream);
+  RG_HIP(inclusive_scan_gather_u32(ps.temp, ps.temp_bytes, ps.pix_count, nullptr, ps.pix_incl, HW, stream));
+  hipLaunchKernelGGL(points_scatter_kernel, dim3((PN + 255) / 256), dim3(256), 0, stream, PN, ps.ppix, ps.pix_count, ps.pix_incl,
+                     ps.pt_sorted);
+  RG_LAUNCH_CHECK("points_scatter_kernel", dbg, stream);
+  return 0;
+}
+
 int radegs_integrate(const RadegsIntegrateArgs* A, radegs_alloc_fn geom_alloc, void* geom_user, radegs_alloc_fn binning_alloc,
                      void* binning_user, radegs_alloc_fn image_alloc, void* image_user, radegs_alloc_fn point_alloc, void* point_user,
                      void* stream_v) {
@@ -1010,22 +1031,8 @@ int radegs_integrate(const RadegsIntegrateArgs* A, radegs_alloc_fn geom_alloc, v
   const BinState& bs = B.bs;
   const ImageState& is = B.is;
 
-  // query points: project, count per pixel, scan, scatter (a counting sort on the pixel index)
-  RG_HIP(hipMemsetAsync(ps.pix_count, 0, HW * sizeof(uint32_t), stream));
-  RG_HIP(hipMemsetAsync(is.n_contrib, 0, 2 * HW * sizeof(uint32_t), stream));
-  {
-    PointsPreArgs pp;
-    pp.PN = PN; pp.points3D = A->points3D; pp.view = A->viewmatrix; pp.focal_x = cam.focal_x; pp.focal_y = cam.focal_y; pp.W = W; pp.H = H;
-    pp.p2d = reinterpret_cast<float2*>(ps.p2d); pp.pdepth = ps.pdepth; pp.ppix = ps.ppix; pp.pix_count = ps.pix_count;
-    pp.out_alpha_integrated = A->out_alpha_integrated; pp.out_color_integrated = A->out_color_integrated;
-    pp.out_coordinate2d = A->out_coordinate2d; pp.out_sdf = A->out_sdf;
-    hipLaunchKernelGGL(points_preprocess_kernel, dim3((PN + 255) / 256), dim3(256), 0, stream, pp);
-    RG_LAUNCH_CHECK("points_preprocess_kernel", dbg, stream);
-    RG_HIP(inclusive_scan_gather_u32(ps.temp, ps.temp_bytes, ps.pix_count, nullptr, ps.pix_incl, HW, stream));
-    hipLaunchKernelGGL(points_scatter_kernel, dim3((PN + 255) / 256), dim3(256), 0, stream, PN, ps.ppix, ps.pix_count, ps.pix_incl,
-                       ps.pt_sorted);
-    RG_LAUNCH_CHECK("points_scatter_kernel", dbg, stream);
-  }
+  const int rq = queue_points(A, cam, ps, is.n_contrib, dbg, stream);
+  if (rq < 0) return rq;
   {
     IntegrateArgs ia;
     ia.ranges = reinterpret_cast<const uint2*>(is.ranges); ia.point_list = bs.point_list;

@@ -48,10 +48,29 @@ def _run(s, pts, debug=False):
     return st[0], [t.cpu().numpy() for t in out], nc
 
 
-def check(s, pts, min_projected=1):
+# kUsedBatches * 64 (csrc/rg_integrate.inc): a tile list this long still has every used bit of phase 1 in LDS, so its four strips take
+# the point-major (cached) phase 2; a longer one makes them replay the 5-sample test per pixel
+BITS_REACH = 12 * 64
+
+
+def strips(o, ref, s):
+    """Per 16x4 pixel strip (one wave of integrate_kernel), from the oracle: the length of its tile's list, the number of query points in
+    the strip and in its fullest pixel."""
+    gx, gy = (s.W + 15) // 16, (s.H + 15) // 16
+    rg = o.get("ranges")[: 2 * gx * gy].reshape(gy, gx, 2).astype(np.int64)
+    per_pixel = np.zeros((gy * 16, gx * 16), np.int64)
+    per_pixel[: s.H, : s.W] = ref[0][8]
+    per_pixel = per_pixel.reshape(gy * 4, 4, gx, 16)
+    return np.repeat(rg[..., 1] - rg[..., 0], 4, axis=0), per_pixel.sum(axis=(1, 3)), per_pixel.max(axis=(1, 3))
+
+
+def check(s, pts, min_projected=1, path=None):
+    """path(*strips(...)): the test's precondition on the phase-2 form its scene reaches, asserted first"""
     assert s.kernel_size == 0.0  # the operator hard-codes kernel_size 0.0 for integrate (upstream __init__.py:283)
     o = oracle_for(s)
     ref = o.integrate(pts)
+    if path:
+        path(*strips(o, ref, s))
     R, got, nc = _run(s, pts)
     H, W = s.H, s.W
     assert R == o.num_rendered, "num_rendered"
@@ -68,9 +87,17 @@ def check(s, pts, min_projected=1):
     return o, got
 
 
+def all_cached(length, pts, pixel_max):
+    assert length.max() <= BITS_REACH, length.max()
+
+
+def some_replay(length, pts, pixel_max):
+    assert length.max() > BITS_REACH, length.max()
+
+
 def test_integrate_random_scene():
     s = make_scene(6000, 200, 152, sh_degree=2, mu_px=4.0, seed=31, kernel_size=0.0, pose="random", require_coord=False, require_depth=True)
-    o, got = check(s, _points(s, 20000, 1, far=500), min_projected=5000)
+    o, got = check(s, _points(s, 20000, 1, far=500), min_projected=5000, path=all_cached)
     a = got[1]
     assert ((a >= 0) & (a <= 1)).all() and (a < 0.5).sum() > 100 and (a > 0.9).sum() > 100
 
@@ -79,8 +106,24 @@ def test_integrate_many_points_per_pixel_and_heavy_overdraw():
     # 64x48 image, 30k points -> ~10 per pixel: several 4-point passes per lane; large splats -> long tile lists
     s = make_scene(1500, 64, 48, sh_degree=0, mu_px=12.0, seed=32, kernel_size=0.0, pose="random", require_coord=False,
                    require_depth=True, low_opacity=True)
-    o, got = check(s, _points(s, 30000, 2, spread=0.3), min_projected=10000)
+    o, got = check(s, _points(s, 30000, 2, spread=0.3), min_projected=10000, path=some_replay)
     assert got[0][8].max() > 8
+
+
+@pytest.mark.parametrize("P,W,H,n,replay", [(3000, 128, 96, 40000, False), (2500, 96, 64, 25000, True)], ids=["cached", "cached_and_replay"])
+def test_integrate_strips_of_more_than_64_points(P, W, H, n, replay):
+    """A cached strip deals its query points to the lanes 64 at a time: here every cached strip needs several deals (up to five in the
+    first scene), and in the second scene some tiles replay with up to five passes of four points per pixel next to cached ones."""
+    s = make_scene(P, W, H, sh_degree=0, mu_px=3.0, seed=41, kernel_size=0.0, pose="random", require_coord=False, require_depth=True)
+
+    def path(length, pts, pixel_max):
+        cached = length <= BITS_REACH
+        assert cached.any() and (pts[cached] > 64).any(), "no cached strip with a second deal"
+        assert replay == (~cached).any(), length.max()
+        if replay:
+            assert pixel_max[~cached].max() > 4, "no replayed pixel with a second pass"   # kPointsPerPass
+
+    check(s, _points(s, n, 9), path=path)
 
 
 def test_integrate_ill_conditioned_gaussians():
