@@ -104,7 +104,7 @@
       if constexpr (COORD) { E0 = lds_b[j * 3 + 0]; E1 = lds_b[j * 3 + 1]; E2 = lds_b[j * 3 + 2]; }
       // the lane's sums over its pixel pairs; components 9..14 as RAW MOMENTS of h = opacity G dL/dalpha about the Gaussian's centre, everything
       // "times dx" applied once to the lane's total (all pixels of a lane share dx): the record blend_bwd_streams_kernel writes
-      // (rg_streams.inc), turned into the reference's sums once per Gaussian by preprocess_bwd_kernel (PreBwdArgs::acc_raw)
+      // (rg_streams.inc), turned into the reference's sums once per Gaussian by preprocess_bwd_kernel (RecordKind::raw_moments, rg_per_gaussian.inc)
       f2 s_col[3], s_nrm[3], s_dt = bc2(0.f), s_dty = bc2(0.f), s_u = bc2(0.f), s_h = bc2(0.f), s_uy = bc2(0.f), s_uyy = bc2(0.f), s_ab = bc2(0.f);
       f2 s_co[COORD ? 3 : 1], s_coy[COORD ? 3 : 1];
 #pragma unroll

@@ -744,54 +744,11 @@ int radegs_forward(const RadegsFwdArgs* A, radegs_alloc_fn geom_alloc, void* geo
   return bin_and_blend(B, A);
 }
 
-// The per-Gaussian backward (computeCov2DCUDA + preprocessCUDA bwd, backward.cu:145-628) over the records `acc`; acc_final: the records
-// already carry the constant factors the blend backward leaves out of its sums (radegs_backward_from_sums).
-static int queue_preprocess_bwd(const RadegsBwdArgs* A, const GeomState& gs, const CamArgs& cam, const float* acc, int rec, bool acc_final,
-                                bool drgb_done, bool dbg, hipStream_t stream, bool chunked = false, int acc_raw = 0, bool acc_rezero = false) {
-  StageTimer tm(ST_PRE_BWD, stream);
-  const int P = A->P;
-  PreBwdArgs pa;
-  pa.P = P; pa.D = A->D; pa.M = A->M;
-  pa.means3D = A->means3D; pa.scales = A->scales; pa.rotations = A->rotations; pa.cov3D_precomp = A->cov3D_precomp; pa.shs = A->shs;
-  pa.radii = A->radii; pa.splat_a = reinterpret_cast<const float4*>(gs.splat_a); pa.clamped = gs.clamped; pa.acc = acc; pa.rec = rec;
-  pa.cam = cam;
-  pa.dL_dmean2D = A->dL_dmean2D; pa.dL_dcolor = A->dL_dcolor; pa.dL_dopacity = A->dL_dopacity; pa.dL_dmean3D = A->dL_dmean3D;
-  pa.dL_dcov3D = A->dL_dcov3D; pa.dL_dsh = A->shs ? A->dL_dsh : nullptr; pa.dL_dscale = A->dL_dscale; pa.dL_drot = A->dL_drot;
-  pa.dL_drgb_clamped = A->dL_drgb_clamped;
-  pa.opacity_grad_intended = A->opacity_grad_intended;
-  pa.drgb_done = drgb_done ? 1 : 0;
-  pa.acc_final = acc_final ? 1 : 0;
-  pa.acc_raw = acc_raw;
-  pa.acc_out = const_cast<float*>(acc);
-  pa.acc_rezero = acc_rezero ? 1 : 0;
-  {  // 16-byte slab moves where shape and alignment allow (SH degree 3: M = 16; also M = 4); any other shape or a tensor off a 16-byte boundary takes the word loop
-    const int rowf = A->M * 3;
-    const bool aligned = (reinterpret_cast<uintptr_t>(pa.shs) & 15u) == 0 && (reinterpret_cast<uintptr_t>(pa.dL_dsh) & 15u) == 0;
-    pa.vec_slab = (pa.shs && rowf % 4 == 0 && rowf <= 4 * kSlabVecs && aligned) ? 1 : 0;
-  }
-  const size_t sh_lds = pa.shs ? (size_t)kPreBwdThreads * (A->M * 3 + 1) * sizeof(float) : 0;
-  const int nblocks = (P + kPreBwdThreads - 1) / kPreBwdThreads;
-  // RadegsBwdArgs::grad_chunks: several launches over consecutive ranges of Gaussians, the caller told after each one (its all-reduce of
-  // the finished rows then runs under the launches that follow)
-  const int chunks = (chunked && A->grad_chunks > 1 && A->grads_ready) ? std::min(A->grad_chunks, nblocks) : 1;
-  const int per = (nblocks + chunks - 1) / chunks;
-  for (int c = 0; c * per < nblocks; c++) {
-    const int nb = std::min(per, nblocks - c * per);
-    pa.first_block = c * per;
-    hipLaunchKernelGGL(preprocess_bwd_kernel, dim3(nb), dim3(kPreBwdThreads), sh_lds, stream, pa);
-    RG_LAUNCH_CHECK("preprocess_bwd_kernel", dbg, stream);
-    if (chunks > 1) {
-      const int first = c * per * kPreBwdThreads;
-      A->grads_ready(A->grads_ready_user, first, std::min(nb * kPreBwdThreads, P - first));
-    }
-  }
-  return 0;
-}
-
+// ---- backward: the stages of Rasterizer::backward ----------------------------------------------------------------------------
 // The scratch of radegs_backward_ordered, carved at 256-byte steps: one partial record per position of point_list, the positions sorted by
 // Gaussian (keys and positions), the sort's temporary.
 struct OrderedScratch {
-  float* part; uint32_t* keys; uint32_t* pos; void* sort_temp; size_t part_bytes, sort_bytes, total;
+  float* part = nullptr; uint32_t* keys = nullptr; uint32_t* pos = nullptr; void* sort_temp = nullptr; size_t part_bytes = 0, sort_bytes = 0, total = 0;
   static OrderedScratch carve(void* base, size_t R, bool coord) {
     OrderedScratch o;
     char* p = static_cast<char*>(base);
@@ -808,118 +765,211 @@ struct OrderedScratch {
   }
 };
 
+// One backward call: its arguments, the states of its forward, the per-Gaussian records and what the stages need to queue their work.
+// radegs_backward_from_sums fills the per-Gaussian part only (A, cam, gs, acc, rec, stream, dbg).
+struct Backward {
+  const RadegsBwdArgs* A = nullptr;
+  CamArgs cam;
+  GeomState gs; BinState bs; ImageState is;
+  float* acc = nullptr; int rec = 0;   // [P][rec] records: the accumulator, or the caller's sums (never written then)
+  hipStream_t stream = nullptr;
+  bool dbg = false, coord = false, depth = false;
+  bool acc_reuse = false;              // the accumulator came all zeros and goes back so (RadegsBwdArgs::acc_reuse)
+  int devid = 0;
+  OrderedScratch os;                   // radegs_backward_ordered with R > 0; os.part == nullptr otherwise
+  bool ordered() const { return os.part != nullptr; }
+};
+
+// The checks every backward entry point makes once its own pointers are there, in this order.  needs_state: a whole backward, which
+// replays the forward's image and binning state and may hand back dL_drgb_clamped in place of dL_dsh (the factored exchange); the hook
+// over caller-supplied sums reads the geometry state only and always returns dL_dsh.  Returns 1: go on; 0: P == 0, nothing is launched;
+// < 0: the error.
+static int check_backward_args(const RadegsBwdArgs* A, bool needs_state) {
+  if (A->struct_size != sizeof(RadegsBwdArgs)) return fail(RADEGS_ERR_INVALID_ARG, "RadegsBwdArgs.struct_size does not match this library's include/radegs.h");
+  if (A->P == 0) return 0;
+  if (!A->geom_buffer || (needs_state && (!A->image_buffer || (A->R > 0 && !A->binning_buffer))))
+    return fail(RADEGS_ERR_INVALID_ARG, "state buffers missing");
+  if (!A->dL_dmean2D || !A->dL_dcolor || !A->dL_dopacity || !A->dL_dmean3D || !A->dL_dcov3D || !A->dL_dscale || !A->dL_drot)
+    return fail(RADEGS_ERR_INVALID_ARG, "gradient outputs missing");
+  if (A->shs && !A->dL_dsh && !(needs_state && A->dL_drgb_clamped)) return fail(RADEGS_ERR_INVALID_ARG, "dL_dsh missing");
+  return 1;
+}
+
+// What has to be zero before the blend: the accumulator, unless its owner keeps it zero -- or, ordered, the partial records (the blend
+// leaves out those of entries it skips; ordered_sums_kernel then writes every record of the accumulator).
+static int queue_acc_zero(const Backward& B) {
+  void* const what = B.ordered() ? static_cast<void*>(B.os.part) : (B.acc_reuse ? nullptr : static_cast<void*>(B.acc));
+  if (!what) return 0;
+  StageTimer tm(ST_ACC_ZERO, B.stream);
+  RG_HIP(hipMemsetAsync(what, 0, B.ordered() ? B.os.part_bytes : (size_t)B.A->P * B.rec * sizeof(float), B.stream));
+  return 0;
+}
+
+// The four formulations of the blend backward.  All leave the same record per Gaussian (raw moments in components 9..14, rg_streams.inc).
+//   ordered   radegs_backward_ordered: the tile-wide kernel, one wave per tile, one partial record per list position
+//   streams   replays the forward's entry streams -- only when the forward that filled THIS image buffer wrote them, and while the
+//             accumulator fits the kernel's 32-bit byte offsets (33 M Gaussians with the coord map, 67 M without)
+//   packed2   tile-wide, valid after either forward: one wave per 16x8 strip (2 pixels per lane)
+//   packed4   tile-wide, one wave per tile (4 per lane) once every entry covers the tile anyway.  Measured on the MI355X: within 1 % of
+//             packed2 either way up to 200 tiles per Gaussian on synthetic scenes, -8 % on C5 (4K, heavy overdraw: 4.41 against 4.80 ms);
+//             never with the coord map (+5 %) -> from R >= 64 P on, without the coord map
+enum class BlendBwd { ordered, streams, packed2, packed4 };
+constexpr uint64_t kStreamBwdMaxAccBytes = 0xFFFFFFFFull;
+static BlendBwd choose_blend_bwd(const Switches& sw, bool ordered, bool has_streams, int P, int R, bool coord) {
+  if (ordered) return BlendBwd::ordered;
+  const bool acc_fits = (uint64_t)P * (uint64_t)(acc_record_floats(coord) * sizeof(float)) <= kStreamBwdMaxAccBytes;
+  if (has_streams && sw.streams_bwd && acc_fits) return BlendBwd::streams;
+  if (sw.bwd_ppl == 2) return BlendBwd::packed2;
+  if (sw.bwd_ppl == 4) return BlendBwd::packed4;
+  return (!coord && (long long)R >= 64ll * P) ? BlendBwd::packed4 : BlendBwd::packed2;
+}
+
+// renderCUDA bwd (R > 0): the pixels' cotangents into per-Gaussian records -- the accumulator, or the ordered scratch's partial records
+static int queue_blend_bwd(const Backward& B) {
+  const RadegsBwdArgs* A = B.A;
+  const GeomState& gs = B.gs; const BinState& bs = B.bs; const ImageState& is = B.is; const CamArgs& cam = B.cam;
+  hipStream_t stream = B.stream;
+  const int ntiles = cam.gx * cam.gy;
+  StageTimer tm(ST_BLEND_BWD, stream);
+  BlendBwdArgs ba;
+  ba.ranges = reinterpret_cast<const uint2*>(is.ranges); ba.point_list = bs.point_list;
+  ba.splat_a = reinterpret_cast<const float4*>(gs.splat_a); ba.splat_b = reinterpret_cast<const float4*>(gs.splat_b);
+  ba.W = cam.W; ba.H = cam.H; ba.gx = cam.gx; ba.ntiles = ntiles; ba.focal_x = cam.focal_x; ba.focal_y = cam.focal_y;
+  ba.bg = A->background; ba.alphas = A->alphas; ba.normalmap = A->normalmap;
+  ba.n_contrib = is.n_contrib; ba.accum_coord = is.accum_coord; ba.accum_depth = is.accum_depth; ba.normal_length = is.normal_length;
+  ba.dL_dpix = A->dL_dpix; ba.dL_dcoord = A->dL_dpix_coord; ba.dL_dmcoord = A->dL_dpix_mcoord; ba.dL_ddepth = A->dL_dpix_depth;
+  ba.dL_dmdepth = A->dL_dpix_mdepth; ba.dL_dalpha = A->dL_dalphas; ba.dL_dnormal = A->dL_dpix_normal;
+  ba.acc = B.ordered() ? B.os.part : B.acc; ba.P = A->P;
+  ba.blk_base = is.blk_base; ba.blk_consumed = is.blk_consumed; ba.blk_chunks = is.blk_chunks; ba.blk_order = is.blk_order; ba.stream_tag = is.stream_tag;
+  {
+    PinnedCount& pin = pinned_for(B.devid);
+    ba.stream_err = (B.devid < 64 && pin.ok()) ? pin.dev() + PIN_STREAM_ERR : nullptr;
+  }
+  if (!ba.alphas || !ba.dL_dpix || !ba.dL_dalpha) return fail(RADEGS_ERR_INVALID_ARG, "pixel gradients missing");
+  if (B.coord && (!ba.dL_dcoord || !ba.dL_dmcoord)) return fail(RADEGS_ERR_INVALID_ARG, "coord gradients missing");
+  if (B.depth && (!ba.dL_ddepth || !ba.dL_dmdepth)) return fail(RADEGS_ERR_INVALID_ARG, "depth gradients missing");
+  if ((B.coord || B.depth) && (!ba.dL_dnormal || !ba.normalmap)) return fail(RADEGS_ERR_INVALID_ARG, "normal gradients missing");
+  const BlendBwd how = choose_blend_bwd(switches(), B.ordered(), image_has_streams(A->image_buffer), A->P, A->R, B.coord);
+  dispatch(B.coord, B.depth, [&](auto c, auto d) {
+    switch (how) {
+      case BlendBwd::ordered: hipLaunchKernelGGL((blend_bwd_ordered_kernel<c, d>), dim3(ntiles), dim3(64), 0, stream, ba); break;
+      case BlendBwd::streams: hipLaunchKernelGGL((blend_bwd_streams_kernel<c, d>), dim3(ntiles * 2), dim3(64), 0, stream, ba); break;
+      case BlendBwd::packed2: hipLaunchKernelGGL((blend_bwd_packed_kernel<c, d, 2>), dim3(ntiles * 2), dim3(64), 0, stream, ba); break;
+      case BlendBwd::packed4: hipLaunchKernelGGL((blend_bwd_packed_kernel<c, d, 4>), dim3(ntiles), dim3(64), 0, stream, ba); break;
+    }
+  });
+  RG_LAUNCH_CHECK("blend_bwd_kernel", B.dbg, stream);
+  return 0;
+}
+
+// Ordered only: the partial records into the accumulator in a fixed order -- a stable sort of (point_list[r], r), after which every
+// Gaussian's positions are consecutive and ascending, then one sum per Gaussian and component over its run
+static int queue_ordered_sums(const Backward& B) {
+  const int P = B.A->P, R = B.A->R;
+  const OrderedScratch& os = B.os;
+  {
+    StageTimer tm(ST_ORDERED_SORT, B.stream);
+    int bits = 1;
+    while (bits < 32 && (1ull << bits) < (unsigned long long)P) bits++;
+    RG_HIP(radix_sort_pairs_u32(os.sort_temp, os.sort_bytes, B.bs.point_list, os.keys, nullptr, os.pos, (size_t)R, bits, B.stream));
+  }
+  StageTimer tm(ST_ORDERED_SUMS, B.stream);
+  const unsigned nb = (unsigned)(((size_t)P * B.rec + 255) / 256);
+  if (B.coord) hipLaunchKernelGGL((ordered_sums_kernel<32>), dim3(nb), dim3(256), 0, B.stream, P, (uint32_t)R, os.keys, os.pos, os.part, B.acc);
+  else hipLaunchKernelGGL((ordered_sums_kernel<16>), dim3(nb), dim3(256), 0, B.stream, P, (uint32_t)R, os.keys, os.pos, os.part, B.acc);
+  RG_LAUNCH_CHECK("ordered_sums_kernel", B.dbg, B.stream);
+  return 0;
+}
+
+// How a launch of preprocess_bwd_kernel treats the records (PreBwdArgs::keep, rezero, drgb_done)
+enum PreBwdFlags : unsigned { kKeepSums = 1u, kRezero = 2u, kDrgbDone = 4u };
+
+// The drgb_ready hand-off (include/radegs.h): the rows the factored exchange all-gathers leave one kernel early, and the caller is told
+static int queue_drgb(const Backward& B, unsigned& flags) {
+  const RadegsBwdArgs* A = B.A;
+  if (!A->dL_drgb_clamped || !A->drgb_ready) return 0;
+  hipLaunchKernelGGL(drgb_clamped_kernel, dim3((A->P + 255) / 256), dim3(256), 0, B.stream, A->P, A->radii, B.gs.clamped, B.acc, B.rec, A->dL_drgb_clamped);
+  RG_LAUNCH_CHECK("drgb_clamped_kernel", B.dbg, B.stream);
+  A->drgb_ready(A->drgb_ready_user);
+  flags |= kDrgbDone;
+  return 0;
+}
+
+// The per-Gaussian backward (computeCov2DCUDA + preprocessCUDA bwd, backward.cu:145-628) over the records B.acc
+static int queue_preprocess_bwd(const Backward& B, RecordKind kind, unsigned flags) {
+  const RadegsBwdArgs* A = B.A;
+  StageTimer tm(ST_PRE_BWD, B.stream);
+  const int P = A->P;
+  PreBwdArgs pa;
+  pa.P = P; pa.D = A->D; pa.M = A->M;
+  pa.means3D = A->means3D; pa.scales = A->scales; pa.rotations = A->rotations; pa.cov3D_precomp = A->cov3D_precomp; pa.shs = A->shs;
+  pa.radii = A->radii; pa.splat_a = reinterpret_cast<const float4*>(B.gs.splat_a); pa.clamped = B.gs.clamped; pa.acc = B.acc; pa.rec = B.rec;
+  pa.cam = B.cam;
+  pa.dL_dmean2D = A->dL_dmean2D; pa.dL_dcolor = A->dL_dcolor; pa.dL_dopacity = A->dL_dopacity; pa.dL_dmean3D = A->dL_dmean3D;
+  pa.dL_dcov3D = A->dL_dcov3D; pa.dL_dsh = A->shs ? A->dL_dsh : nullptr; pa.dL_dscale = A->dL_dscale; pa.dL_drot = A->dL_drot;
+  pa.dL_drgb_clamped = A->dL_drgb_clamped;
+  pa.opacity_grad_intended = A->opacity_grad_intended;
+  pa.kind = kind;
+  pa.keep = (flags & kKeepSums) ? 1 : 0; pa.rezero = (flags & kRezero) ? 1 : 0; pa.drgb_done = (flags & kDrgbDone) ? 1 : 0;
+  {  // 16-byte slab moves where shape and alignment allow (SH degree 3: M = 16; also M = 4); any other shape or a tensor off a 16-byte boundary takes the word loop
+    const int rowf = A->M * 3;
+    const bool aligned = (reinterpret_cast<uintptr_t>(pa.shs) & 15u) == 0 && (reinterpret_cast<uintptr_t>(pa.dL_dsh) & 15u) == 0;
+    pa.vec_slab = (pa.shs && rowf % 4 == 0 && rowf <= 4 * kSlabVecs && aligned) ? 1 : 0;
+  }
+  const size_t sh_lds = pa.shs ? (size_t)kPreBwdThreads * (A->M * 3 + 1) * sizeof(float) : 0;
+  const int nblocks = (P + kPreBwdThreads - 1) / kPreBwdThreads;
+  // RadegsBwdArgs::grad_chunks: several launches over consecutive ranges of Gaussians, the caller told after each one (its all-reduce of
+  // the finished rows then runs under the launches that follow)
+  const int chunks = (A->grad_chunks > 1 && A->grads_ready) ? std::min(A->grad_chunks, nblocks) : 1;
+  const int per = (nblocks + chunks - 1) / chunks;
+  for (int c = 0; c * per < nblocks; c++) {
+    const int nb = std::min(per, nblocks - c * per);
+    pa.first_block = c * per;
+    hipLaunchKernelGGL(preprocess_bwd_kernel, dim3(nb), dim3(kPreBwdThreads), sh_lds, B.stream, pa);
+    RG_LAUNCH_CHECK("preprocess_bwd_kernel", B.dbg, B.stream);
+    if (chunks > 1) {
+      const int first = c * per * kPreBwdThreads;
+      A->grads_ready(A->grads_ready_user, first, std::min(nb * kPreBwdThreads, P - first));
+    }
+  }
+  return 0;
+}
+
 // radegs_backward (ordered = false) and radegs_backward_ordered (ordered = true): they differ in how the blend backward's wave totals
 // reach the per-Gaussian records, nowhere else.
 static int backward_impl(const RadegsBwdArgs* A, radegs_alloc_fn accum_alloc, void* accum_user, bool ordered, void* scratch, size_t scratch_bytes,
                          void* stream_v) {
   if (!A || !accum_alloc) return fail(RADEGS_ERR_INVALID_ARG, "null argument");
-  if (A->struct_size != sizeof(RadegsBwdArgs)) return fail(RADEGS_ERR_INVALID_ARG, "RadegsBwdArgs.struct_size does not match this library's include/radegs.h");
-  if (A->P == 0) return 0;
-  if (!A->geom_buffer || !A->image_buffer || (A->R > 0 && !A->binning_buffer))
-    return fail(RADEGS_ERR_INVALID_ARG, "state buffers missing");
-  if (!A->dL_dmean2D || !A->dL_dcolor || !A->dL_dopacity || !A->dL_dmean3D || !A->dL_dcov3D || !A->dL_dscale || !A->dL_drot)
-    return fail(RADEGS_ERR_INVALID_ARG, "gradient outputs missing");
-  if (A->shs && !A->dL_dsh && !A->dL_drgb_clamped) return fail(RADEGS_ERR_INVALID_ARG, "dL_dsh missing");
-  hipStream_t stream = static_cast<hipStream_t>(stream_v);
-  const bool dbg = A->debug != 0;
-  const bool coord = A->require_coord != 0, depth = A->require_depth != 0;
-  const int P = A->P, W = A->width, H = A->height, R = A->R;
-  OrderedScratch os{};
+  int rc = check_backward_args(A, true);
+  if (rc <= 0) return rc;
+  Backward B;
+  B.A = A; B.stream = static_cast<hipStream_t>(stream_v);
+  B.dbg = A->debug != 0; B.coord = A->require_coord != 0; B.depth = A->require_depth != 0;
+  const int P = A->P, R = A->R;
   if (ordered && R > 0) {
     if (!scratch) return fail(RADEGS_ERR_INVALID_ARG, "radegs_backward_ordered: scratch is NULL with R > 0");
-    os = OrderedScratch::carve(scratch, (size_t)R, coord);
-    if (scratch_bytes < os.total) return fail(RADEGS_ERR_INVALID_ARG, "radegs_backward_ordered: scratch smaller than radegs_backward_ordered_scratch_bytes(P, R, require_coord)");
+    B.os = OrderedScratch::carve(scratch, (size_t)R, B.coord);
+    if (scratch_bytes < B.os.total) return fail(RADEGS_ERR_INVALID_ARG, "radegs_backward_ordered: scratch smaller than radegs_backward_ordered_scratch_bytes(P, R, require_coord)");
   }
-  int devid = 0;
-  (void)hipGetDevice(&devid);
-  {
-    const int rc = check_stream_error(devid);
-    if (rc < 0) return rc;
-  }
-  const CamArgs cam = make_cam(A->viewmatrix, A->projmatrix, A->cam_pos, W, H, A->tan_fovx, A->tan_fovy, A->kernel_size, A->scale_modifier);
-  const int ntiles = cam.gx * cam.gy;
-  GeomState gs = GeomState::carve(A->geom_buffer, (size_t)P, coord, 0);
-  BinState bs = BinState::carve(A->binning_buffer, (size_t)R, 0);
-  ImageState is = ImageState::carve(A->image_buffer, (size_t)W, (size_t)H);
+  (void)hipGetDevice(&B.devid);
+  if ((rc = check_stream_error(B.devid)) < 0) return rc;
+  B.cam = make_cam(A->viewmatrix, A->projmatrix, A->cam_pos, A->width, A->height, A->tan_fovx, A->tan_fovy, A->kernel_size, A->scale_modifier);
+  B.gs = GeomState::carve(A->geom_buffer, (size_t)P, B.coord, 0);
+  B.bs = BinState::carve(A->binning_buffer, (size_t)R, 0);
+  B.is = ImageState::carve(A->image_buffer, (size_t)A->width, (size_t)A->height);
+  B.rec = acc_record_floats(B.coord);
+  B.acc = static_cast<float*>(accum_alloc(accum_user, (size_t)P * B.rec * sizeof(float)));
+  if (!B.acc) return fail(RADEGS_ERR_ALLOC, "accumulator allocation failed");
+  B.acc_reuse = A->acc_reuse != 0 && !A->keep_sums;   // the caller's scratch is zero and wants to stay so (include/radegs.h)
 
-  const int rec = acc_record_floats(coord);
-  const size_t abytes = (size_t)P * rec * sizeof(float);
-  float* acc = static_cast<float*>(accum_alloc(accum_user, abytes));
-  if (!acc) return fail(RADEGS_ERR_ALLOC, "accumulator allocation failed");
-  int acc_raw = 0;
-  const bool acc_reuse = A->acc_reuse != 0 && !A->keep_sums;   // the caller's scratch is zero and wants to stay so (include/radegs.h)
-  if (ordered && R > 0) {   // ordered_sums_kernel writes every record of acc; what needs zeros is the partial records the blend leaves out
-    StageTimer tm(ST_ACC_ZERO, stream);
-    RG_HIP(hipMemsetAsync(os.part, 0, os.part_bytes, stream));
-  } else if (!acc_reuse) {
-    StageTimer tm(ST_ACC_ZERO, stream);
-    RG_HIP(hipMemsetAsync(acc, 0, abytes, stream));
-  }
-
-  if (R > 0) {
-    StageTimer tm(ST_BLEND_BWD, stream);
-    BlendBwdArgs ba;
-    ba.ranges = reinterpret_cast<const uint2*>(is.ranges); ba.point_list = bs.point_list;
-    ba.splat_a = reinterpret_cast<const float4*>(gs.splat_a); ba.splat_b = reinterpret_cast<const float4*>(gs.splat_b);
-    ba.W = W; ba.H = H; ba.gx = cam.gx; ba.ntiles = ntiles; ba.focal_x = cam.focal_x; ba.focal_y = cam.focal_y;
-    ba.bg = A->background; ba.alphas = A->alphas; ba.normalmap = A->normalmap;
-    ba.n_contrib = is.n_contrib; ba.accum_coord = is.accum_coord; ba.accum_depth = is.accum_depth; ba.normal_length = is.normal_length;
-    ba.dL_dpix = A->dL_dpix; ba.dL_dcoord = A->dL_dpix_coord; ba.dL_dmcoord = A->dL_dpix_mcoord; ba.dL_ddepth = A->dL_dpix_depth;
-    ba.dL_dmdepth = A->dL_dpix_mdepth; ba.dL_dalpha = A->dL_dalphas; ba.dL_dnormal = A->dL_dpix_normal;
-    ba.acc = ordered ? os.part : acc; ba.P = P;
-    ba.blk_base = is.blk_base; ba.blk_consumed = is.blk_consumed; ba.blk_chunks = is.blk_chunks; ba.blk_order = is.blk_order; ba.stream_tag = is.stream_tag;
-    {
-      PinnedCount& pin = pinned_for(devid);
-      ba.stream_err = (devid < 64 && pin.ok()) ? pin.dev() + PIN_STREAM_ERR : nullptr;
-    }
-    if (!ba.alphas || !ba.dL_dpix || !ba.dL_dalpha) return fail(RADEGS_ERR_INVALID_ARG, "pixel gradients missing");
-    if (coord && (!ba.dL_dcoord || !ba.dL_dmcoord)) return fail(RADEGS_ERR_INVALID_ARG, "coord gradients missing");
-    if (depth && (!ba.dL_ddepth || !ba.dL_dmdepth)) return fail(RADEGS_ERR_INVALID_ARG, "depth gradients missing");
-    if ((coord || depth) && (!ba.dL_dnormal || !ba.normalmap)) return fail(RADEGS_ERR_INVALID_ARG, "normal gradients missing");
-    // the forward's entry streams are replayed only when the forward that filled THIS image buffer wrote them
-    const Switches sw = switches();
-    acc_raw = 1;   // both blend backwards leave raw moments in components 9..14 of the records (rg_streams.inc)
-    // (the stream backward addresses the accumulator with 32-bit byte offsets: 33 M Gaussians with the coord map, 67 M without; beyond, the
-    // tile-wide backward -- valid after either forward -- takes over)
-    constexpr uint64_t kStreamBwdMaxAccBytes = 0xFFFFFFFFull;
-    const bool acc_fits = (uint64_t)A->P * (uint64_t)((coord ? 32 : 16) * sizeof(float)) <= kStreamBwdMaxAccBytes;
-    if (ordered) {   // the tile-wide backward, one wave per tile ("valid after either forward" below): one partial record per list position
-      dispatch(coord, depth, [&](auto c, auto d) { hipLaunchKernelGGL((blend_bwd_ordered_kernel<c, d>), dim3(ntiles), dim3(64), 0, stream, ba); });
-    } else if (image_has_streams(A->image_buffer) && sw.streams_bwd && acc_fits) {
-      dispatch(coord, depth, [&](auto c, auto d) { hipLaunchKernelGGL((blend_bwd_streams_kernel<c, d>), dim3(ntiles * 2), dim3(64), 0, stream, ba); });
-    } else {
-      // one wave per 16x8 strip (2 pixels per lane); one wave per tile (4 per lane) once every entry covers the tile anyway: within 1 %
-      // either way up to 200 tiles per Gaussian on synthetic scenes, -8 % on C5 (4K, heavy overdraw: 4.41 against 4.80 ms); never with
-      // the coord map (+5 %)
-      const int ppl = (sw.bwd_ppl == 2 || sw.bwd_ppl == 4) ? sw.bwd_ppl : ((!coord && (long long)R >= 64ll * P) ? 4 : 2);
-      dispatch(coord, depth, [&](auto c, auto d) {
-        if (ppl == 2) hipLaunchKernelGGL((blend_bwd_packed_kernel<c, d, 2>), dim3(ntiles * 2), dim3(64), 0, stream, ba);
-        else hipLaunchKernelGGL((blend_bwd_packed_kernel<c, d, 4>), dim3(ntiles), dim3(64), 0, stream, ba);
-      });
-    }
-    RG_LAUNCH_CHECK("blend_bwd_kernel", dbg, stream);
-  }
-  if (ordered && R > 0) {
-    {   // stable sort of (point_list[r], r): every Gaussian's positions end up consecutive and ascending
-      StageTimer tm(ST_ORDERED_SORT, stream);
-      int bits = 1;
-      while (bits < 32 && (1ull << bits) < (unsigned long long)P) bits++;
-      RG_HIP(radix_sort_pairs_u32(os.sort_temp, os.sort_bytes, bs.point_list, os.keys, nullptr, os.pos, (size_t)R, bits, stream));
-    }
-    StageTimer tm(ST_ORDERED_SUMS, stream);
-    const unsigned nb = (unsigned)(((size_t)P * rec + 255) / 256);
-    if (coord) hipLaunchKernelGGL((ordered_sums_kernel<32>), dim3(nb), dim3(256), 0, stream, P, (uint32_t)R, os.keys, os.pos, os.part, acc);
-    else hipLaunchKernelGGL((ordered_sums_kernel<16>), dim3(nb), dim3(256), 0, stream, P, (uint32_t)R, os.keys, os.pos, os.part, acc);
-    RG_LAUNCH_CHECK("ordered_sums_kernel", dbg, stream);
-  }
-  bool drgb_done = false;
-  if (A->dL_drgb_clamped && A->drgb_ready) {   // the rows the factored exchange all-gathers leave one kernel early (include/radegs.h)
-    hipLaunchKernelGGL(drgb_clamped_kernel, dim3((P + 255) / 256), dim3(256), 0, stream, P, A->radii, gs.clamped, acc, rec, A->dL_drgb_clamped);
-    RG_LAUNCH_CHECK("drgb_clamped_kernel", dbg, stream);
-    A->drgb_ready(A->drgb_ready_user);
-    drgb_done = true;
-  }
-  return queue_preprocess_bwd(A, gs, cam, acc, rec, false, drgb_done, dbg, stream, true, acc_raw ? (A->keep_sums ? 2 : 1) : 0, acc_reuse);
+  if ((rc = queue_acc_zero(B)) < 0) return rc;
+  if (R > 0 && (rc = queue_blend_bwd(B)) < 0) return rc;
+  if (B.ordered() && (rc = queue_ordered_sums(B)) < 0) return rc;
+  // a blend leaves raw moments; without one (R == 0) the records are the zeros they started as
+  const RecordKind kind = R > 0 ? RecordKind::raw_moments : RecordKind::blend_sums;
+  unsigned flags = (B.acc_reuse ? kRezero : 0u) | ((R > 0 && A->keep_sums) ? kKeepSums : 0u);
+  if ((rc = queue_drgb(B, flags)) < 0) return rc;
+  return queue_preprocess_bwd(B, kind, flags);
 }
 
 int radegs_backward(const RadegsBwdArgs* A, radegs_alloc_fn accum_alloc, void* accum_user, void* stream_v) {
@@ -935,33 +985,24 @@ int radegs_backward_ordered(const RadegsBwdArgs* A, radegs_alloc_fn accum_alloc,
   return backward_impl(A, accum_alloc, accum_user, true, scratch, scratch_bytes, stream_v);
 }
 
+// The per-Gaussian half alone, over the caller's sums, with the hand-off hooks of radegs_backward (tests reach the separate
+// dL_drgb_clamped kernel and the chunked launches this way)
 int radegs_backward_from_sums(const RadegsBwdArgs* A, const float* sums, void* stream_v) {
   if (!A || !sums) return fail(RADEGS_ERR_INVALID_ARG, "null argument");
-  if (A->struct_size != sizeof(RadegsBwdArgs)) return fail(RADEGS_ERR_INVALID_ARG, "RadegsBwdArgs.struct_size does not match this library's include/radegs.h");
-  if (A->P == 0) return 0;
-  if (!A->geom_buffer) return fail(RADEGS_ERR_INVALID_ARG, "state buffers missing");
-  if (!A->dL_dmean2D || !A->dL_dcolor || !A->dL_dopacity || !A->dL_dmean3D || !A->dL_dcov3D || !A->dL_dscale || !A->dL_drot)
-    return fail(RADEGS_ERR_INVALID_ARG, "gradient outputs missing");
-  if (A->shs && !A->dL_dsh) return fail(RADEGS_ERR_INVALID_ARG, "dL_dsh missing");
-  const int rc = check_gaussians(A, A->radii && A->means3D && A->viewmatrix && A->projmatrix && A->cam_pos, false);
-  if (rc < 0) return rc;
+  int rc = check_backward_args(A, false);
+  if (rc <= 0) return rc;
+  if ((rc = check_gaussians(A, A->radii && A->means3D && A->viewmatrix && A->projmatrix && A->cam_pos, false)) < 0) return rc;
   if (reinterpret_cast<uintptr_t>(sums) & 15u) return fail(RADEGS_ERR_INVALID_ARG, "sums must be 16-byte aligned");
-  hipStream_t stream = static_cast<hipStream_t>(stream_v);
-  const bool coord = A->require_coord != 0;
-  const CamArgs cam = make_cam(A->viewmatrix, A->projmatrix, A->cam_pos, A->width, A->height, A->tan_fovx, A->tan_fovy, A->kernel_size,
-                               A->scale_modifier);
-  GeomState gs = GeomState::carve(A->geom_buffer, (size_t)A->P, coord, 0);
-  const int rec = acc_record_floats(coord);
-  const bool dbg = A->debug != 0;
-  // the hand-off hooks of radegs_backward, over `sums` (tests reach the separate dL_drgb_clamped kernel and the chunked launches this way)
-  bool drgb_done = false;
-  if (A->dL_drgb_clamped && A->drgb_ready) {
-    hipLaunchKernelGGL(drgb_clamped_kernel, dim3((A->P + 255) / 256), dim3(256), 0, stream, A->P, A->radii, gs.clamped, sums, rec, A->dL_drgb_clamped);
-    RG_LAUNCH_CHECK("drgb_clamped_kernel", dbg, stream);
-    A->drgb_ready(A->drgb_ready_user);
-    drgb_done = true;
-  }
-  return queue_preprocess_bwd(A, gs, cam, sums, rec, true, drgb_done, dbg, stream, true);
+  Backward B;
+  B.A = A; B.stream = static_cast<hipStream_t>(stream_v);
+  B.dbg = A->debug != 0; B.coord = A->require_coord != 0;
+  B.cam = make_cam(A->viewmatrix, A->projmatrix, A->cam_pos, A->width, A->height, A->tan_fovx, A->tan_fovy, A->kernel_size, A->scale_modifier);
+  B.gs = GeomState::carve(A->geom_buffer, (size_t)A->P, B.coord, 0);
+  B.rec = acc_record_floats(B.coord);
+  B.acc = const_cast<float*>(sums);   // read only: neither kKeepSums nor kRezero
+  unsigned flags = 0;
+  if ((rc = queue_drgb(B, flags)) < 0) return rc;
+  return queue_preprocess_bwd(B, RecordKind::reference_sums, flags);
 }
 
 // The query points of radegs_integrate: project, count per pixel, scan, scatter (a counting sort on the pixel index).  Also clears the

@@ -165,6 +165,37 @@ _READY_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p)
 _GRADS_READY_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int)
 
 
+def _c_hook(fn_type, fn, errors):
+    """The Python callable `fn` as a C hook of type `fn_type` (it is not handed the hook's leading user pointer; the other arguments arrive
+    as ints).  An exception it raises must not unwind through the C frame: it is appended to `errors`, and the caller re-raises it once
+    the native call has returned.  fn None: no hook."""
+    if fn is None:
+        return None
+
+    def _call(_user, *args):
+        try:
+            fn(*(int(x) for x in args))
+        except Exception as ex:  # noqa: BLE001
+            errors.append(ex)
+    return fn_type(_call)
+
+
+def _bwd_args(**fields):
+    """RadegsBwdArgs from keyword fields (struct_size filled in; a field not named is 0 / NULL).  A tensor stands for its device pointer,
+    None for NULL, a hook made by _c_hook for its C address."""
+    unknown = set(fields) - {name for name, _ in RadegsBwdArgs._fields_}
+    if unknown:
+        raise TypeError(f"RadegsBwdArgs has no field {sorted(unknown)}")
+    a = RadegsBwdArgs(struct_size=ctypes.sizeof(RadegsBwdArgs))
+    for name, v in fields.items():
+        if isinstance(v, torch.Tensor):
+            v = _ptr(v)
+        elif isinstance(v, (_READY_FN, _GRADS_READY_FN)):
+            v = ctypes.cast(v, ctypes.c_void_p)
+        setattr(a, name, v)
+    return a
+
+
 def library():
     """Load libradegs_hip.so (built in-tree by rade-gs_amd/build.py).  Fails loudly."""
     global _lib
@@ -518,35 +549,26 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
         ready_cb, ready_err = None, []
         owner = getattr(grad_alloc, "__self__", None)
         if drgb is not None and owner is not None and callable(getattr(owner, "drgb_ready", None)) and getattr(owner, "early_drgb", False):
-            def _ready(_user, _owner=owner):
-                try:
-                    _owner.drgb_ready()
-                except Exception as ex:  # noqa: BLE001 -- must not unwind through the C frame
-                    ready_err.append(ex)
-            ready_cb = _READY_FN(_ready)
+            ready_cb = _c_hook(_READY_FN, owner.drgb_ready, ready_err)
         # ... and may take the per-Gaussian backward in several launches, told after each one which rows are final (include/radegs.h:
         # grad_chunks / grads_ready): its all-reduce of those rows then runs under the launches that follow
         chunks_cb, nchunks = None, 0
         if owner is not None and callable(getattr(owner, "grads_ready", None)) and int(getattr(owner, "grad_chunks", 0) or 0) > 1 \
                 and getattr(owner, "early_grads", False):
             nchunks = int(owner.grad_chunks)
-
-            def _chunk(_user, first, count, _owner=owner):
-                try:
-                    _owner.grads_ready(int(first), int(count))
-                except Exception as ex:  # noqa: BLE001 -- must not unwind through the C frame
-                    ready_err.append(ex)
-            chunks_cb = _GRADS_READY_FN(_chunk)
-        a = RadegsBwdArgs(ctypes.sizeof(RadegsBwdArgs), P, int(degree), M, int(R), W, H, _ptr(bg), _ptr(m3), _ptr(shs), _ptr(col), _ptr(al), _ptr(sc), _ptr(rot),
-                          _ptr(cov), _ptr(vm), _ptr(pm), _ptr(cp), float(scale_modifier), float(tan_fovx), float(tan_fovy),
-                          float(kernel_size), _ptr(rad), _ptr(nm), _ptr(gb) if gb.numel() else None, _ptr(bb) if bb.numel() else None,
-                          _ptr(ib) if ib.numel() else None, _ptr(g[0]), _ptr(g[1]), _ptr(g[2]), _ptr(g[3]), _ptr(g[4]), _ptr(g[5]),
-                          _ptr(g[6]), _ptr(dL_dmeans2D), _ptr(dL_dcolors), _ptr(dL_dopacity), _ptr(dL_dmeans3D), _ptr(dL_dcov3D),
-                          _ptr(dL_dsh) if (M and dL_dsh is not None) else None, _ptr(dL_dscales), _ptr(dL_drotations),
-                          int(bool(require_coord)), int(bool(require_depth)), int(bool(debug)), _ptr(drgb), int(bool(OPACITY_GRAD_INTENDED)),
-                          ctypes.cast(ready_cb, ctypes.c_void_p) if ready_cb is not None else None, None,
-                          nchunks, ctypes.cast(chunks_cb, ctypes.c_void_p) if chunks_cb is not None else None, None,
-                          int(bool(KEEP_ACC)), int(acc_cached is not None))
+            chunks_cb = _c_hook(_GRADS_READY_FN, owner.grads_ready, ready_err)
+        a = _bwd_args(P=P, D=int(degree), M=M, R=int(R), width=W, height=H, background=bg, means3D=m3, shs=shs, colors_precomp=col, alphas=al,
+                      scales=sc, rotations=rot, cov3D_precomp=cov, viewmatrix=vm, projmatrix=pm, cam_pos=cp,
+                      scale_modifier=float(scale_modifier), tan_fovx=float(tan_fovx), tan_fovy=float(tan_fovy), kernel_size=float(kernel_size),
+                      radii=rad, normalmap=nm, geom_buffer=gb if gb.numel() else None, binning_buffer=bb if bb.numel() else None,
+                      image_buffer=ib if ib.numel() else None,
+                      dL_dpix=g[0], dL_dpix_coord=g[1], dL_dpix_mcoord=g[2], dL_dpix_depth=g[3], dL_dpix_mdepth=g[4], dL_dalphas=g[5],
+                      dL_dpix_normal=g[6],
+                      dL_dmean2D=dL_dmeans2D, dL_dcolor=dL_dcolors, dL_dopacity=dL_dopacity, dL_dmean3D=dL_dmeans3D, dL_dcov3D=dL_dcov3D,
+                      dL_dsh=dL_dsh if M else None, dL_dscale=dL_dscales, dL_drot=dL_drotations,
+                      require_coord=int(bool(require_coord)), require_depth=int(bool(require_depth)), debug=int(bool(debug)),
+                      dL_drgb_clamped=drgb, opacity_grad_intended=int(bool(OPACITY_GRAD_INTENDED)), drgb_ready=ready_cb,
+                      grad_chunks=nchunks, grads_ready=chunks_cb, keep_sums=int(bool(KEEP_ACC)), acc_reuse=int(acc_cached is not None))
         if ordered:
             rc = _backward_ordered(L, a, acc, P, R, require_coord, dev, akey)
         else:
@@ -606,29 +628,15 @@ def backward_from_sums(sums, means3D, radii, colors, scales, rotations, scale_mo
     want_drgb = bool(want_drgb) or drgb_ready is not None
     drgb = torch.full((P, 3), float("nan"), **fo) if want_drgb else None
     cb_err = []
-    ready_cb = chunks_cb = None
-    if drgb_ready is not None:
-        def _ready(_user):
-            try:
-                drgb_ready()
-            except Exception as ex:  # noqa: BLE001 -- must not unwind through the C frame
-                cb_err.append(ex)
-        ready_cb = _READY_FN(_ready)
-    if grads_ready is not None:
-        def _chunk(_user, first, count):
-            try:
-                grads_ready(int(first), int(count))
-            except Exception as ex:  # noqa: BLE001 -- must not unwind through the C frame
-                cb_err.append(ex)
-        chunks_cb = _GRADS_READY_FN(_chunk)
-    a = RadegsBwdArgs(ctypes.sizeof(RadegsBwdArgs), P, int(degree), M, 0, int(image_width), int(image_height), None, _ptr(m3), _ptr(shs), _ptr(col), None, _ptr(sc), _ptr(rot),
-                      _ptr(cov), _ptr(vm), _ptr(pm), _ptr(cp), float(scale_modifier), float(tan_fovx), float(tan_fovy), float(kernel_size),
-                      _ptr(rad), None, _ptr(gb), None, None, None, None, None, None, None, None, None,
-                      _ptr(dL_dmeans2D), _ptr(dL_dcolors), _ptr(dL_dopacity), _ptr(dL_dmeans3D), _ptr(dL_dcov3D),
-                      _ptr(dL_dsh) if M else None, _ptr(dL_dscales), _ptr(dL_drotations), int(bool(require_coord)), 0, 0, _ptr(drgb),
-                      int(bool(OPACITY_GRAD_INTENDED)), ctypes.cast(ready_cb, ctypes.c_void_p) if ready_cb is not None else None, None,
-                      int(grad_chunks), ctypes.cast(chunks_cb, ctypes.c_void_p) if chunks_cb is not None else None, None,
-                      int(bool(keep_sums)), 0)
+    ready_cb, chunks_cb = _c_hook(_READY_FN, drgb_ready, cb_err), _c_hook(_GRADS_READY_FN, grads_ready, cb_err)
+    a = _bwd_args(P=P, D=int(degree), M=M, width=int(image_width), height=int(image_height), means3D=m3, shs=shs, colors_precomp=col,
+                  scales=sc, rotations=rot, cov3D_precomp=cov, viewmatrix=vm, projmatrix=pm, cam_pos=cp,
+                  scale_modifier=float(scale_modifier), tan_fovx=float(tan_fovx), tan_fovy=float(tan_fovy), kernel_size=float(kernel_size),
+                  radii=rad, geom_buffer=gb,
+                  dL_dmean2D=dL_dmeans2D, dL_dcolor=dL_dcolors, dL_dopacity=dL_dopacity, dL_dmean3D=dL_dmeans3D, dL_dcov3D=dL_dcov3D,
+                  dL_dsh=dL_dsh if M else None, dL_dscale=dL_dscales, dL_drot=dL_drotations, require_coord=int(bool(require_coord)),
+                  dL_drgb_clamped=drgb, opacity_grad_intended=int(bool(OPACITY_GRAD_INTENDED)), drgb_ready=ready_cb,
+                  grad_chunks=int(grad_chunks), grads_ready=chunks_cb, keep_sums=int(bool(keep_sums)))
     with torch.cuda.device(dev):
         rc = L.radegs_backward_from_sums(ctypes.byref(a), _ptr(sm), _stream(dev))
     if cb_err:

@@ -2,8 +2,8 @@
 
     python scripts/compare_kernel_disasm.py OLD.so NEW.so
 
-For every gfx950 kernel symbol of OLD: is it in NEW, and are the instruction streams (`llvm-objdump -d` with addresses, encodings and the zero
-padding behind a kernel stripped, so a kernel that merely moved inside its code object compares equal) the same?  Kernels only NEW has are listed.  Exit status 1
+For every gfx950 kernel symbol of OLD: is it in NEW, and are the instruction streams (`llvm-objdump -d` with addresses, encodings and the zero or
+s_nop padding behind a kernel stripped, so a kernel that merely moved inside its code object compares equal) the same?  Kernels only NEW has are listed.  Exit status 1
 when a kernel of OLD is missing from NEW or differs.
 """
 import os
@@ -43,6 +43,9 @@ def kernels_of(lib):
                         out[cur] = []
                 elif cur and line.strip() and line.strip() != "...":   # "...": zero padding up to the next symbol's alignment
                     out[cur].append(re.sub(r"\s*//.*$", "", line).strip())   # the trailing comment is the address
+        for ins in out.values():   # the padding behind a kernel can also be s_nop up to the next symbol's alignment: not part of the kernel
+            while len(ins) > 1 and ins[-1] == "s_nop 0" and ins[-2] in ("s_nop 0", "s_endpgm"):
+                ins.pop()
         return out
     finally:
         shutil.rmtree(tmp, ignore_errors=True)

@@ -1,5 +1,5 @@
 """Scenes and packers for the direct tests of the per-Gaussian kernels (preprocess_fwd_kernel / preprocess_bwd_kernel,
-csrc/radegs_kernels.hip): test infrastructure, no GPU.
+csrc/rg_per_gaussian.inc): test infrastructure, no GPU.
 
 Builders return a Case: the Scene, what the call takes besides it (precomputed colours / covariance, scale_modifier), one class name
 per row (for failure messages) and -- after `prepare()` -- the oracle's forward plus the class counts computed FROM THE ORACLE'S OWN
@@ -347,7 +347,7 @@ def assert_fields(pairs, rows, cls, what):
 
 
 # The slab of preprocess_bwd_kernel / sh_grad_from_views_kernel, restated: word e of a block's contiguous [nrows][rowf] slab lives at LDS word
-# g * (rowf + 1) + c with g = mulhi(e, ceil(2^32 / rowf)) standing in for e // rowf (csrc/radegs_kernels.hip::slab_copy), `threads` words per step.
+# g * (rowf + 1) + c with g = mulhi(e, ceil(2^32 / rowf)) standing in for e // rowf (csrc/rg_per_gaussian.inc::SlabMap), `threads` words per step.
 def slab_positions(nrows, rowf, threads=128, tail=True):
     """-> (e, LDS word) for every word the copy touches; tail=False: the copy of a block that ignores a short last block (for the mutation check)"""
     n = (nrows if tail else threads) * rowf

@@ -17,8 +17,8 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GRADS = ("dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dscales", "dL_drotations")
-# What preprocess_bwd_kernel's `acc_raw == 2` branch (RadegsBwdArgs::keep_sums) does to a record: it stores float4 2 and 3 of it again, i.e.
-# slots 8..15.  Slot 8 (r2.x), slot 11 (the abs-gradient sum, passed through) and slot 15 (acc.dop) go back as they came; slots 9 and 10
+# What preprocess_bwd_kernel does to a record it keeps (RadegsBwdArgs::keep_sums, AccRecord::store_sums): it stores float4 2 and 3 of it again, i.e.
+# slots 8..15.  Slot 8, slot 11 (the abs-gradient sum, passed through) and slot 15 (the opacity sum) go back as they came; slots 9 and 10
 # become the reference's mean2D sums (the moments times the conic, plus the plane terms) and slots 12..14 the raw second moments times
 # -0.5f.  So LAST_ACC must equal the fixed-order sum BIT FOR BIT in every slot but 9, 10, 12, 13, 14 ...
 REWRITTEN = (9, 10, 12, 13, 14)

@@ -1,11 +1,13 @@
-"""The per-Gaussian kernels looked at directly, bit for bit (csrc/radegs_kernels.hip: preprocess_fwd_kernel, preprocess_bwd_kernel,
+"""The per-Gaussian kernels looked at directly, bit for bit (csrc/rg_per_gaussian.inc: preprocess_fwd_kernel, preprocess_bwd_kernel,
 drgb_clamped_kernel, sh_grad_from_views_kernel).
 
 a  every word the forward leaves per Gaussian (splat_a, splat_b, clamped, rect, depth_key, radii, tiles_touched) against the oracle's arrays;
 b  the backward over the ORACLE'S OWN per-Gaussian sums against the oracle's gradients, both opacity modes;
 c  the backward over sums the oracle never produces against the host build of the same headers;
 d  the launch modes of the backward (grad_chunks, the separate dL_drgb_clamped kernel) against one plain launch;
-e  sh_grad_from_views against a float64 restatement of the SH basis.
+e  sh_grad_from_views against a float64 restatement of the SH basis;
+f  the ordered backward with and without keep_sums: the write-back of the records does not change what is returned;
+g  the records a keep_sums backward leaves, as reference sums through backward_from_sums, against what that backward returned.
 
 Bit equality is expected, not hoped for: the product is built with -ffp-contract=off, IEEE divide and square root, and the three headers call
 nothing from a library but sqrtf and ceilf (the one exception, skip_threshold's logf, fills slot 6 of splat_a and is compared with the same
@@ -220,6 +222,82 @@ def test_launch_modes_return_the_same_bits(P):
 
 
 GRADS_ORDER = ("dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dscales", "dL_drotations")
+
+
+# ============================================================================ f, g. the three kinds of accumulator record, tied together
+# preprocess_bwd_kernel reads a record as one of three kinds (csrc/rg_per_gaussian.inc::RecordKind): raw moments (every blend backward), the
+# reference's final sums (backward_from_sums), blend sums with the constant factors pending (no blend at all).  The ordered backward
+# (RADEGS_DETERMINISTIC=1) makes the raw records bit-reproducible, so the kinds can be held against each other bit for bit.
+KIND_SCENES = [257, 513, 3001]     # tail_scene(257): degree 2, the word-loop slab; tail_scene(513); _mode_case(3001): coord map, kernel_size 0.1
+
+
+def _ordered_case(P, monkeypatch):
+    """-> (case, HipRun after its forward, cotangents), with the ordered backward switched on"""
+    monkeypatch.setenv("RADEGS_DETERMINISTIC", "1")
+    c = _mode_case(P)
+    h = _run(c)
+    visible = int((h.state[8] > 0).sum())
+    assert h.state[0] > 0 and visible > P // 2, "R = %d, %d of %d rows visible" % (h.state[0], visible, P)
+    return c, h, upstream_grads(c.s, 3)
+
+
+def _same_grads(got, want, c, what):
+    pairs = {k: (got[k].reshape(c.P, -1), want[k].reshape(c.P, -1)) for k in GRADS}
+    assert len(pairs) == 8
+    for k, (a, b) in pairs.items():
+        print("%s: %s: %d of %d words differ" % (what, k, int((a.view(np.uint32) != b.view(np.uint32)).sum()), a.size))
+    pg.assert_fields(pairs, np.ones(c.P, bool), c.cls, what)
+
+
+@pytest.mark.parametrize("P", KIND_SCENES)
+def test_keeping_the_sums_does_not_change_what_is_returned(P, monkeypatch):
+    """RadegsBwdArgs::keep_sums makes the kernel write every visible record back in the reference's form; the eight gradients of the launch
+    must not notice (same forward state, same fixed-order sums: bit for bit)."""
+    from test_gpu_deterministic import _backward
+    c, h, g = _ordered_case(P, monkeypatch)
+    plain, none, _ = _backward(h, h.state, g, keep=False)
+    kept, acc, _ = _backward(h, h.state, g, keep=True)
+    assert none is None and acc[h.state[8].cpu().numpy() > 0].any()
+    _same_grads(kept, plain, c, "P=%d, KEEP_ACC on against off" % P)
+
+
+def reference_form(acc, s):
+    """LAST_ACC of a backward with keep_sums -- the record in the reference's form WITHOUT the constant factors (include/radegs.h) -- with
+    those factors applied in float32 exactly as preprocess_bwd_kernel applies them to a record whose factors are pending: 1/focal on the
+    plane sums (slots 4, 5 and, with the coord map, 19..24 alternating), (0.5f * W) and (0.5f * H) on the mean2D sums (slots 9, 10); focal
+    as rg_launch.inc::make_cam computes it."""
+    f32 = np.float32
+    focal_x, focal_y = f32(s.W) / (f32(2.0) * f32(s.tanfovx)), f32(s.H) / (f32(2.0) * f32(s.tanfovy))
+    ifx, ify = f32(1.0) / focal_x, f32(1.0) / focal_y
+    a = acc.astype(np.float32).copy()
+    a[:, 4] *= ifx
+    a[:, 5] *= ify
+    if a.shape[1] == 32:
+        a[:, 19:25:2] *= ifx
+        a[:, 20:25:2] *= ify
+    a[:, 9] *= f32(0.5) * f32(s.W)
+    a[:, 10] *= f32(0.5) * f32(s.H)
+    assert a.dtype == np.float32
+    return a
+
+
+@pytest.mark.parametrize("P", KIND_SCENES)
+def test_raw_records_and_reference_sums_return_the_same_bits(P, monkeypatch):
+    """An ordered backward with keep_sums returns its gradients from RAW records and leaves them behind in the reference's form; those, with
+    the constant factors applied (reference_form), are records of the REFERENCE kind.  backward_from_sums over them must return what the
+    ordered backward returned, in both opacity modes: the conversion of a raw record (rg_preprocess_bwd.h: the moments times the conic, the
+    -0.5f on the second moments, W/2 and H/2 afterwards) and the pending 1/focal factors are then the only difference between the two
+    paths, and each is one float32 operation on either side.
+    Criterion from the parent of the commit that added this test (same scenes, same GPU): all eight gradients bit-identical in both modes,
+    0 of every tensor's words differing -- so bit identity is what is asserted."""
+    import diff_gaussian_rasterization._C as C
+    from test_gpu_deterministic import _backward
+    c, h, g = _ordered_case(P, monkeypatch)
+    for intended in (False, True):
+        monkeypatch.setattr(C, "OPACITY_GRAD_INTENDED", intended)
+        want, acc, _ = _backward(h, h.state, g, keep=True)
+        got = backward_from_sums(h, reference_form(acc, c.s))
+        _same_grads(got, want, c, "P=%d, opacity_grad_intended=%s, reference kind against raw kind" % (P, intended))
 
 
 # ============================================================================================================ e. sh_grad_from_views
