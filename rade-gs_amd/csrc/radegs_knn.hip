@@ -139,7 +139,9 @@ __global__ void __launch_bounds__(64) knn3_kernel(int P, int nb, const float* __
       if (want && k != ic) update3(q, best);
     }
   }
-  if (live) out[order[i]] = (best[0] + best[1] + best[2]) / 3.0f;
+  // fewer than three neighbours exist: +inf, the mean over a missing distance, as oracle/knn_oracle.py defines it.  A deliberate departure
+  // from the published library's arithmetic, where the unfilled slot keeps FLT_MAX and (d0 + d1 + FLT_MAX) / 3 stays finite at P = 3.
+  if (live) out[order[i]] = P < 4 ? INFINITY : (best[0] + best[1] + best[2]) / 3.0f;
 }
 
 }  // namespace rgk

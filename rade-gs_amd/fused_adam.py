@@ -44,7 +44,7 @@ class Adam(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         L = _lib()
-        batches = {}  # (device, betas, eps) -> list of RadegsAdamTensor (+ keep-alive refs)
+        todo = []
         for group in self.param_groups:
             for p in group["params"]:
                 if p.grad is None:
@@ -59,14 +59,23 @@ class Adam(torch.optim.Optimizer):
                     st["step"] = torch.tensor(0.0, dtype=torch.float32)
                     st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["step"] += 1
-                g = p.grad.contiguous()
-                if not st["exp_avg"].is_contiguous() or not st["exp_avg_sq"].is_contiguous():
-                    st["exp_avg"], st["exp_avg_sq"] = st["exp_avg"].contiguous(), st["exp_avg_sq"].contiguous()
-                key = (p.device, tuple(group["betas"]), float(group["eps"]))
-                batches.setdefault(key, []).append((RadegsAdamTensor(p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(),
-                                                                     st["exp_avg_sq"].data_ptr(), p.numel(), float(group["lr"]),
-                                                                     float(st["step"])), g))
+                # the kernel walks all four arrays with the parameter's numel: state surgery that left a moment (or a gradient) of
+                # another size, type or device would make it read and write out of bounds
+                for name, t in (("grad", p.grad), ("exp_avg", st["exp_avg"]), ("exp_avg_sq", st["exp_avg_sq"])):
+                    if t.numel() != p.numel() or t.dtype != torch.float32 or t.device != p.device:
+                        raise RuntimeError(f"fused Adam: `{name}` is {t.dtype} with {t.numel()} elements on {t.device}; the parameter is "
+                                           f"float32 with {p.numel()} elements on {p.device}")
+                todo.append((group, p, st))
+        batches = {}  # (device, betas, eps) -> list of RadegsAdamTensor (+ keep-alive refs); no step advanced, nothing launched so far
+        for group, p, st in todo:
+            st["step"] += 1
+            g = p.grad.contiguous()
+            if not st["exp_avg"].is_contiguous() or not st["exp_avg_sq"].is_contiguous():
+                st["exp_avg"], st["exp_avg_sq"] = st["exp_avg"].contiguous(), st["exp_avg_sq"].contiguous()
+            key = (p.device, tuple(group["betas"]), float(group["eps"]))
+            batches.setdefault(key, []).append((RadegsAdamTensor(p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(),
+                                                                 st["exp_avg_sq"].data_ptr(), p.numel(), float(group["lr"]),
+                                                                 float(st["step"])), g))
         for (dev, betas, eps), items in batches.items():
             for i in range(0, len(items), MAX_TENSORS):
                 chunk = items[i:i + MAX_TENSORS]

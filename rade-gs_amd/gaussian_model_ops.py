@@ -65,11 +65,14 @@ class _ScalingOpacity3DFilter(torch.autograd.Function):
         if rc != 0:
             raise RuntimeError(f"radegs_filter3d_forward failed ({rc})")
         ctx.save_for_backward(sc, op, f3)
+        ctx.set_materialize_grads(False)     # an output that nothing downstream uses arrives as None, not as a tensor of zeros
         return scales, opacity
 
     @staticmethod
     def backward(ctx, g_scales, g_opacity):
         sc, op, f3 = ctx.saved_tensors
+        if g_scales is None and g_opacity is None:
+            return None, None, None
         gs = None if g_scales is None else g_scales.contiguous()
         go = None if g_opacity is None else g_opacity.contiguous()
         g_sc, g_op = torch.empty_like(sc), torch.empty_like(op)
@@ -91,7 +94,10 @@ def scaling_n_opacity_with_3D_filter(scaling_raw, opacity_raw, filter_3D):
 def compute_3D_filter(xyz, cameras):
     """GaussianModel.compute_3D_filter (scene/gaussian_model.py:179-232): returns the (P,1) `filter_3D` buffer for the
     Gaussian centres `xyz` and an iterable of cameras (attributes R, T, image_width, image_height, FoVx, FoVy), all cameras
-    in one kernel instead of ~15 torch kernels per camera."""
+    in one kernel instead of ~15 torch kernels per camera.
+
+    A point that no camera sees takes the largest distance over the points that are seen, as upstream.  When no camera sees ANY point,
+    upstream raises (it takes `.max()` of an empty selection); this returns a filter of exactly 0 for every point instead."""
     import math
 
     import numpy as np
