@@ -604,6 +604,66 @@ int radegs_appearance_head_backward(int orig_height, int orig_width, int feat_he
                                     size_t scratch_bytes, float* grad_feat, float* grad_image, float* grad_W2, float* grad_b2, float* grad_W3,
                                     float* grad_b3, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * TSDF fusion: mesh_extract.py:51-105, the DTU route from depth maps to recon.ply, which upstream
+ * hands to Open3D's VoxelBlockGrid on the CPU.  Conventions as above: device pointers unless marked (host), 0 or a
+ * negative RADEGS_ERR_*, work enqueued on `stream`, nothing read back, sizes of 0 legal.  All device arithmetic is
+ * float32, one rounding per operation, products before sums in the order written here.
+ *
+ * The grid: blocks of 16^3 voxels.  block_size = 16 voxel_size, sdf_trunc = voxel_size trunc_voxel_multiplier (both
+ * rounded to float32 once, on the host).  A block's coordinate is floor(world / block_size) per axis, each in
+ * [-2^20, 2^20); its key is (z + 2^20) << 42 | (y + 2^20) << 21 | (x + 2^20).  The grid is `keys` [n] ascending and
+ * `slots` [n] int: block i's voxels are rows slots[i] of tsdf / weight [capacity][4096] and color
+ * [capacity][4096][3], voxel index (z * 16 + y) * 16 + x.
+ * cam16 (host): fx, fy, cx, cy, then a 3x4 matrix by rows.
+ *
+ * radegs_tsdf_touch: the matrix is camera to world.  For every pixel (4i, 4j), i < H / 4, j < W / 4, with
+ *   d = depth / depth_scale, 0 < d < depth_max: ray ((x - cx) / fx, (y - cy) / fy, 1); t_min = max(d - sdf_trunc, 0),
+ *   t_max = min(d + sdf_trunc, depth_max), step = (t_max - t_min) / 3; the four points ray * (t_min + k step) go to
+ *   the world as ((m0 px + m1 py) + m2 pz) + m3 per row and yield one block each.  Then as radegs_tsdf_unique_plan
+ *   with an empty grid, over 4 (W / 4) (H / 4) items: size the workspace for that.
+ * radegs_tsdf_unique_plan: coords int [n,3].  Sorts the keys (two stable 32-bit passes), marks first occurrences and
+ *   looks them up in the grid's keys.  counts3 (device) = {distinct blocks, those not in the grid, 1 if a
+ *   coordinate lay outside the 21 bits -- such an item yields no block: refuse the call}.  workspace:
+ *   radegs_tsdf_unique_bytes(n), 16-byte aligned, untouched until the calls below have run.
+ * radegs_tsdf_unique_emit: coords_out int [n_unique,3], ascending by key; n_unique as read back.
+ * radegs_tsdf_insert_apply: new_keys / new_slots [ngrid + n_new]: the grid with the new blocks merged in, the new
+ *   block of rank r (in key order) in slot ngrid + r -- the caller provides capacity >= ngrid + n_new and
+ *   zero-fills those rows.  active_slots [n_unique], active_coords [n_unique,3]: the listed blocks.
+ * radegs_tsdf_integrate: the matrix is world to camera with its rotation part multiplied by voxel_size (in float64,
+ *   before the conversion).  One workgroup per listed block.  Per voxel X = 16 b + v (integers, as float32):
+ *   p = ((m0 X.x + m1 X.y) + m2 X.z) + m3 per row; skipped unless p.z > 0; u = (fx p.x) / p.z + cx, v likewise;
+ *   ui = roundf(u), vi = roundf(v) (half away from zero); skipped unless 0 <= ui < W, 0 <= vi < H;
+ *   d = depth[vi][ui] / depth_scale, sdf = d - p.z; skipped unless d > 0, d <= depth_max, sdf >= -sdf_trunc;
+ *   s = min(sdf, sdf_trunc) / sdf_trunc; inv = 1 / (w + 1); tsdf = (w tsdf + s) inv; color = (w color + c) inv per
+ *   channel (color [H][W][3]); w = w + 1.  color and block_color are both given or both null.
+ * radegs_tsdf_extract_plan / _emit: marching cubes over the cells whose eight corners (looked up across block
+ *   borders) all have weight > weight_threshold; case bit i = corner i negative (csrc/rg_mc_tables.h, generated by
+ *   scripts/make_mc_tables.py).  A voxel owns the edges leaving it along +x, +y, +z; an owned edge carries a vertex
+ *   iff a valid cell cuts it: ratio = (0 - tsdf_o) / (tsdf_e - tsdf_o), position voxel_size (X + ratio axis),
+ *   colour c_o + ratio (c_e - c_o).  Vertices in (key, voxel, axis) order, faces in (key, voxel of the cell's lowest
+ *   corner, table) order.  counts2 (device) = {V, F}; workspace: radegs_tsdf_extract_bytes(n), 16-byte aligned,
+ *   untouched until emit has run.  At most 2^19 - 1 blocks.  vertices [V,3], faces [F,3], colors [V,3] or null.
+ * --------------------------------------------------------------------------------------------------------------- */
+size_t radegs_tsdf_unique_bytes(long long n);
+int radegs_tsdf_touch(int W, int H, const float* depth /* [H,W] */, const float* cam16, float depth_scale, float depth_max, float sdf_trunc,
+                      float block_size, void* workspace, size_t workspace_bytes, long long* counts3, void* stream);
+int radegs_tsdf_unique_plan(long long n, const int* coords /* [n,3] */, long long ngrid, const unsigned long long* grid_keys, void* workspace,
+                            size_t workspace_bytes, long long* counts3, void* stream);
+int radegs_tsdf_unique_emit(long long n, const void* workspace, long long n_unique, int* coords_out /* [n_unique,3] */, void* stream);
+int radegs_tsdf_insert_apply(long long n, const void* workspace, long long ngrid, const unsigned long long* grid_keys, const int* grid_slots,
+                             long long n_unique, long long n_new, unsigned long long* new_keys, int* new_slots, int* active_slots,
+                             int* active_coords, void* stream);
+int radegs_tsdf_integrate(long long n_active, const int* active_slots, const int* active_coords, long long capacity, int W, int H, const float* depth,
+                          const float* color, const float* cam16, float depth_scale, float depth_max, float sdf_trunc, float* tsdf, float* weight,
+                          float* block_color, void* stream);
+size_t radegs_tsdf_extract_bytes(long long n);
+int radegs_tsdf_extract_plan(long long n, const unsigned long long* keys, const int* slots, const float* tsdf, const float* weight,
+                             float weight_threshold, void* workspace, size_t workspace_bytes, long long* counts2, void* stream);
+int radegs_tsdf_extract_emit(long long n, const unsigned long long* keys, const int* slots, const float* tsdf, const float* block_color,
+                             float voxel_size, const void* workspace, long long V, long long F, float* vertices, long long* faces, float* colors,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -100,7 +100,10 @@ EXPORTED_SYMBOLS = ("radegs_forward", "radegs_backward", "radegs_backward_ordere
                     "radegs_mesheval_sample_bytes", "radegs_mesheval_sample_count", "radegs_mesheval_sample_emit", "radegs_mesheval_grid_bytes",
                     "radegs_mesheval_grid_build", "radegs_mesheval_thin_rounds", "radegs_mesheval_nearest", "radegs_mesheval_sum_bytes",
                     "radegs_mesheval_sum_below", "radegs_mesheval_obs_mask", "radegs_mesheval_above_plane", "radegs_mesheval_dilate",
-                    "radegs_mesheval_cull_vertices", "radegs_tetmesh_filter_plan_flags")
+                    "radegs_mesheval_cull_vertices", "radegs_tetmesh_filter_plan_flags",
+                    # TSDF fusion (bound in tsdf.py)
+                    "radegs_tsdf_unique_bytes", "radegs_tsdf_touch", "radegs_tsdf_unique_plan", "radegs_tsdf_unique_emit", "radegs_tsdf_insert_apply",
+                    "radegs_tsdf_integrate", "radegs_tsdf_extract_bytes", "radegs_tsdf_extract_plan", "radegs_tsdf_extract_emit")
 
 _lib = None
 # test hook: when True, the per-Gaussian accumulation scratch of the last backward is kept in LAST_ACC
