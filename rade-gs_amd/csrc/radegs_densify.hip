@@ -15,6 +15,7 @@
 
 #include "../../include/radegs.h"
 #include "rg_prims.h"
+#include "rg_workspace.h"
 
 namespace rgd {
 
@@ -196,20 +197,19 @@ __global__ void __launch_bounds__(256) apply_kernel(const Table t) {
     if (!fast[u] && e0[u] < n) apply_words(t, in, out, W, kind, n, e0[u], r0[u], c0[u], code0[u], code3[u] != 0xFFFFFFFFu);
 }
 
-struct Workspace { uint32_t *flags, *incl, *src_of; void* scan_temp; size_t scan_bytes; };
+struct Workspace { uint32_t *flags, *incl, *src_of; void* scan_temp; size_t scan_bytes, bytes; };
 
-static size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-static size_t carve(int P, void* base, Workspace* w) {
-  const size_t n = (size_t)P, scan_bytes = rg::scan_temp_bytes(6 * n);
-  size_t off = 0;
-  char* b = static_cast<char*>(base);
-  auto take = [&](size_t bytes) { char* p = b ? b + off : nullptr; off += align256(bytes); return p; };
-  char* src_of = take(2 * n * 4);   // first: radegs_densify_apply finds it at the start.  At most 2 P rows come out (clone and split exclude each other)
-  char* flags = take(6 * n * 4);
-  char* incl = take(6 * n * 4);
-  char* scan = take(scan_bytes);
-  if (w) *w = Workspace{reinterpret_cast<uint32_t*>(flags), reinterpret_cast<uint32_t*>(incl), reinterpret_cast<uint32_t*>(src_of), scan, scan_bytes};
-  return off;
+static Workspace carve(int P, void* base) {
+  const size_t n = (size_t)P;
+  rg::Carver c(base);
+  Workspace v;
+  v.scan_bytes = rg::scan_temp_bytes(6 * n);
+  v.src_of = c.take<uint32_t>(2 * n);   // first: radegs_densify_apply finds it at the start.  At most 2 P rows come out (clone and split exclude each other)
+  v.flags = c.take<uint32_t>(6 * n);
+  v.incl = c.take<uint32_t>(6 * n);
+  v.scan_temp = c.take<char>(v.scan_bytes);
+  v.bytes = c.off;
+  return v;
 }
 
 }  // namespace rgd
@@ -221,9 +221,9 @@ int radegs_densify_stats(int P, const float* grad_means2D, const int* radii, con
   if (P < 0) return RADEGS_ERR_INVALID_ARG;
   if (P == 0) return 0;
   if (!grad_means2D || (!radii && !visible) || !accum || !accum_abs || !accum_abs_max || !denom) return RADEGS_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(rgd::stats_kernel<false>, dim3((P + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), P, grad_means2D, radii, visible,
+  hipLaunchKernelGGL(rgd::stats_kernel<false>, dim3(rg::blocks_of((size_t)P)), dim3(256), 0, static_cast<hipStream_t>(stream), P, grad_means2D, radii, visible,
                      accum, accum_abs, accum_abs_max, denom, max_radii2D);
-  return hipGetLastError() == hipSuccess ? 0 : RADEGS_ERR_HIP;
+  return rg::launch_status();
 }
 
 int radegs_densify_stats_reduced(int P, const float* densify_stats, const int* radii_max, float* accum, float* accum_abs, float* accum_abs_max,
@@ -231,12 +231,12 @@ int radegs_densify_stats_reduced(int P, const float* densify_stats, const int* r
   if (P < 0) return RADEGS_ERR_INVALID_ARG;
   if (P == 0) return 0;
   if (!densify_stats || !accum || !accum_abs || !accum_abs_max || !denom) return RADEGS_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(rgd::stats_kernel<true>, dim3((P + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), P, densify_stats, radii_max,
+  hipLaunchKernelGGL(rgd::stats_kernel<true>, dim3(rg::blocks_of((size_t)P)), dim3(256), 0, static_cast<hipStream_t>(stream), P, densify_stats, radii_max,
                      static_cast<const uint8_t*>(nullptr), accum, accum_abs, accum_abs_max, denom, max_radii2D);
-  return hipGetLastError() == hipSuccess ? 0 : RADEGS_ERR_HIP;
+  return rg::launch_status();
 }
 
-size_t radegs_densify_plan_bytes(int P) { return P <= 0 ? 0 : rgd::carve(P, nullptr, nullptr); }
+size_t radegs_densify_plan_bytes(int P) { return P <= 0 ? 0 : rgd::carve(P, nullptr).bytes; }
 
 int radegs_densify_plan(int P, const float* accum, const float* accum_abs, const float* denom, const float* scaling_raw, const float* opacity_raw,
                         float max_grad, const float* abs_threshold, float dense_threshold, float min_opacity, int prune_big, float big_threshold,
@@ -245,15 +245,14 @@ int radegs_densify_plan(int P, const float* accum, const float* accum_abs, const
   hipStream_t s = static_cast<hipStream_t>(stream_v);
   if (P == 0) return hipMemsetAsync(counts4, 0, 4 * sizeof(int), s) == hipSuccess ? 0 : RADEGS_ERR_HIP;
   if (!accum || !accum_abs || !denom || !scaling_raw || !opacity_raw || !abs_threshold || !workspace ||
-      workspace_bytes < radegs_densify_plan_bytes(P) || (reinterpret_cast<uintptr_t>(workspace) & 15))
+      workspace_bytes < radegs_densify_plan_bytes(P) || !rg::aligned16(workspace))
     return RADEGS_ERR_INVALID_ARG;
-  rgd::Workspace w;
-  rgd::carve(P, workspace, &w);
-  hipLaunchKernelGGL(rgd::decide_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, accum, accum_abs, denom, scaling_raw, opacity_raw, max_grad,
+  const rgd::Workspace w = rgd::carve(P, workspace);
+  hipLaunchKernelGGL(rgd::decide_kernel, dim3(rg::blocks_of((size_t)P)), dim3(256), 0, s, P, accum, accum_abs, denom, scaling_raw, opacity_raw, max_grad,
                      abs_threshold, dense_threshold, min_opacity, prune_big, big_threshold, w.flags);
   if (rg::inclusive_scan_gather_u32(w.scan_temp, w.scan_bytes, w.flags, nullptr, w.incl, 6 * (size_t)P, s) != hipSuccess) return RADEGS_ERR_HIP;
-  hipLaunchKernelGGL(rgd::index_kernel, dim3((unsigned)((4 * (size_t)P + 255) / 256)), dim3(256), 0, s, (uint32_t)P, w.flags, w.incl, w.src_of, counts4);
-  return hipGetLastError() == hipSuccess ? 0 : RADEGS_ERR_HIP;
+  hipLaunchKernelGGL(rgd::index_kernel, dim3(rg::blocks_of(4 * (size_t)P)), dim3(256), 0, s, (uint32_t)P, w.flags, w.incl, w.src_of, counts4);
+  return rg::launch_status();
 }
 
 int radegs_densify_apply(int P, int P_out, int rest_floats, const RadegsDensifyTensors* tensors, const float* unit_normals, const void* workspace,
@@ -283,7 +282,7 @@ int radegs_densify_apply(int P, int P_out, int rest_floats, const RadegsDensifyT
   t.scaling = tensors->in[4]; t.rotation = tensors->in[5]; t.z = unit_normals;
   t.src_of = static_cast<const uint32_t*>(workspace);
   hipLaunchKernelGGL(rgd::apply_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), t);
-  return hipGetLastError() == hipSuccess ? 0 : RADEGS_ERR_HIP;
+  return rg::launch_status();
 }
 
 }  // extern "C"

@@ -14,6 +14,7 @@
 
 #include "../../include/radegs.h"
 #include "rg_prims.h"
+#include "rg_workspace.h"
 
 namespace rgk {
 
@@ -144,38 +145,49 @@ __global__ void __launch_bounds__(64) knn3_kernel(int P, int nb, const float* __
   if (live) out[order[i]] = P < 4 ? INFINITY : (best[0] + best[1] + best[2]) / 3.0f;
 }
 
+struct Workspace {
+  uint32_t *mm, *codes, *codes_sorted, *order;
+  float *sorted, *boxes;
+  void* sort_temp;
+  size_t sort_bytes, nb, bytes;
+};
+static Workspace carve(int P, void* base) {
+  const size_t n = (size_t)P;
+  rg::Carver c(base);
+  Workspace v;
+  v.nb = (n + kBox - 1) / kBox;
+  v.sort_bytes = rg::sort_temp_bytes(n);
+  v.mm = c.take<uint32_t>(6);   // min xyz, max xyz
+  v.codes = c.take<uint32_t>(n);
+  v.codes_sorted = c.take<uint32_t>(n);
+  v.order = c.take<uint32_t>(n);
+  v.sorted = c.take<float>(3 * n);
+  v.boxes = c.take<float>(6 * v.nb);
+  v.sort_temp = c.take<char>(v.sort_bytes);
+  v.bytes = c.off;
+  return v;
+}
+
 }  // namespace rgk
 
 extern "C" {
 
-size_t radegs_knn_scratch_bytes(int P) {
-  const size_t n = (size_t)(P > 0 ? P : 1), nb = (n + rgk::kBox - 1) / rgk::kBox;
-  return 256 /* bounds */ + 4 * (n * 4 + 256) /* codes, sorted codes, order */ + n * 12 + 256 + nb * 24 + 256 + rg::sort_temp_bytes(n) + 1024;
-}
+size_t radegs_knn_scratch_bytes(int P) { return rgk::carve(P > 0 ? P : 1, nullptr).bytes; }
 
 int radegs_knn_mean_dist2(int P, const float* points, void* scratch, float* out, void* stream_v) {
   if (P < 0) return RADEGS_ERR_INVALID_ARG;
   if (P == 0) return 0;
   if (!points || !scratch || !out) return RADEGS_ERR_INVALID_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream_v);
-  char* p = static_cast<char*>(scratch);
-  auto take = [&](size_t bytes) { char* r = p; p += (bytes + 255) & ~size_t(255); return r; };
-  const size_t n = (size_t)P, nb = (n + rgk::kBox - 1) / rgk::kBox;
-  uint32_t* mm = reinterpret_cast<uint32_t*>(take(6 * 4));
-  uint32_t* codes = reinterpret_cast<uint32_t*>(take(n * 4));
-  uint32_t* codes_sorted = reinterpret_cast<uint32_t*>(take(n * 4));
-  uint32_t* order = reinterpret_cast<uint32_t*>(take(n * 4));
-  float* sorted = reinterpret_cast<float*>(take(n * 12));
-  float* boxes = reinterpret_cast<float*>(take(nb * 24));
-  char* stemp = take(rg::sort_temp_bytes(n));
+  const rgk::Workspace w = rgk::carve(P, scratch);
   const uint32_t init[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
-  if (hipMemcpyAsync(mm, init, sizeof(init), hipMemcpyHostToDevice, s) != hipSuccess) return RADEGS_ERR_HIP;
-  hipLaunchKernelGGL(rgk::bounds_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, points, mm);
-  hipLaunchKernelGGL(rgk::morton_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, points, mm, codes);
-  if (rg::radix_sort_pairs_u32(stemp, rg::sort_temp_bytes(n), codes, codes_sorted, nullptr, order, n, 30, s) != hipSuccess) return RADEGS_ERR_HIP;
-  hipLaunchKernelGGL(rgk::gather_boxes_kernel, dim3((unsigned)nb), dim3(256), 0, s, P, points, order, sorted, boxes);
-  hipLaunchKernelGGL(rgk::knn3_kernel, dim3((P + 63) / 64), dim3(64), 0, s, P, (int)nb, sorted, boxes, order, out);
-  return hipGetLastError() == hipSuccess ? 0 : RADEGS_ERR_HIP;
+  if (hipMemcpyAsync(w.mm, init, sizeof(init), hipMemcpyHostToDevice, s) != hipSuccess) return RADEGS_ERR_HIP;
+  hipLaunchKernelGGL(rgk::bounds_kernel, dim3(rg::blocks_of((size_t)P)), dim3(256), 0, s, P, points, w.mm);
+  hipLaunchKernelGGL(rgk::morton_kernel, dim3(rg::blocks_of((size_t)P)), dim3(256), 0, s, P, points, w.mm, w.codes);
+  if (rg::radix_sort_pairs_u32(w.sort_temp, w.sort_bytes, w.codes, w.codes_sorted, nullptr, w.order, (size_t)P, 30, s) != hipSuccess) return RADEGS_ERR_HIP;
+  hipLaunchKernelGGL(rgk::gather_boxes_kernel, dim3((unsigned)w.nb), dim3(256), 0, s, P, points, w.order, w.sorted, w.boxes);
+  hipLaunchKernelGGL(rgk::knn3_kernel, dim3((P + 63) / 64), dim3(64), 0, s, P, (int)w.nb, w.sorted, w.boxes, w.order, out);
+  return rg::launch_status();
 }
 
 }  // extern "C"

@@ -20,16 +20,13 @@
 
 #include "../../include/radegs.h"
 #include "rg_prims.h"
+#include "rg_workspace.h"
 
 namespace rgme {
 
-constexpr unsigned long long kMaxItems = 0xFFFFFFFFull - 65536ull;   // what the u32 sort / scan address
-constexpr double kMaxSubdiv = 30000.0;                               // n1, n2 beyond this: the per-triangle count would leave 32 bits
+using rg::kMaxItems;
+constexpr double kMaxSubdiv = 30000.0;   // n1, n2 beyond this: the per-triangle count would leave 32 bits
 constexpr int kSumBlocks = 1024;
-
-static size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-static unsigned blocks_of(size_t n) { return (unsigned)((n + 255) / 256); }
-static int last() { return hipGetLastError() == hipSuccess ? 0 : RADEGS_ERR_HIP; }
 
 // ---------------------------------------------------------------- triangle sampling ----------------------------------------------------------------
 struct Tri {
@@ -128,15 +125,19 @@ __global__ void __launch_bounds__(256) tri_emit_kernel(long long V, long long F,
   }
 }
 
-static size_t sample_carve(long long F, void* base, uint32_t** incl, void** temp, size_t* temp_bytes) {
-  const size_t tb = rg::scan_temp_bytes((size_t)F);
-  size_t off = 0;
-  char* b = static_cast<char*>(base);
-  auto take = [&](size_t bytes) { char* p = b ? b + off : nullptr; off += align256(bytes); return p; };
-  char* i = take((size_t)F * 4);
-  char* t = take(tb);
-  if (incl) { *incl = reinterpret_cast<uint32_t*>(i); *temp = t; *temp_bytes = tb; }
-  return off;
+struct SampleView {
+  uint32_t* incl;
+  void* temp;
+  size_t temp_bytes, bytes;
+};
+static SampleView sample_carve(long long F, void* base) {
+  rg::Carver c(base);
+  SampleView v;
+  v.temp_bytes = rg::scan_temp_bytes((size_t)F);
+  v.incl = c.take<uint32_t>((size_t)F);
+  v.temp = c.take<char>(v.temp_bytes);
+  v.bytes = c.off;
+  return v;
 }
 
 // -------------------------------------------------------------------- the grid --------------------------------------------------------------------
@@ -167,34 +168,24 @@ __global__ void __launch_bounds__(256) reorder_kernel(uint32_t N, const double* 
   for (int k = 0; k < 3; k++) sorted[3 * (size_t)s + k] = pts[3 * i + k];
 }
 
-__device__ __forceinline__ uint32_t lower_bound(const uint32_t* __restrict__ keys, uint32_t N, uint32_t key) {
-  uint32_t lo = 0, hi = N;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (keys[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
 struct GridView {
   uint32_t *keys, *perm, *keys_in;
   double* pts;
   void* temp;
-  size_t temp_bytes;
+  size_t temp_bytes, bytes;
 };
-static size_t grid_carve(long long N, void* base, GridView* w) {
-  const size_t n = (size_t)N, tb = rg::sort_temp_bytes(n);
-  size_t off = 0;
-  char* b = static_cast<char*>(base);
-  auto take = [&](size_t bytes) { char* p = b ? b + off : nullptr; off += align256(bytes); return p; };
-  char* keys = take(n * 4);
-  char* perm = take(n * 4);
-  char* pts = take(n * 24);
-  char* keys_in = take(n * 4);
-  char* temp = take(tb);
-  auto u = [](char* p) { return reinterpret_cast<uint32_t*>(p); };
-  if (w) *w = GridView{u(keys), u(perm), u(keys_in), reinterpret_cast<double*>(pts), temp, tb};
-  return off;
+static GridView grid_carve(long long N, void* base) {
+  const size_t n = (size_t)N;
+  rg::Carver c(base);
+  GridView v;
+  v.temp_bytes = rg::sort_temp_bytes(n);
+  v.keys = c.take<uint32_t>(n);
+  v.perm = c.take<uint32_t>(n);
+  v.pts = c.take<double>(3 * n);
+  v.keys_in = c.take<uint32_t>(n);
+  v.temp = c.take<char>(v.temp_bytes);
+  v.bytes = c.off;
+  return v;
 }
 static bool grid_args_ok(long long N, const double* origin3, double cell) {
   return N > 0 && (unsigned long long)N < kMaxItems && origin3 && cell > 0.0 && isfinite(cell) && isfinite(origin3[0]) && isfinite(origin3[1]) &&
@@ -218,7 +209,7 @@ __global__ void __launch_bounds__(256) thin_round_kernel(uint32_t N, const uint3
       bool kept_below = false, all_removed = true;
       for (int d = 0; d < 27 && !kept_below; d++) {
         const uint32_t key = key_of(cx + (d % 3) - 1, cy + ((d / 3) % 3) - 1, cz + (d / 9) - 1);
-        for (uint32_t c = lower_bound(keys, N, key); c < N && keys[c] == key; c++) {
+        for (uint32_t c = rg::lower_bound(keys, N, key); c < N && keys[c] == key; c++) {
           const uint32_t j = perm[c];
           if (j >= i) continue;
           const double dx = px - pts[3 * (size_t)c], dy = py - pts[3 * (size_t)c + 1], dz = pz - pts[3 * (size_t)c + 2];
@@ -241,7 +232,7 @@ __global__ void __launch_bounds__(256) thin_round_kernel(uint32_t N, const uint3
 // ------------------------------------------------------------------ nearest neighbour ------------------------------------------------------------------
 __device__ __forceinline__ void scan_cell(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ perm, const double* __restrict__ pts, uint32_t N,
                                           uint32_t key, double qx, double qy, double qz, double& best, uint32_t& best_i) {
-  for (uint32_t c = lower_bound(keys, N, key); c < N && keys[c] == key; c++) {
+  for (uint32_t c = rg::lower_bound(keys, N, key); c < N && keys[c] == key; c++) {
     const double dx = qx - pts[3 * (size_t)c], dy = qy - pts[3 * (size_t)c + 1], dz = qz - pts[3 * (size_t)c + 2];
     const double d2 = (dx * dx + dy * dy) + dz * dz;
     const uint32_t j = perm[c];
@@ -397,102 +388,93 @@ __global__ void __launch_bounds__(256) cull_vertices_kernel(long long NV, const 
 extern "C" {
 
 size_t radegs_mesheval_sample_bytes(long long F) {
-  if (F <= 0 || (unsigned long long)F >= rgme::kMaxItems) return 0;
-  return rgme::sample_carve(F, nullptr, nullptr, nullptr, nullptr);
+  if (F <= 0 || (unsigned long long)F >= rg::kMaxItems) return 0;
+  return rgme::sample_carve(F, nullptr).bytes;
 }
 
 int radegs_mesheval_sample_count(long long V, long long F, const double* vertices, const long long* faces, double density, void* workspace,
                                  size_t workspace_bytes, int* counts, unsigned long long* totals2, void* stream_v) {
   if (V < 0 || F < 0 || !totals2 || !(density > 0.0) || !isfinite(density)) return RADEGS_ERR_INVALID_ARG;
-  if ((unsigned long long)F >= rgme::kMaxItems) return RADEGS_ERR_TOO_LARGE;
+  if ((unsigned long long)F >= rg::kMaxItems) return RADEGS_ERR_TOO_LARGE;
   hipStream_t s = static_cast<hipStream_t>(stream_v);
   if (hipMemsetAsync(totals2, 0, 2 * sizeof(unsigned long long), s) != hipSuccess) return RADEGS_ERR_HIP;
   if (F == 0) return 0;
-  if (!vertices || !faces || !counts || !workspace || workspace_bytes < radegs_mesheval_sample_bytes(F) || (reinterpret_cast<uintptr_t>(workspace) & 15))
+  if (!vertices || !faces || !counts || !workspace || workspace_bytes < radegs_mesheval_sample_bytes(F) || !rg::aligned16(workspace))
     return RADEGS_ERR_INVALID_ARG;
-  uint32_t* incl;
-  void* temp;
-  size_t temp_bytes;
-  rgme::sample_carve(F, workspace, &incl, &temp, &temp_bytes);
+  const rgme::SampleView w = rgme::sample_carve(F, workspace);
   uint32_t* cnt = reinterpret_cast<uint32_t*>(counts);
-  hipLaunchKernelGGL(rgme::tri_count_kernel, dim3(rgme::blocks_of((size_t)F)), dim3(256), 0, s, V, F, vertices, faces, density, cnt, totals2);
-  if (rg::inclusive_scan_gather_u32(temp, temp_bytes, cnt, nullptr, incl, (size_t)F, s) != hipSuccess) return RADEGS_ERR_HIP;
-  return rgme::last();
+  hipLaunchKernelGGL(rgme::tri_count_kernel, dim3(rg::blocks_of((size_t)F)), dim3(256), 0, s, V, F, vertices, faces, density, cnt, totals2);
+  if (rg::inclusive_scan_gather_u32(w.temp, w.temp_bytes, cnt, nullptr, w.incl, (size_t)F, s) != hipSuccess) return RADEGS_ERR_HIP;
+  return rg::launch_status();
 }
 
 int radegs_mesheval_sample_emit(long long V, long long F, const double* vertices, const long long* faces, double density, const void* workspace,
                                 long long M, double* out, void* stream) {
   if (V < 0 || F < 0 || M < 0 || !(density > 0.0)) return RADEGS_ERR_INVALID_ARG;
-  if ((unsigned long long)F >= rgme::kMaxItems || (unsigned long long)M >= 0xFFFFFFFFull) return RADEGS_ERR_TOO_LARGE;
+  if ((unsigned long long)F >= rg::kMaxItems || (unsigned long long)M >= 0xFFFFFFFFull) return RADEGS_ERR_TOO_LARGE;
   if (F == 0 || M == 0) return 0;
   if (!vertices || !faces || !workspace || !out) return RADEGS_ERR_INVALID_ARG;
-  uint32_t* incl;
-  void* temp;
-  size_t temp_bytes;
-  rgme::sample_carve(F, const_cast<void*>(workspace), &incl, &temp, &temp_bytes);
-  hipLaunchKernelGGL(rgme::tri_emit_kernel, dim3(rgme::blocks_of((size_t)M)), dim3(256), 0, static_cast<hipStream_t>(stream), V, F, M, vertices, faces,
-                     density, incl, out);
-  return rgme::last();
+  const rgme::SampleView w = rgme::sample_carve(F, const_cast<void*>(workspace));
+  hipLaunchKernelGGL(rgme::tri_emit_kernel, dim3(rg::blocks_of((size_t)M)), dim3(256), 0, static_cast<hipStream_t>(stream), V, F, M, vertices, faces,
+                     density, w.incl, out);
+  return rg::launch_status();
 }
 
 size_t radegs_mesheval_grid_bytes(long long N) {
-  if (N <= 0 || (unsigned long long)N >= rgme::kMaxItems) return 0;
-  return rgme::grid_carve(N, nullptr, nullptr);
+  if (N <= 0 || (unsigned long long)N >= rg::kMaxItems) return 0;
+  return rgme::grid_carve(N, nullptr).bytes;
 }
 
 int radegs_mesheval_grid_build(long long N, const double* points, const double* origin3, double cell, void* workspace, size_t workspace_bytes,
                                void* stream_v) {
   if (N < 0) return RADEGS_ERR_INVALID_ARG;
-  if ((unsigned long long)N >= rgme::kMaxItems) return RADEGS_ERR_TOO_LARGE;
+  if ((unsigned long long)N >= rg::kMaxItems) return RADEGS_ERR_TOO_LARGE;
   if (N == 0) return 0;
   if (!rgme::grid_args_ok(N, origin3, cell) || !points || !workspace || workspace_bytes < radegs_mesheval_grid_bytes(N) ||
-      (reinterpret_cast<uintptr_t>(workspace) & 15))
+      !rg::aligned16(workspace))
     return RADEGS_ERR_INVALID_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream_v);
-  rgme::GridView w;
-  rgme::grid_carve(N, workspace, &w);
+  const rgme::GridView w = rgme::grid_carve(N, workspace);
   const rgme::Grid g{origin3[0], origin3[1], origin3[2], cell};
-  const unsigned nb = rgme::blocks_of((size_t)N);
+  const unsigned nb = rg::blocks_of((size_t)N);
   hipLaunchKernelGGL(rgme::cell_key_kernel, dim3(nb), dim3(256), 0, s, (uint32_t)N, points, g, w.keys_in);
   if (rg::radix_sort_pairs_u32(w.temp, w.temp_bytes, w.keys_in, w.keys, nullptr, w.perm, (size_t)N, 32, s) != hipSuccess) return RADEGS_ERR_HIP;
   hipLaunchKernelGGL(rgme::reorder_kernel, dim3(nb), dim3(256), 0, s, (uint32_t)N, points, w.perm, w.pts);
-  return rgme::last();
+  return rg::launch_status();
 }
 
 int radegs_mesheval_thin_rounds(long long N, const void* grid_workspace, const double* origin3, double cell, double radius, int rounds,
                                 unsigned char* state, unsigned* undecided, void* stream_v) {
   if (N < 0 || rounds < 0) return RADEGS_ERR_INVALID_ARG;
-  if ((unsigned long long)N >= rgme::kMaxItems) return RADEGS_ERR_TOO_LARGE;
+  if ((unsigned long long)N >= rg::kMaxItems) return RADEGS_ERR_TOO_LARGE;
   if (N == 0 || rounds == 0) return 0;
   if (!rgme::grid_args_ok(N, origin3, cell) || !grid_workspace || !state || !undecided || !(radius >= 0.0) || !(radius <= cell))
     return RADEGS_ERR_INVALID_ARG;   // 27 cells cover the radius only while it is no larger than a cell
   hipStream_t s = static_cast<hipStream_t>(stream_v);
-  rgme::GridView w;
-  rgme::grid_carve(N, const_cast<void*>(grid_workspace), &w);
+  const rgme::GridView w = rgme::grid_carve(N, const_cast<void*>(grid_workspace));
   const rgme::Grid g{origin3[0], origin3[1], origin3[2], cell};
   for (int r = 0; r < rounds; r++)
-    hipLaunchKernelGGL(rgme::thin_round_kernel, dim3(rgme::blocks_of((size_t)N)), dim3(256), 0, s, (uint32_t)N, w.keys, w.perm, w.pts, g, radius * radius,
+    hipLaunchKernelGGL(rgme::thin_round_kernel, dim3(rg::blocks_of((size_t)N)), dim3(256), 0, s, (uint32_t)N, w.keys, w.perm, w.pts, g, radius * radius,
                        state, undecided);
-  return rgme::last();
+  return rg::launch_status();
 }
 
 int radegs_mesheval_nearest(long long N, const void* grid_workspace, const double* origin3, double cell, long long Q, const double* queries,
                             double max_dist, double* dist, long long* index, void* stream) {
   if (N < 0 || Q < 0 || !(max_dist > 0.0) || !isfinite(max_dist)) return RADEGS_ERR_INVALID_ARG;
-  if ((unsigned long long)N >= rgme::kMaxItems) return RADEGS_ERR_TOO_LARGE;
+  if ((unsigned long long)N >= rg::kMaxItems) return RADEGS_ERR_TOO_LARGE;
   if (Q == 0) return 0;
   if (N == 0 || !rgme::grid_args_ok(N, origin3, cell) || !grid_workspace || !queries || !dist || !index) return RADEGS_ERR_INVALID_ARG;
   const double shells = ceil(max_dist / cell) + 1.0;
   if (!(shells <= 512.0)) return RADEGS_ERR_INVALID_ARG;   // half the shortest key period: a larger shell would visit a cell twice
-  rgme::GridView w;
-  rgme::grid_carve(N, const_cast<void*>(grid_workspace), &w);
+  const rgme::GridView w = rgme::grid_carve(N, const_cast<void*>(grid_workspace));
   const rgme::Grid g{origin3[0], origin3[1], origin3[2], cell};
-  hipLaunchKernelGGL(rgme::nearest_kernel, dim3(rgme::blocks_of((size_t)Q)), dim3(256), 0, static_cast<hipStream_t>(stream), (uint32_t)N, w.keys, w.perm,
+  hipLaunchKernelGGL(rgme::nearest_kernel, dim3(rg::blocks_of((size_t)Q)), dim3(256), 0, static_cast<hipStream_t>(stream), (uint32_t)N, w.keys, w.perm,
                      w.pts, g, Q, queries, max_dist, (int)shells, dist, index);
-  return rgme::last();
+  return rg::launch_status();
 }
 
-size_t radegs_mesheval_sum_bytes(void) { return rgme::align256(2 * rgme::kSumBlocks * sizeof(double)); }
+size_t radegs_mesheval_sum_bytes(void) { return rg::align256(2 * rgme::kSumBlocks * sizeof(double)); }
 
 int radegs_mesheval_sum_below(long long Q, const double* dist, double max_dist, void* workspace, size_t workspace_bytes, double* out2, void* stream_v) {
   if (Q < 0 || !out2) return RADEGS_ERR_INVALID_ARG;
@@ -504,7 +486,7 @@ int radegs_mesheval_sum_below(long long Q, const double* dist, double max_dist, 
   double* partial = static_cast<double*>(workspace);
   hipLaunchKernelGGL(rgme::below_partial_kernel, dim3(nb), dim3(256), 0, s, Q, dist, max_dist, partial);
   hipLaunchKernelGGL(rgme::below_final_kernel, dim3(1), dim3(256), 0, s, nb, partial, out2);
-  return rgme::last();
+  return rg::launch_status();
 }
 
 int radegs_mesheval_obs_mask(long long N, const double* points, const double* box10, const int* dims3, const unsigned char* volume,
@@ -521,24 +503,24 @@ int radegs_mesheval_obs_mask(long long N, const double* points, const double* bo
     b.dim[k] = dims3[k];
   }
   b.res = box10[9];
-  hipLaunchKernelGGL(rgme::obs_mask_kernel, dim3(rgme::blocks_of((size_t)N)), dim3(256), 0, static_cast<hipStream_t>(stream), N, points, b, volume, inbound,
+  hipLaunchKernelGGL(rgme::obs_mask_kernel, dim3(rg::blocks_of((size_t)N)), dim3(256), 0, static_cast<hipStream_t>(stream), N, points, b, volume, inbound,
                      grid_inbound, in_obs);
-  return rgme::last();
+  return rg::launch_status();
 }
 
 int radegs_mesheval_above_plane(long long N, const double* points, const double* plane4, unsigned char* above, void* stream) {
   if (N < 0 || !plane4) return RADEGS_ERR_INVALID_ARG;
   if (N == 0) return 0;
   if (!points || !above) return RADEGS_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(rgme::plane_side_kernel, dim3(rgme::blocks_of((size_t)N)), dim3(256), 0, static_cast<hipStream_t>(stream), N, points, plane4[0],
+  hipLaunchKernelGGL(rgme::plane_side_kernel, dim3(rg::blocks_of((size_t)N)), dim3(256), 0, static_cast<hipStream_t>(stream), N, points, plane4[0],
                      plane4[1], plane4[2], plane4[3], above);
-  return rgme::last();
+  return rg::launch_status();
 }
 
 int radegs_mesheval_dilate(int W, int H, const unsigned char* mask, int radius, unsigned char* out, void* stream) {
   if (W < 1 || H < 1 || radius < 0 || radius > 64 || !mask || !out) return RADEGS_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(rgme::dilate_kernel, dim3(rgme::blocks_of((size_t)W * H)), dim3(256), 0, static_cast<hipStream_t>(stream), W, H, mask, radius, out);
-  return rgme::last();
+  hipLaunchKernelGGL(rgme::dilate_kernel, dim3(rg::blocks_of((size_t)W * H)), dim3(256), 0, static_cast<hipStream_t>(stream), W, H, mask, radius, out);
+  return rg::launch_status();
 }
 
 int radegs_mesheval_cull_vertices(long long NV, const float* vertices, int ncam, const RadegsCullCamera* cameras, const unsigned char* masks,
@@ -546,9 +528,9 @@ int radegs_mesheval_cull_vertices(long long NV, const float* vertices, int ncam,
   if (NV < 0 || ncam < 0) return RADEGS_ERR_INVALID_ARG;
   if (NV == 0) return 0;
   if (!vertices || !flags || (ncam && (!cameras || !masks)) || (reinterpret_cast<uintptr_t>(cameras) & 7)) return RADEGS_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(rgme::cull_vertices_kernel, dim3(rgme::blocks_of((size_t)NV)), dim3(256), 0, static_cast<hipStream_t>(stream), NV, vertices, ncam,
+  hipLaunchKernelGGL(rgme::cull_vertices_kernel, dim3(rg::blocks_of((size_t)NV)), dim3(256), 0, static_cast<hipStream_t>(stream), NV, vertices, ncam,
                      cameras, masks, flags);
-  return rgme::last();
+  return rg::launch_status();
 }
 
 }  // extern "C"

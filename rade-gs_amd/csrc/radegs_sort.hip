@@ -19,6 +19,7 @@
 #include <stdlib.h>
 
 #include "rg_prims.h"
+#include "rg_workspace.h"
 
 namespace rg {
 
@@ -366,13 +367,12 @@ static hipError_t radix_sort_pairs(void* temp, size_t temp_bytes, const K* keys_
   const int items = sort_items_per_thread(n, items_override);
   if (items < 0) return hipErrorInvalidValue;
   const uint32_t nblocks = (uint32_t)((n + (size_t)kSortThreads * items - 1) / ((size_t)kSortThreads * items));
-  char* p = static_cast<char*>(temp);
-  auto take = [&](size_t bytes) { char* r = p; p += (bytes + 255) & ~size_t(255); return r; };
-  K* tkeys = reinterpret_cast<K*>(take(n * sizeof(uint32_t)));
-  uint32_t* tvals = reinterpret_cast<uint32_t*>(take(n * sizeof(uint32_t)));
+  Carver c(temp);
+  K* tkeys = reinterpret_cast<K*>(c.take<uint32_t>(n));   // a word per key whatever K is
+  uint32_t* tvals = c.take<uint32_t>(n);
   const int bins = digit_bits > 8 ? 512 : 256;
-  uint32_t* hist = reinterpret_cast<uint32_t*>(take((size_t)bins * nblocks * sizeof(uint32_t)));
-  uint32_t* totals = reinterpret_cast<uint32_t*>(take(bins * sizeof(uint32_t)));
+  uint32_t* hist = c.take<uint32_t>((size_t)bins * nblocks);
+  uint32_t* totals = c.take<uint32_t>(bins);
   const int passes = (end_bit + digit_bits - 1) / digit_bits;
   const int width = (end_bit + passes - 1) / passes;  // balanced digits: 13 bits -> 7 + 6, 32 -> 8 x 4
   const K* src_k = keys_in;
@@ -424,6 +424,30 @@ hipError_t radix_sort_pairs_u16(void* temp, size_t temp_bytes, const uint16_t* k
                                 uint32_t* vals_out, size_t n, int end_bit, hipStream_t stream, const uint32_t* n_dev, int items_override) {
   if (end_bit > 16) return hipErrorInvalidValue;
   return radix_sort_pairs<uint16_t>(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, n, end_bit, stream, n_dev, items_override);
+}
+
+namespace {
+// dst[i] = src[idx[i]] for i < min(cap, *n_dev)
+__global__ void __launch_bounds__(256) gather_kernel(uint32_t cap, const uint32_t* __restrict__ n_dev, const uint32_t* __restrict__ src,
+                                                     const uint32_t* __restrict__ idx, uint32_t* __restrict__ dst) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= cap || (n_dev && i >= *n_dev)) return;
+  dst[i] = src[idx[i]];
+}
+}  // namespace
+
+// The order of (major, minor) word pairs (rg_prims.h): two stable sorts, the minor word first, with one gather of the major word through
+// the first permutation in between.
+hipError_t radix_sort_order_2xu32(void* temp, size_t temp_bytes, const uint32_t* minor, const uint32_t* major, uint32_t* major_sorted,
+                                  uint32_t* perm, uint32_t* s0, uint32_t* s1, uint32_t* s2, size_t n, int minor_end_bit, int major_end_bit,
+                                  hipStream_t stream, const uint32_t* n_dev) {
+  if (n == 0) return hipSuccess;
+  if (minor_end_bit < 1 || minor_end_bit > 32 || major_end_bit < 1 || major_end_bit > 32 || temp_bytes < sort_temp_bytes(n) || n > kMaxItems)
+    return hipErrorInvalidValue;
+  hipError_t e = radix_sort_pairs_u32(temp, temp_bytes, minor, s0, nullptr, s1, n, minor_end_bit, stream, n_dev);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(gather_kernel, dim3(blocks_of(n)), dim3(256), 0, stream, (uint32_t)n, n_dev, major, s1, s2);
+  return radix_sort_pairs_u32(temp, temp_bytes, s2, major_sorted, s1, perm, n, major_end_bit, stream, n_dev);
 }
 
 }  // namespace rg

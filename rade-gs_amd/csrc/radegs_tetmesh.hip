@@ -12,8 +12,8 @@
 //         classify_kernel       per tet: case code, #crossing edges, one- / two-triangle flag        -> flags[3 T], code[T]
 //         rg::inclusive_scan_gather_u32 over the 3 T flags: instance offsets and the two face numberings in one scan
 //         emit_edges_kernel     (lo, hi) of every crossing edge at offset[tet] + rank of the edge inside the tet
-//         rg::radix_sort_pairs_u32 by hi, gather lo through the permutation, rg::radix_sort_pairs_u32 by lo (stable: LSD over the
-//                               pair).  The instance count E stays on the device (n_dev); the grids are sized by the capacity 4 T.
+//         rg::radix_sort_order_2xu32: the stable order of the (lo, hi) pairs, hi the minor word.  The instance count E stays on the
+//                               device (n_dev); the grids are sized by the capacity 4 T.
 //         head_kernel           first instance of every distinct (lo, hi)   -> scan -> vertex id of every sorted instance
 //         scatter_ids_kernel    vertex id back to the instance's emission slot + the two counts
 //   emit  vertex_kernel         interp_v and the three gathers, one thread per head instance
@@ -23,10 +23,12 @@
 
 #include "../../include/radegs.h"
 #include "rg_prims.h"
+#include "rg_workspace.h"
 
 namespace rgt {
 
-constexpr unsigned long long kMaxItems = 0xFFFFFFFFull - 65536ull;   // what the u32 sort / scan address
+using rg::blocks_of;
+using rg::kMaxItems;
 
 // rows of upstream's 16 x 6 triangle table (utils/tetmesh.py:23-40), one nibble per entry, entry 0 lowest; 0xF = none
 __constant__ uint32_t kTriTable[16] = {0xFFFFFFu, 0xFFF201u, 0xFFF304u, 0x431241u, 0xFFF513u, 0x352032u, 0x451041u, 0xFFF524u,
@@ -84,13 +86,6 @@ __global__ void __launch_bounds__(256) emit_edges_kernel(long long T, const int4
       hi[at] = a < b ? b : a;
       at++;
     }
-}
-
-__global__ void __launch_bounds__(256) gather_kernel(uint32_t cap, const uint32_t* __restrict__ n_dev, const uint32_t* __restrict__ src,
-                                                     const uint32_t* __restrict__ idx, uint32_t* __restrict__ dst) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= cap || i >= *n_dev) return;
-  dst[i] = src[idx[i]];
 }
 
 // head[i] = 1 where sorted instance i opens a new (lo, hi); 0 elsewhere, up to the capacity (the scan runs over all of it)
@@ -161,38 +156,33 @@ __global__ void __launch_bounds__(256) face_kernel(long long T, long long n_face
 }
 
 struct Workspace {
-  uint32_t *bits, *flags, *incl, *lo, *hi, *b1, *perm1, *lo_g, *lo_sorted, *perm2;
+  uint32_t *bits, *flags, *incl;
   uint8_t* code;
+  uint32_t *lo, *hi, *b1, *perm1, *lo_g, *lo_sorted, *perm2;   // b1, perm1, lo_g: the sort's scratch
   void* temp;
-  size_t temp_bytes;
-  // after the second sort: head flags live in lo_g, the scanned vertex ids in perm1, the per-slot ids in b1
+  size_t temp_bytes, bytes;
+  // after the sort: head flags live in lo_g, the scanned vertex ids in perm1, the per-slot ids in b1
 };
 
-static size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 static size_t capacity(long long T) { return 4 * (size_t)T; }
-static size_t carve(int V, long long T, void* base, Workspace* w) {
+static Workspace carve(int V, long long T, void* base) {
   const size_t n = (size_t)T, cap = capacity(T);
-  size_t temp_bytes = rg::sort_temp_bytes(cap);
-  if (rg::scan_temp_bytes(cap) > temp_bytes) temp_bytes = rg::scan_temp_bytes(cap);
-  if (rg::scan_temp_bytes(3 * n) > temp_bytes) temp_bytes = rg::scan_temp_bytes(3 * n);
-  size_t off = 0;
-  char* b = static_cast<char*>(base);
-  auto take = [&](size_t bytes) { char* p = b ? b + off : nullptr; off += align256(bytes); return p; };
-  char* bits = take((((size_t)V + 63) / 64) * 8);
-  char* flags = take(3 * n * 4);
-  char* incl = take(3 * n * 4);
-  char* code = take(n);
-  char* arr[7];
-  for (int k = 0; k < 7; k++) arr[k] = take(cap * 4);
-  char* temp = take(temp_bytes);
-  auto u = [](char* p) { return reinterpret_cast<uint32_t*>(p); };
-  if (w) *w = Workspace{u(bits), u(flags), u(incl), u(arr[0]), u(arr[1]), u(arr[2]), u(arr[3]), u(arr[4]), u(arr[5]), u(arr[6]),
-                        reinterpret_cast<uint8_t*>(code), temp, temp_bytes};
-  return off;
+  rg::Carver c(base);
+  Workspace v;
+  v.temp_bytes = rg::sort_temp_bytes(cap);
+  if (rg::scan_temp_bytes(cap) > v.temp_bytes) v.temp_bytes = rg::scan_temp_bytes(cap);
+  if (rg::scan_temp_bytes(3 * n) > v.temp_bytes) v.temp_bytes = rg::scan_temp_bytes(3 * n);
+  v.bits = c.take<uint32_t>(2 * (((size_t)V + 63) / 64));   // whole 64-bit words: occ_pack_kernel writes one per wave
+  v.flags = c.take<uint32_t>(3 * n);
+  v.incl = c.take<uint32_t>(3 * n);
+  v.code = c.take<uint8_t>(n);
+  for (uint32_t** a : {&v.lo, &v.hi, &v.b1, &v.perm1, &v.lo_g, &v.lo_sorted, &v.perm2}) *a = c.take<uint32_t>(cap);
+  v.temp = c.take<char>(v.temp_bytes);
+  v.bytes = c.off;
+  return v;
 }
 
 static bool sizes_ok(int V, long long T) { return V >= 0 && T >= 0 && 5ull * (unsigned long long)T < kMaxItems; }   // V < 2^31: it is an int
-static unsigned blocks_of(size_t n) { return (unsigned)((n + 255) / 256); }
 
 // ------------------------------------------------------------- per-point kernels -------------------------------------------------------------
 // One thread per Gaussian: its eight box corners (24 consecutive floats: six 16-byte stores) and its centre.
@@ -343,22 +333,33 @@ __global__ void __launch_bounds__(256) filter_apply_kernel(long long NV, long lo
   }
 }
 
-static size_t filter_carve(long long NV, long long NF, void* base, uint32_t** flags, uint32_t** incl, void** temp, size_t* temp_bytes) {
-  const size_t n = (size_t)(NV + NF), tb = rg::scan_temp_bytes(n);
-  size_t off = 0;
-  char* b = static_cast<char*>(base);
-  auto take = [&](size_t bytes) { char* p = b ? b + off : nullptr; off += align256(bytes); return p; };
-  char* f = take(n * 4);
-  char* i = take(n * 4);
-  char* t = take(tb);
-  if (flags) { *flags = reinterpret_cast<uint32_t*>(f); *incl = reinterpret_cast<uint32_t*>(i); *temp = t; *temp_bytes = tb; }
-  return off;
+struct FilterView {
+  uint32_t *flags, *incl;
+  void* temp;
+  size_t temp_bytes, bytes;
+};
+static FilterView filter_carve(long long NV, long long NF, void* base) {
+  const size_t n = (size_t)(NV + NF);
+  rg::Carver c(base);
+  FilterView v;
+  v.temp_bytes = rg::scan_temp_bytes(n);
+  v.flags = c.take<uint32_t>(n);
+  v.incl = c.take<uint32_t>(n);
+  v.temp = c.take<char>(v.temp_bytes);
+  v.bytes = c.off;
+  return v;
 }
 static bool filter_sizes_ok(long long NV, long long NF) {
   return NV >= 0 && NF >= 0 && (unsigned long long)NV < kMaxItems && (unsigned long long)NF < kMaxItems && (unsigned long long)(NV + NF) < kMaxItems;
 }
 
-static int last() { return hipGetLastError() == hipSuccess ? 0 : RADEGS_ERR_HIP; }
+// The part of the two filter plans after the vertex flags w.flags[0, NV) are on their way: the face flags, the scan, the counts.
+static int filter_plan_faces(long long NV, long long NF, const long long* faces, const FilterView& w, long long* counts2, hipStream_t s) {
+  if (NF) hipLaunchKernelGGL(keep_face_kernel, dim3(blocks_of((size_t)NF)), dim3(256), 0, s, NV, NF, faces, w.flags);
+  if (rg::inclusive_scan_gather_u32(w.temp, w.temp_bytes, w.flags, nullptr, w.incl, (size_t)(NV + NF), s) != hipSuccess) return RADEGS_ERR_HIP;
+  hipLaunchKernelGGL(filter_counts_kernel, dim3(1), dim3(1), 0, s, NV, NF, w.incl, counts2);
+  return rg::launch_status();
+}
 
 }  // namespace rgt
 
@@ -366,7 +367,7 @@ extern "C" {
 
 size_t radegs_tetmesh_plan_bytes(int V, long long T) {
   if (!rgt::sizes_ok(V, T) || V == 0 || T == 0) return 0;
-  return rgt::carve(V, T, nullptr, nullptr);
+  return rgt::carve(V, T, nullptr).bytes;
 }
 
 int radegs_tetmesh_plan(int V, long long T, const int* tets, const float* sdf, void* workspace, size_t workspace_bytes, long long* counts2,
@@ -375,28 +376,27 @@ int radegs_tetmesh_plan(int V, long long T, const int* tets, const float* sdf, v
   if (!rgt::sizes_ok(V, T)) return RADEGS_ERR_TOO_LARGE;
   hipStream_t s = static_cast<hipStream_t>(stream_v);
   if (V == 0 || T == 0) return hipMemsetAsync(counts2, 0, 2 * sizeof(long long), s) == hipSuccess ? 0 : RADEGS_ERR_HIP;
-  if (!tets || !sdf || !workspace || workspace_bytes < radegs_tetmesh_plan_bytes(V, T) || (reinterpret_cast<uintptr_t>(workspace) & 15) ||
-      (reinterpret_cast<uintptr_t>(tets) & 15))
+  if (!tets || !sdf || !workspace || workspace_bytes < radegs_tetmesh_plan_bytes(V, T) || !rg::aligned16(workspace) ||
+      !rg::aligned16(tets))
     return RADEGS_ERR_INVALID_ARG;
-  rgt::Workspace w;
-  rgt::carve(V, T, workspace, &w);
+  const rgt::Workspace w = rgt::carve(V, T, workspace);
   const uint32_t cap = (uint32_t)rgt::capacity(T);
   const int4* tets4 = reinterpret_cast<const int4*>(tets);
   int end_bit = 1;
   while (end_bit < 31 && ((unsigned)(V - 1) >> end_bit)) end_bit++;
-  hipLaunchKernelGGL(rgt::occ_pack_kernel, dim3(rgt::blocks_of((size_t)V)), dim3(256), 0, s, (uint32_t)V, sdf, reinterpret_cast<unsigned long long*>(w.bits));
-  hipLaunchKernelGGL(rgt::classify_kernel, dim3(rgt::blocks_of((size_t)T)), dim3(256), 0, s, T, (uint32_t)V, tets4, w.bits, w.flags, w.code);
+  hipLaunchKernelGGL(rgt::occ_pack_kernel, dim3(rg::blocks_of((size_t)V)), dim3(256), 0, s, (uint32_t)V, sdf, reinterpret_cast<unsigned long long*>(w.bits));
+  hipLaunchKernelGGL(rgt::classify_kernel, dim3(rg::blocks_of((size_t)T)), dim3(256), 0, s, T, (uint32_t)V, tets4, w.bits, w.flags, w.code);
   if (rg::inclusive_scan_gather_u32(w.temp, w.temp_bytes, w.flags, nullptr, w.incl, 3 * (size_t)T, s) != hipSuccess) return RADEGS_ERR_HIP;
   const uint32_t* n_dev = w.incl + (T - 1);   // E, the number of crossing-edge instances: never read by the host
-  hipLaunchKernelGGL(rgt::emit_edges_kernel, dim3(rgt::blocks_of((size_t)T)), dim3(256), 0, s, T, tets4, w.code, w.incl, w.lo, w.hi);
-  if (rg::radix_sort_pairs_u32(w.temp, w.temp_bytes, w.hi, w.b1, nullptr, w.perm1, cap, end_bit, s, n_dev) != hipSuccess) return RADEGS_ERR_HIP;
-  hipLaunchKernelGGL(rgt::gather_kernel, dim3(rgt::blocks_of(cap)), dim3(256), 0, s, cap, n_dev, w.lo, w.perm1, w.lo_g);
-  if (rg::radix_sort_pairs_u32(w.temp, w.temp_bytes, w.lo_g, w.lo_sorted, w.perm1, w.perm2, cap, end_bit, s, n_dev) != hipSuccess) return RADEGS_ERR_HIP;
+  hipLaunchKernelGGL(rgt::emit_edges_kernel, dim3(rg::blocks_of((size_t)T)), dim3(256), 0, s, T, tets4, w.code, w.incl, w.lo, w.hi);
+  if (rg::radix_sort_order_2xu32(w.temp, w.temp_bytes, w.hi, w.lo, w.lo_sorted, w.perm2, w.b1, w.perm1, w.lo_g, cap, end_bit, end_bit, s, n_dev) !=
+      hipSuccess)
+    return RADEGS_ERR_HIP;
   uint32_t *head = w.lo_g, *vid_incl = w.perm1, *vid_of = w.b1;
-  hipLaunchKernelGGL(rgt::head_kernel, dim3(rgt::blocks_of(cap)), dim3(256), 0, s, cap, n_dev, w.lo_sorted, w.hi, w.perm2, head);
+  hipLaunchKernelGGL(rgt::head_kernel, dim3(rg::blocks_of(cap)), dim3(256), 0, s, cap, n_dev, w.lo_sorted, w.hi, w.perm2, head);
   if (rg::inclusive_scan_gather_u32(w.temp, w.temp_bytes, head, nullptr, vid_incl, cap, s) != hipSuccess) return RADEGS_ERR_HIP;
-  hipLaunchKernelGGL(rgt::scatter_ids_kernel, dim3(rgt::blocks_of(cap)), dim3(256), 0, s, cap, T, w.incl, w.perm2, vid_incl, vid_of, counts2);
-  return rgt::last();
+  hipLaunchKernelGGL(rgt::scatter_ids_kernel, dim3(rg::blocks_of(cap)), dim3(256), 0, s, cap, T, w.incl, w.perm2, vid_incl, vid_of, counts2);
+  return rg::launch_status();
 }
 
 int radegs_tetmesh_emit(int V, long long T, const int* tets, const float* sdf, const float* vertices, const float* scales, const void* workspace,
@@ -408,16 +408,15 @@ int radegs_tetmesh_emit(int V, long long T, const int* tets, const float* sdf, c
   if (!tets || !sdf || !vertices || !scales || !workspace || (n_verts && (!end_points || !end_sdf || !end_scales || !interp_v)) || (n_faces && !faces))
     return RADEGS_ERR_INVALID_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream_v);
-  rgt::Workspace w;
-  rgt::carve(V, T, const_cast<void*>(workspace), &w);
+  const rgt::Workspace w = rgt::carve(V, T, const_cast<void*>(workspace));
   const uint32_t cap = (uint32_t)rgt::capacity(T);
   const uint32_t* n_dev = w.incl + (T - 1);
   if (n_verts)
-    hipLaunchKernelGGL(rgt::vertex_kernel, dim3(rgt::blocks_of(cap)), dim3(256), 0, s, cap, n_dev, n_verts, w.lo_g, w.perm1, w.lo_sorted, w.hi, w.perm2,
+    hipLaunchKernelGGL(rgt::vertex_kernel, dim3(rg::blocks_of(cap)), dim3(256), 0, s, cap, n_dev, n_verts, w.lo_g, w.perm1, w.lo_sorted, w.hi, w.perm2,
                        vertices, sdf, scales, end_points, end_sdf, end_scales, interp_v);
   if (n_faces)
-    hipLaunchKernelGGL(rgt::face_kernel, dim3(rgt::blocks_of((size_t)T)), dim3(256), 0, s, T, n_faces, w.code, w.incl, w.b1, faces);
-  return rgt::last();
+    hipLaunchKernelGGL(rgt::face_kernel, dim3(rg::blocks_of((size_t)T)), dim3(256), 0, s, T, n_faces, w.code, w.incl, w.b1, faces);
+  return rg::launch_status();
 }
 
 int radegs_tetra_points(int P, const float* xyz, const float* scales3, const float* rotation_raw, float* out_points, float* out_scale, void* stream) {
@@ -428,7 +427,7 @@ int radegs_tetra_points(int P, const float* xyz, const float* scales3, const flo
     return RADEGS_ERR_INVALID_ARG;
   hipLaunchKernelGGL(rgt::tetra_points_kernel, dim3((P + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), P, xyz, scales3, rotation_raw,
                      out_points, out_scale);
-  return rgt::last();
+  return rg::launch_status();
 }
 
 int radegs_cull_alpha_accumulate(long long PN, const float* alpha_integrated, const float* point_coordinate, const float* mask, const float* gt_mask,
@@ -436,17 +435,17 @@ int radegs_cull_alpha_accumulate(long long PN, const float* alpha_integrated, co
   if (PN < 0 || PN >= (1ll << 39) || W < 1 || H < 1) return RADEGS_ERR_INVALID_ARG;
   if (PN == 0) return 0;
   if (!alpha_integrated || !point_coordinate || !mask || !final_sdf || !weight || (reinterpret_cast<uintptr_t>(point_coordinate) & 7)) return RADEGS_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(rgt::cull_alpha_kernel, dim3(rgt::blocks_of((size_t)PN)), dim3(256), 0, static_cast<hipStream_t>(stream), PN, alpha_integrated,
+  hipLaunchKernelGGL(rgt::cull_alpha_kernel, dim3(rg::blocks_of((size_t)PN)), dim3(256), 0, static_cast<hipStream_t>(stream), PN, alpha_integrated,
                      reinterpret_cast<const float2*>(point_coordinate), mask, gt_mask, masks_extra, W, H, final_sdf, weight);
-  return rgt::last();
+  return rg::launch_status();
 }
 
 int radegs_cull_alpha_finish(long long PN, const float* final_sdf, const int* weight, float* sdf_out, void* stream) {
   if (PN < 0 || PN >= (1ll << 39)) return RADEGS_ERR_INVALID_ARG;
   if (PN == 0) return 0;
   if (!final_sdf || !weight || !sdf_out) return RADEGS_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(rgt::cull_finish_kernel, dim3(rgt::blocks_of((size_t)PN)), dim3(256), 0, static_cast<hipStream_t>(stream), PN, final_sdf, weight, sdf_out);
-  return rgt::last();
+  hipLaunchKernelGGL(rgt::cull_finish_kernel, dim3(rg::blocks_of((size_t)PN)), dim3(256), 0, static_cast<hipStream_t>(stream), PN, final_sdf, weight, sdf_out);
+  return rg::launch_status();
 }
 
 int radegs_tetmesh_bisect(long long N, float* left_pts, float* right_pts, float* left_sdf, float* right_sdf, const float* mid_sdf, float* mid_pts_out,
@@ -454,14 +453,14 @@ int radegs_tetmesh_bisect(long long N, float* left_pts, float* right_pts, float*
   if (N < 0 || N >= (1ll << 39)) return RADEGS_ERR_INVALID_ARG;
   if (N == 0) return 0;
   if (!left_pts || !right_pts || !left_sdf || !right_sdf || !mid_sdf || !mid_pts_out) return RADEGS_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(rgt::bisect_kernel, dim3(rgt::blocks_of((size_t)N)), dim3(256), 0, static_cast<hipStream_t>(stream), N, left_pts, right_pts, left_sdf,
+  hipLaunchKernelGGL(rgt::bisect_kernel, dim3(rg::blocks_of((size_t)N)), dim3(256), 0, static_cast<hipStream_t>(stream), N, left_pts, right_pts, left_sdf,
                      right_sdf, mid_sdf, mid_pts_out);
-  return rgt::last();
+  return rg::launch_status();
 }
 
 size_t radegs_tetmesh_filter_plan_bytes(long long NV, long long NF) {
   if (!rgt::filter_sizes_ok(NV, NF) || NV + NF == 0) return 0;
-  return rgt::filter_carve(NV, NF, nullptr, nullptr, nullptr, nullptr, nullptr);
+  return rgt::filter_carve(NV, NF, nullptr).bytes;
 }
 
 int radegs_tetmesh_filter_plan(long long NV, long long NF, const float* end_points, const float* end_scales, const long long* faces, void* workspace,
@@ -471,17 +470,11 @@ int radegs_tetmesh_filter_plan(long long NV, long long NF, const float* end_poin
   hipStream_t s = static_cast<hipStream_t>(stream_v);
   if (NV == 0) return hipMemsetAsync(counts2, 0, 2 * sizeof(long long), s) == hipSuccess ? 0 : RADEGS_ERR_HIP;   // no vertex: no face survives
   if (!end_points || !end_scales || (NF && !faces) || !workspace || workspace_bytes < radegs_tetmesh_filter_plan_bytes(NV, NF) ||
-      (reinterpret_cast<uintptr_t>(workspace) & 15))
+      !rg::aligned16(workspace))
     return RADEGS_ERR_INVALID_ARG;
-  uint32_t *flags, *incl;
-  void* temp;
-  size_t temp_bytes;
-  rgt::filter_carve(NV, NF, workspace, &flags, &incl, &temp, &temp_bytes);
-  hipLaunchKernelGGL(rgt::keep_vertex_kernel, dim3(rgt::blocks_of((size_t)NV)), dim3(256), 0, s, NV, end_points, end_scales, flags);
-  if (NF) hipLaunchKernelGGL(rgt::keep_face_kernel, dim3(rgt::blocks_of((size_t)NF)), dim3(256), 0, s, NV, NF, faces, flags);
-  if (rg::inclusive_scan_gather_u32(temp, temp_bytes, flags, nullptr, incl, (size_t)(NV + NF), s) != hipSuccess) return RADEGS_ERR_HIP;
-  hipLaunchKernelGGL(rgt::filter_counts_kernel, dim3(1), dim3(1), 0, s, NV, NF, incl, counts2);
-  return rgt::last();
+  const rgt::FilterView w = rgt::filter_carve(NV, NF, workspace);
+  hipLaunchKernelGGL(rgt::keep_vertex_kernel, dim3(rg::blocks_of((size_t)NV)), dim3(256), 0, s, NV, end_points, end_scales, w.flags);
+  return rgt::filter_plan_faces(NV, NF, faces, w, counts2, s);
 }
 
 int radegs_tetmesh_filter_plan_flags(long long NV, long long NF, const unsigned* vertex_flags, const long long* faces, void* workspace,
@@ -491,17 +484,11 @@ int radegs_tetmesh_filter_plan_flags(long long NV, long long NF, const unsigned*
   hipStream_t s = static_cast<hipStream_t>(stream_v);
   if (NV == 0) return hipMemsetAsync(counts2, 0, 2 * sizeof(long long), s) == hipSuccess ? 0 : RADEGS_ERR_HIP;
   if (!vertex_flags || (NF && !faces) || !workspace || workspace_bytes < radegs_tetmesh_filter_plan_bytes(NV, NF) ||
-      (reinterpret_cast<uintptr_t>(workspace) & 15))
+      !rg::aligned16(workspace))
     return RADEGS_ERR_INVALID_ARG;
-  uint32_t *flags, *incl;
-  void* temp;
-  size_t temp_bytes;
-  rgt::filter_carve(NV, NF, workspace, &flags, &incl, &temp, &temp_bytes);
-  if (hipMemcpyAsync(flags, vertex_flags, (size_t)NV * sizeof(uint32_t), hipMemcpyDeviceToDevice, s) != hipSuccess) return RADEGS_ERR_HIP;
-  if (NF) hipLaunchKernelGGL(rgt::keep_face_kernel, dim3(rgt::blocks_of((size_t)NF)), dim3(256), 0, s, NV, NF, faces, flags);
-  if (rg::inclusive_scan_gather_u32(temp, temp_bytes, flags, nullptr, incl, (size_t)(NV + NF), s) != hipSuccess) return RADEGS_ERR_HIP;
-  hipLaunchKernelGGL(rgt::filter_counts_kernel, dim3(1), dim3(1), 0, s, NV, NF, incl, counts2);
-  return rgt::last();
+  const rgt::FilterView w = rgt::filter_carve(NV, NF, workspace);
+  if (hipMemcpyAsync(w.flags, vertex_flags, (size_t)NV * sizeof(uint32_t), hipMemcpyDeviceToDevice, s) != hipSuccess) return RADEGS_ERR_HIP;
+  return rgt::filter_plan_faces(NV, NF, faces, w, counts2, s);
 }
 
 int radegs_tetmesh_filter_apply(long long NV, long long NF, const float* points, const long long* faces, const void* workspace, long long nv_out,
@@ -510,13 +497,10 @@ int radegs_tetmesh_filter_apply(long long NV, long long NF, const float* points,
   if (!rgt::filter_sizes_ok(NV, NF)) return RADEGS_ERR_TOO_LARGE;
   if (NV == 0 || nv_out == 0) return 0;
   if (!points || (NF && !faces) || !workspace || !out_vertices || (nf_out && !out_faces)) return RADEGS_ERR_INVALID_ARG;
-  uint32_t *flags, *incl;
-  void* temp;
-  size_t temp_bytes;
-  rgt::filter_carve(NV, NF, const_cast<void*>(workspace), &flags, &incl, &temp, &temp_bytes);
-  hipLaunchKernelGGL(rgt::filter_apply_kernel, dim3(rgt::blocks_of((size_t)(NV + (nf_out ? NF : 0)))), dim3(256), 0, static_cast<hipStream_t>(stream), NV,
-                     nf_out ? NF : 0, nv_out, nf_out, points, faces, flags, incl, out_vertices, out_faces);
-  return rgt::last();
+  const rgt::FilterView w = rgt::filter_carve(NV, NF, const_cast<void*>(workspace));
+  hipLaunchKernelGGL(rgt::filter_apply_kernel, dim3(rg::blocks_of((size_t)(NV + (nf_out ? NF : 0)))), dim3(256), 0, static_cast<hipStream_t>(stream), NV,
+                     nf_out ? NF : 0, nv_out, nf_out, points, faces, w.flags, w.incl, out_vertices, out_faces);
+  return rg::launch_status();
 }
 
 }  // extern "C"

@@ -1,8 +1,9 @@
 // radegs_tsdf.hip -- TSDF fusion: the step between the renderer's median depth maps and recon.ply on the reference's DTU
 // route, mesh_extract.py:51-105, which upstream hands to Open3D's VoxelBlockGrid on the CPU.
-//     compute_unique_block_coordinates     touch_keys_kernel -> the 64-bit sort -> first_kernel -> scans -> unique_emit_kernel
-//     integrate                            coords_keys_kernel -> the same sort, first_kernel against the grid -> insert_old / insert_new_kernel
-//                                          (the merged key array), fuse_view_kernel
+//     compute_unique_block_coordinates     touch_keys_kernel (the key as two words) -> rg::radix_sort_order_2xu32 -> join_keys_kernel ->
+//                                          first_kernel -> scans -> unique_emit_kernel
+//     integrate                            coords_keys_kernel -> the same sort and join, first_kernel against the grid -> insert_old /
+//                                          insert_new_kernel (the merged key array), fuse_view_kernel
 //     extract_triangle_mesh                extract_count_kernel -> scans over the blocks -> extract_vertices_kernel, extract_faces_kernel
 //
 // The specification is include/radegs.h, "TSDF fusion"; tests/tsdf_restatement.py restates it in NumPy float32 and the kernels are held to
@@ -10,7 +11,7 @@
 //
 // The grid.  A block is 16^3 voxels; its coordinate floor(world / block_size) per axis is packed into a 63-bit key (21 bits per axis, bias
 // 2^20, z highest).  The grid is the ascending key array plus, per key, a slot into dense storage [capacity][4096] (voxel (z * 16 + y) * 16 + x);
-// a block is found by lower_bound, as radegs_mesheval.hip finds a cell.  A new block takes the next free slot, so a view's new blocks are one
+// a block is found by rg::lower_bound, as radegs_mesheval.hip finds a cell.  A new block takes the next free slot, so a view's new blocks are one
 // contiguous range of the storage (the caller zero-fills it) and no block ever moves.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -19,19 +20,16 @@
 #include "../../include/radegs.h"
 #include "rg_mc_tables.h"
 #include "rg_prims.h"
+#include "rg_workspace.h"
 
 namespace rgts {
 
-constexpr unsigned long long kMaxItems = 0xFFFFFFFFull - 65536ull;   // what the u32 sort / scan address
-constexpr unsigned long long kNoKey = ~0ull;                          // a sample that touches nothing; sorts last (real keys have 63 bits)
+using rg::blocks_of;
+constexpr unsigned long long kNoKey = ~0ull;   // a sample that touches nothing; sorts last (real keys have 63 bits)
 constexpr int kBias = 1 << 20;
 constexpr int kVox = 4096;
 constexpr int kPad = 18, kPad3 = 18 * 18 * 18;      // a block's corners with one layer of its neighbours on every side
 constexpr int kCells = 17, kCells3 = 17 * 17 * 17;  // the cells whose lowest corner is at -1 .. 15 per axis
-
-static size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-static unsigned blocks_of(size_t n) { return (unsigned)((n + 255) / 256); }
-static int last() { return hipGetLastError() == hipSuccess ? 0 : RADEGS_ERR_HIP; }
 
 struct Camera {
   float fx, fy, cx, cy;
@@ -48,27 +46,19 @@ __device__ __forceinline__ void unpack_key(unsigned long long key, int& bx, int&
 }
 __device__ __forceinline__ bool in_range(int c) { return c >= -kBias && c < kBias; }
 
-__device__ __forceinline__ uint32_t lower_bound(const unsigned long long* __restrict__ keys, uint32_t n, unsigned long long key) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (keys[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
 // position of the block at (bx, by, bz) in the key array, -1 when absent (or outside the key range)
 __device__ __forceinline__ int find_block(const unsigned long long* __restrict__ keys, uint32_t n, int bx, int by, int bz) {
   if (!in_range(bx) || !in_range(by) || !in_range(bz)) return -1;
   const unsigned long long key = pack_key(bx, by, bz);
-  const uint32_t p = lower_bound(keys, n, key);
+  const uint32_t p = rg::lower_bound(keys, n, key);
   return (p < n && keys[p] == key) ? (int)p : -1;
 }
 
 // ------------------------------------------------------------------------- touch -------------------------------------------------------------------------
 // One thread per sampled pixel (4i, 4j): four points along its ray between d - trunc and d + trunc, each one key.  A coordinate outside the
-// 21 bits raises the flag and yields no key: it never wraps.
+// 21 bits raises the flag and yields no key: it never wraps.  The key leaves as its two words, lo[] and hi[], which is what the sort takes.
 __global__ void __launch_bounds__(256) touch_keys_kernel(int W, int H, const float* __restrict__ depth, Camera c, float depth_scale, float depth_max,
-                                                         float trunc, float block_size, unsigned long long* __restrict__ keys, uint32_t* __restrict__ flag) {
+                                                         float trunc, float block_size, uint32_t* __restrict__ lo, uint32_t* __restrict__ hi, uint32_t* __restrict__ flag) {
   const int w4 = W / 4, h4 = H / 4;
   const long long s = (long long)blockIdx.x * 256 + threadIdx.x;
   if (s >= (long long)w4 * h4) return;
@@ -93,35 +83,29 @@ __global__ void __launch_bounds__(256) touch_keys_kernel(int W, int H, const flo
       if (fits) key = pack_key((int)b[0], (int)b[1], (int)b[2]);
       else *flag = 1u;
     }
-    keys[4 * s + k] = key;
+    lo[4 * s + k] = (uint32_t)key;
+    hi[4 * s + k] = (uint32_t)(key >> 32);
   }
 }
 
-__global__ void __launch_bounds__(256) coords_keys_kernel(uint32_t n, const int* __restrict__ coords, unsigned long long* __restrict__ keys,
-                                                          uint32_t* __restrict__ flag) {
+__global__ void __launch_bounds__(256) coords_keys_kernel(uint32_t n, const int* __restrict__ coords, uint32_t* __restrict__ lo,
+                                                          uint32_t* __restrict__ hi, uint32_t* __restrict__ flag) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= n) return;
   const int bx = coords[3 * (size_t)i], by = coords[3 * (size_t)i + 1], bz = coords[3 * (size_t)i + 2];
   const bool fits = in_range(bx) && in_range(by) && in_range(bz);
-  keys[i] = fits ? pack_key(bx, by, bz) : kNoKey;
+  const unsigned long long key = fits ? pack_key(bx, by, bz) : kNoKey;
+  lo[i] = (uint32_t)key;
+  hi[i] = (uint32_t)(key >> 32);
   if (!fits) *flag = 1u;
 }
 
 // ------------------------------------------------------------------- sort, unique, insert -------------------------------------------------------------------
-// The 64-bit sort is two stable 32-bit sorts, low word first.
-__global__ void __launch_bounds__(256) low_words_kernel(uint32_t n, const unsigned long long* __restrict__ keys, uint32_t* __restrict__ lo) {
+// The sorted keys from what rg::radix_sort_order_2xu32 leaves: the high words in order, the low words through the permutation.
+__global__ void __launch_bounds__(256) join_keys_kernel(uint32_t n, const uint32_t* __restrict__ hi_sorted, const uint32_t* __restrict__ lo,
+                                                        const uint32_t* __restrict__ perm, unsigned long long* __restrict__ sorted) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i < n) lo[i] = (uint32_t)keys[i];
-}
-__global__ void __launch_bounds__(256) high_words_kernel(uint32_t n, const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ perm,
-                                                         uint32_t* __restrict__ hi) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i < n) hi[i] = (uint32_t)(keys[perm[i]] >> 32);
-}
-__global__ void __launch_bounds__(256) gather_keys_kernel(uint32_t n, const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ perm,
-                                                          unsigned long long* __restrict__ sorted) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i < n) sorted[i] = keys[perm[i]];
+  if (i < n) sorted[i] = ((unsigned long long)hi_sorted[i] << 32) | lo[perm[i]];
 }
 
 // first[j]: sorted[j] is a real key and differs from its predecessor.  Against the grid: pos[j] = how many grid keys are smaller,
@@ -136,7 +120,7 @@ __global__ void __launch_bounds__(256) first_kernel(uint32_t n, const unsigned l
   uint32_t p = 0;
   bool found = false;
   if (f && ngrid) {
-    p = lower_bound(grid_keys, ngrid, key);
+    p = rg::lower_bound(grid_keys, ngrid, key);
     found = p < ngrid && grid_keys[p] == key;
   }
   first[j] = f;
@@ -172,7 +156,7 @@ __global__ void __launch_bounds__(256) insert_old_kernel(uint32_t ngrid, const u
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= ngrid) return;
   const unsigned long long key = grid_keys[i];
-  const uint32_t p = n ? lower_bound(sorted, n, key) : 0u;
+  const uint32_t p = n ? rg::lower_bound(sorted, n, key) : 0u;
   const uint32_t at = i + (p ? fresh_incl[p - 1] : 0u);
   if (at >= total) return;
   new_keys[at] = key;
@@ -209,50 +193,36 @@ __global__ void __launch_bounds__(256) insert_new_kernel(uint32_t n, const unsig
 }
 
 struct UniqueView {
-  unsigned long long *keys, *sorted;
-  uint32_t *word, *word_sorted, *perm1, *perm2, *first, *fresh, *pos, *first_incl, *fresh_incl, *flag;
+  unsigned long long* sorted;
+  uint32_t *lo, *hi, *hi_sorted, *perm, *first, *fresh, *pos, *first_incl, *fresh_incl, *flag;   // first, fresh, pos: the sort's scratch before
   void* temp;
-  size_t temp_bytes;
+  size_t temp_bytes, bytes;
 };
-static size_t unique_carve(long long N, void* base, UniqueView* w) {
-  const size_t n = (size_t)N, ts = rg::sort_temp_bytes(n), tc = rg::scan_temp_bytes(n), tb = ts > tc ? ts : tc;
-  size_t off = 0;
-  char* b = static_cast<char*>(base);
-  auto take = [&](size_t bytes) { char* p = b ? b + off : nullptr; off += align256(bytes); return p; };
-  auto u = [](char* p) { return reinterpret_cast<uint32_t*>(p); };
-  auto q = [](char* p) { return reinterpret_cast<unsigned long long*>(p); };
+static UniqueView unique_carve(long long N, void* base) {
+  const size_t n = (size_t)N, ts = rg::sort_temp_bytes(n), tc = rg::scan_temp_bytes(n);
+  rg::Carver c(base);
   UniqueView v;
-  v.keys = q(take(n * 8));
-  v.sorted = q(take(n * 8));
-  v.word = u(take(n * 4));
-  v.word_sorted = u(take(n * 4));
-  v.perm1 = u(take(n * 4));
-  v.perm2 = u(take(n * 4));
-  v.first = u(take(n * 4));
-  v.fresh = u(take(n * 4));
-  v.pos = u(take(n * 4));
-  v.first_incl = u(take(n * 4));
-  v.fresh_incl = u(take(n * 4));
-  v.flag = u(take(4));
-  v.temp = take(tb);
-  v.temp_bytes = tb;
-  if (w) *w = v;
-  return off;
+  v.temp_bytes = ts > tc ? ts : tc;
+  v.sorted = c.take<unsigned long long>(n);
+  for (uint32_t** a : {&v.lo, &v.hi, &v.hi_sorted, &v.perm, &v.first, &v.fresh, &v.pos, &v.first_incl, &v.fresh_incl}) *a = c.take<uint32_t>(n);
+  v.flag = c.take<uint32_t>(1);
+  v.temp = c.take<char>(v.temp_bytes);
+  v.bytes = c.off;
+  return v;
 }
 
-// keys [n] (and the flag) are in the workspace: sort them, mark the first occurrences, look them up in the grid, scan, leave the counts
+// the key words lo, hi [n] (and the flag) are in the workspace: sort them, mark the first occurrences, look them up in the grid, scan,
+// leave the counts
 static int unique_run(uint32_t n, const UniqueView& w, uint32_t ngrid, const unsigned long long* grid_keys, long long* counts3, hipStream_t s) {
   const unsigned nb = blocks_of(n);
-  hipLaunchKernelGGL(low_words_kernel, dim3(nb), dim3(256), 0, s, n, w.keys, w.word);
-  if (rg::radix_sort_pairs_u32(w.temp, w.temp_bytes, w.word, w.word_sorted, nullptr, w.perm1, n, 32, s) != hipSuccess) return RADEGS_ERR_HIP;
-  hipLaunchKernelGGL(high_words_kernel, dim3(nb), dim3(256), 0, s, n, w.keys, w.perm1, w.word);
-  if (rg::radix_sort_pairs_u32(w.temp, w.temp_bytes, w.word, w.word_sorted, w.perm1, w.perm2, n, 32, s) != hipSuccess) return RADEGS_ERR_HIP;
-  hipLaunchKernelGGL(gather_keys_kernel, dim3(nb), dim3(256), 0, s, n, w.keys, w.perm2, w.sorted);
+  if (rg::radix_sort_order_2xu32(w.temp, w.temp_bytes, w.lo, w.hi, w.hi_sorted, w.perm, w.first, w.fresh, w.pos, n, 32, 32, s) != hipSuccess)
+    return RADEGS_ERR_HIP;
+  hipLaunchKernelGGL(join_keys_kernel, dim3(nb), dim3(256), 0, s, n, w.hi_sorted, w.lo, w.perm, w.sorted);
   hipLaunchKernelGGL(first_kernel, dim3(nb), dim3(256), 0, s, n, w.sorted, ngrid, grid_keys, w.first, w.fresh, w.pos);
   if (rg::inclusive_scan_gather_u32(w.temp, w.temp_bytes, w.first, nullptr, w.first_incl, n, s) != hipSuccess) return RADEGS_ERR_HIP;
   if (rg::inclusive_scan_gather_u32(w.temp, w.temp_bytes, w.fresh, nullptr, w.fresh_incl, n, s) != hipSuccess) return RADEGS_ERR_HIP;
   hipLaunchKernelGGL(counts_kernel, dim3(1), dim3(1), 0, s, n, w.first_incl, w.fresh_incl, w.flag, counts3);
-  return last();
+  return rg::launch_status();
 }
 
 // ------------------------------------------------------------------------ integrate ------------------------------------------------------------------------
@@ -524,26 +494,20 @@ struct ExtractView {
   uint32_t *vbase, *block_nv, *block_nt, *nv_incl, *nt_incl;
   unsigned long long* totals;
   void* temp;
-  size_t temp_bytes;
+  size_t temp_bytes, bytes;
 };
-static size_t extract_carve(long long N, void* base, ExtractView* w) {
-  const size_t n = (size_t)N, tb = rg::scan_temp_bytes(n);
-  size_t off = 0;
-  char* b = static_cast<char*>(base);
-  auto take = [&](size_t bytes) { char* p = b ? b + off : nullptr; off += align256(bytes); return p; };
-  auto u = [](char* p) { return reinterpret_cast<uint32_t*>(p); };
+static ExtractView extract_carve(long long N, void* base) {
+  const size_t n = (size_t)N;
+  rg::Carver c(base);
   ExtractView v;
-  v.info = reinterpret_cast<uint8_t*>(take(n * kVox));
-  v.vbase = u(take(n * kVox * 4));
-  v.block_nv = u(take(n * 4));
-  v.block_nt = u(take(n * 4));
-  v.nv_incl = u(take(n * 4));
-  v.nt_incl = u(take(n * 4));
-  v.totals = reinterpret_cast<unsigned long long*>(take(16));
-  v.temp = take(tb);
-  v.temp_bytes = tb;
-  if (w) *w = v;
-  return off;
+  v.temp_bytes = rg::scan_temp_bytes(n);
+  v.info = c.take<uint8_t>(n * kVox);
+  v.vbase = c.take<uint32_t>(n * kVox);
+  for (uint32_t** a : {&v.block_nv, &v.block_nt, &v.nv_incl, &v.nt_incl}) *a = c.take<uint32_t>(n);
+  v.totals = c.take<unsigned long long>(2);
+  v.temp = c.take<char>(v.temp_bytes);
+  v.bytes = c.off;
+  return v;
 }
 
 static bool camera_ok(const float* cam16) {
@@ -562,15 +526,14 @@ static Camera camera_of(const float* cam16) {
   return c;
 }
 static bool positive(float v) { return v > 0.0f && isfinite(v); }
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace rgts
 
 extern "C" {
 
 size_t radegs_tsdf_unique_bytes(long long n) {
-  if (n <= 0 || (unsigned long long)n >= rgts::kMaxItems) return 0;
-  return rgts::unique_carve(n, nullptr, nullptr);
+  if (n <= 0 || (unsigned long long)n >= rg::kMaxItems) return 0;
+  return rgts::unique_carve(n, nullptr).bytes;
 }
 
 int radegs_tsdf_touch(int W, int H, const float* depth, const float* cam16, float depth_scale, float depth_max, float sdf_trunc, float block_size,
@@ -580,63 +543,59 @@ int radegs_tsdf_touch(int W, int H, const float* depth, const float* cam16, floa
     return RADEGS_ERR_INVALID_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream_v);
   const long long samples = (long long)(W / 4) * (H / 4), n = 4 * samples;
-  if ((unsigned long long)n >= rgts::kMaxItems) return RADEGS_ERR_TOO_LARGE;
+  if ((unsigned long long)n >= rg::kMaxItems) return RADEGS_ERR_TOO_LARGE;
   if (n == 0) return hipMemsetAsync(counts3, 0, 3 * sizeof(long long), s) == hipSuccess ? 0 : RADEGS_ERR_HIP;
-  if (!depth || !workspace || workspace_bytes < radegs_tsdf_unique_bytes(n) || !rgts::aligned16(workspace)) return RADEGS_ERR_INVALID_ARG;
-  rgts::UniqueView w;
-  rgts::unique_carve(n, workspace, &w);
+  if (!depth || !workspace || workspace_bytes < radegs_tsdf_unique_bytes(n) || !rg::aligned16(workspace)) return RADEGS_ERR_INVALID_ARG;
+  const rgts::UniqueView w = rgts::unique_carve(n, workspace);
   if (hipMemsetAsync(w.flag, 0, 4, s) != hipSuccess) return RADEGS_ERR_HIP;
-  hipLaunchKernelGGL(rgts::touch_keys_kernel, dim3(rgts::blocks_of((size_t)samples)), dim3(256), 0, s, W, H, depth, rgts::camera_of(cam16), depth_scale,
-                     depth_max, sdf_trunc, block_size, w.keys, w.flag);
+  hipLaunchKernelGGL(rgts::touch_keys_kernel, dim3(rg::blocks_of((size_t)samples)), dim3(256), 0, s, W, H, depth, rgts::camera_of(cam16), depth_scale,
+                     depth_max, sdf_trunc, block_size, w.lo, w.hi, w.flag);
   return rgts::unique_run((uint32_t)n, w, 0u, nullptr, counts3, s);
 }
 
 int radegs_tsdf_unique_plan(long long n, const int* coords, long long ngrid, const unsigned long long* grid_keys, void* workspace,
                             size_t workspace_bytes, long long* counts3, void* stream_v) {
   if (n < 0 || ngrid < 0 || !counts3 || (ngrid && !grid_keys)) return RADEGS_ERR_INVALID_ARG;
-  if ((unsigned long long)n >= rgts::kMaxItems || (unsigned long long)ngrid >= rgts::kMaxItems) return RADEGS_ERR_TOO_LARGE;
+  if ((unsigned long long)n >= rg::kMaxItems || (unsigned long long)ngrid >= rg::kMaxItems) return RADEGS_ERR_TOO_LARGE;
   hipStream_t s = static_cast<hipStream_t>(stream_v);
   if (n == 0) return hipMemsetAsync(counts3, 0, 3 * sizeof(long long), s) == hipSuccess ? 0 : RADEGS_ERR_HIP;
-  if (!coords || !workspace || workspace_bytes < radegs_tsdf_unique_bytes(n) || !rgts::aligned16(workspace)) return RADEGS_ERR_INVALID_ARG;
-  rgts::UniqueView w;
-  rgts::unique_carve(n, workspace, &w);
+  if (!coords || !workspace || workspace_bytes < radegs_tsdf_unique_bytes(n) || !rg::aligned16(workspace)) return RADEGS_ERR_INVALID_ARG;
+  const rgts::UniqueView w = rgts::unique_carve(n, workspace);
   if (hipMemsetAsync(w.flag, 0, 4, s) != hipSuccess) return RADEGS_ERR_HIP;
-  hipLaunchKernelGGL(rgts::coords_keys_kernel, dim3(rgts::blocks_of((size_t)n)), dim3(256), 0, s, (uint32_t)n, coords, w.keys, w.flag);
+  hipLaunchKernelGGL(rgts::coords_keys_kernel, dim3(rg::blocks_of((size_t)n)), dim3(256), 0, s, (uint32_t)n, coords, w.lo, w.hi, w.flag);
   return rgts::unique_run((uint32_t)n, w, (uint32_t)ngrid, grid_keys, counts3, s);
 }
 
 int radegs_tsdf_unique_emit(long long n, const void* workspace, long long n_unique, int* coords_out, void* stream) {
   if (n < 0 || n_unique < 0 || n_unique > n) return RADEGS_ERR_INVALID_ARG;
-  if ((unsigned long long)n >= rgts::kMaxItems) return RADEGS_ERR_TOO_LARGE;
+  if ((unsigned long long)n >= rg::kMaxItems) return RADEGS_ERR_TOO_LARGE;
   if (n == 0 || n_unique == 0) return 0;
   if (!workspace || !coords_out) return RADEGS_ERR_INVALID_ARG;
-  rgts::UniqueView w;
-  rgts::unique_carve(n, const_cast<void*>(workspace), &w);
-  hipLaunchKernelGGL(rgts::unique_emit_kernel, dim3(rgts::blocks_of((size_t)n)), dim3(256), 0, static_cast<hipStream_t>(stream), (uint32_t)n, w.sorted,
+  const rgts::UniqueView w = rgts::unique_carve(n, const_cast<void*>(workspace));
+  hipLaunchKernelGGL(rgts::unique_emit_kernel, dim3(rg::blocks_of((size_t)n)), dim3(256), 0, static_cast<hipStream_t>(stream), (uint32_t)n, w.sorted,
                      w.first, w.first_incl, (uint32_t)n_unique, coords_out);
-  return rgts::last();
+  return rg::launch_status();
 }
 
 int radegs_tsdf_insert_apply(long long n, const void* workspace, long long ngrid, const unsigned long long* grid_keys, const int* grid_slots,
                              long long n_unique, long long n_new, unsigned long long* new_keys, int* new_slots, int* active_slots,
                              int* active_coords, void* stream_v) {
   if (n < 0 || ngrid < 0 || n_unique < 0 || n_new < 0 || n_new > n_unique || n_unique > n) return RADEGS_ERR_INVALID_ARG;
-  if ((unsigned long long)n >= rgts::kMaxItems || (unsigned long long)(ngrid + n_new) >= 0x7FFFFFFFull) return RADEGS_ERR_TOO_LARGE;
+  if ((unsigned long long)n >= rg::kMaxItems || (unsigned long long)(ngrid + n_new) >= 0x7FFFFFFFull) return RADEGS_ERR_TOO_LARGE;
   if ((ngrid && (!grid_keys || !grid_slots)) || ((ngrid + n_new) && (!new_keys || !new_slots)) || (n_unique && (!active_slots || !active_coords)) ||
       (n && !workspace))
     return RADEGS_ERR_INVALID_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream_v);
-  rgts::UniqueView w{};
-  if (n) rgts::unique_carve(n, const_cast<void*>(workspace), &w);
+  const rgts::UniqueView w = n ? rgts::unique_carve(n, const_cast<void*>(workspace)) : rgts::UniqueView{};
   const uint32_t total = (uint32_t)(ngrid + n_new);
   if (ngrid)
-    hipLaunchKernelGGL(rgts::insert_old_kernel, dim3(rgts::blocks_of((size_t)ngrid)), dim3(256), 0, s, (uint32_t)ngrid, grid_keys, grid_slots, (uint32_t)n,
+    hipLaunchKernelGGL(rgts::insert_old_kernel, dim3(rg::blocks_of((size_t)ngrid)), dim3(256), 0, s, (uint32_t)ngrid, grid_keys, grid_slots, (uint32_t)n,
                        w.sorted, w.fresh_incl, total, new_keys, new_slots);
   if (n)
-    hipLaunchKernelGGL(rgts::insert_new_kernel, dim3(rgts::blocks_of((size_t)n)), dim3(256), 0, s, (uint32_t)n, w.sorted, w.first, w.fresh, w.pos,
+    hipLaunchKernelGGL(rgts::insert_new_kernel, dim3(rg::blocks_of((size_t)n)), dim3(256), 0, s, (uint32_t)n, w.sorted, w.first, w.fresh, w.pos,
                        w.first_incl, w.fresh_incl, (uint32_t)ngrid, grid_slots, (uint32_t)n_unique, total, new_keys, new_slots, active_slots,
                        active_coords);
-  return rgts::last();
+  return rg::launch_status();
 }
 
 int radegs_tsdf_integrate(long long n_active, const int* active_slots, const int* active_coords, long long capacity, int W, int H, const float* depth,
@@ -656,12 +615,12 @@ int radegs_tsdf_integrate(long long n_active, const int* active_slots, const int
   else
     hipLaunchKernelGGL(rgts::fuse_view_kernel<false>, dim3((unsigned)n_active), dim3(256), 0, s, active_slots, active_coords, (uint32_t)capacity, W, H, depth,
                        color, c, depth_scale, depth_max, sdf_trunc, tsdf, weight, block_color);
-  return rgts::last();
+  return rg::launch_status();
 }
 
 size_t radegs_tsdf_extract_bytes(long long n) {
   if (n <= 0 || (unsigned long long)n >= (1ull << 19)) return 0;   // 2^19 blocks: every voxel index below 2^31
-  return rgts::extract_carve(n, nullptr, nullptr);
+  return rgts::extract_carve(n, nullptr).bytes;
 }
 
 int radegs_tsdf_extract_plan(long long n, const unsigned long long* keys, const int* slots, const float* tsdf, const float* weight,
@@ -670,17 +629,16 @@ int radegs_tsdf_extract_plan(long long n, const unsigned long long* keys, const 
   if ((unsigned long long)n >= (1ull << 19)) return RADEGS_ERR_TOO_LARGE;
   hipStream_t s = static_cast<hipStream_t>(stream_v);
   if (n == 0) return hipMemsetAsync(counts2, 0, 2 * sizeof(long long), s) == hipSuccess ? 0 : RADEGS_ERR_HIP;
-  if (!keys || !slots || !tsdf || !weight || !workspace || workspace_bytes < radegs_tsdf_extract_bytes(n) || !rgts::aligned16(workspace))
+  if (!keys || !slots || !tsdf || !weight || !workspace || workspace_bytes < radegs_tsdf_extract_bytes(n) || !rg::aligned16(workspace))
     return RADEGS_ERR_INVALID_ARG;
-  rgts::ExtractView w;
-  rgts::extract_carve(n, workspace, &w);
+  const rgts::ExtractView w = rgts::extract_carve(n, workspace);
   if (hipMemsetAsync(w.totals, 0, 16, s) != hipSuccess) return RADEGS_ERR_HIP;
   hipLaunchKernelGGL(rgts::extract_count_kernel, dim3((unsigned)n), dim3(256), 0, s, (uint32_t)n, keys, slots, tsdf, weight, weight_threshold, w.info,
                      w.block_nv, w.block_nt, w.totals);
   if (rg::inclusive_scan_gather_u32(w.temp, w.temp_bytes, w.block_nv, nullptr, w.nv_incl, (size_t)n, s) != hipSuccess) return RADEGS_ERR_HIP;
   if (rg::inclusive_scan_gather_u32(w.temp, w.temp_bytes, w.block_nt, nullptr, w.nt_incl, (size_t)n, s) != hipSuccess) return RADEGS_ERR_HIP;
   hipLaunchKernelGGL(rgts::extract_counts_kernel, dim3(1), dim3(1), 0, s, w.totals, counts2);
-  return rgts::last();
+  return rg::launch_status();
 }
 
 int radegs_tsdf_extract_emit(long long n, const unsigned long long* keys, const int* slots, const float* tsdf, const float* block_color,
@@ -692,8 +650,7 @@ int radegs_tsdf_extract_emit(long long n, const unsigned long long* keys, const 
   if (!keys || !slots || !tsdf || !workspace || (V && !vertices) || (F && !faces) || (V && (block_color == nullptr) != (colors == nullptr)))
     return RADEGS_ERR_INVALID_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream_v);
-  rgts::ExtractView w;
-  rgts::extract_carve(n, const_cast<void*>(workspace), &w);
+  const rgts::ExtractView w = rgts::extract_carve(n, const_cast<void*>(workspace));
   if (block_color)
     hipLaunchKernelGGL(rgts::extract_vertices_kernel<true>, dim3((unsigned)n), dim3(256), 0, s, (uint32_t)n, keys, slots, tsdf, block_color, voxel_size, w.info,
                        w.nv_incl, w.vbase, (uint32_t)V, vertices, colors);
@@ -702,7 +659,7 @@ int radegs_tsdf_extract_emit(long long n, const unsigned long long* keys, const 
                        w.info, w.nv_incl, w.vbase, (uint32_t)V, vertices, colors);
   hipLaunchKernelGGL(rgts::extract_faces_kernel, dim3((unsigned)n), dim3(256), 0, s, (uint32_t)n, keys, slots, tsdf, w.info, w.nt_incl, w.vbase, (uint32_t)F,
                      faces);
-  return rgts::last();
+  return rg::launch_status();
 }
 
 }  // extern "C"

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from diff_gaussian_rasterization import _C
-from tetmesh import ERR_TOO_LARGE, _workspace
+from tetmesh import ERR_TOO_LARGE, _check, _workspace
 from tetmesh import _lib as _tetmesh_lib
 
 _bound = False
@@ -60,13 +60,6 @@ def _lib():
         L.radegs_tetmesh_filter_plan_flags.argtypes = [ll, ll, vp, vp, vp, sz, vp, vp]
         _bound = True
     return L
-
-
-def _check(rc, what):
-    if rc == ERR_TOO_LARGE:
-        raise RuntimeError(f"{what}: the input is larger than the 32-bit sort / scan primitives address (include/radegs.h)")
-    if rc != 0:
-        raise RuntimeError(f"{what} failed ({rc})")
 
 
 def _doubles(values):

@@ -3,6 +3,8 @@ libradegs_sort_check.so, built by rade-gs_amd/build.py) with the instantiation f
 
     sort   d = ((key - key_base) mod 2^32) & (2^end_bit - 1);  perm = np.argsort(d, kind="stable")
            keys_out == keys_in[perm] (the whole key, bits above end_bit included), vals_out == vals_in[perm] (perm itself without vals_in)
+    order  of (major, minor) word pairs:  perm = np.lexsort((minor & mask_minor, major & mask_major))
+           perm_out == perm, major_sorted == major[perm] (the whole word)
     scan   c = vals[idx] (w * h of the packed word in the packed form);  out == cumsum(c) in uint64 cast to uint32,
            packed_out == vals[idx],  *sq_sum == sum(c^2) as an exact uint64
 
@@ -42,6 +44,8 @@ def _lib():
             f.restype, f.argtypes = ci, [vp, sz, vp, vp, vp, vp, sz, ci, vp, vp, ci]
         L.sortcheck_sort_u32_27.restype = ci                     # ..., n, key_base, stream, items
         L.sortcheck_sort_u32_27.argtypes = [vp, sz, vp, vp, vp, vp, sz, u32, vp, ci]
+        L.sortcheck_sort_2xu32.restype = ci                      # temp, temp_bytes, minor, major, major_sorted, perm, s0, s1, s2, n, end bits, stream, n_dev
+        L.sortcheck_sort_2xu32.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, sz, ci, ci, vp, vp]
         L.sortcheck_scan.restype = ci                            # temp, temp_bytes, vals, idx, out, n, stream, packed_out, sq_sum, items
         L.sortcheck_scan.argtypes = [vp, sz, vp, vp, vp, sz, vp, vp, vp, ci]
         _LIB = L
@@ -318,6 +322,113 @@ def test_temp_bytes_bound_every_instantiation():
         for items in (4, 16):
             nb64 = (-(-n // (256 * items)) + 64) & ~63
             assert nb64 * 12 + 4 * n <= L.sortcheck_scan_temp_bytes(n), (n, items)
+
+
+# ------------------------------------------------------- the order of two-word pairs -------------------------------------------------------
+
+PAIR_SIZES = [1, 63, 2047, 2048, 2049, 3 * 2048 + 517]      # the size rule picks the 8-item instantiation: a block is 2048
+PAIR_BITS = [(1, 1), (17, 21), (32, 32)]                    # (minor_end_bit, major_end_bit)
+PAIR_PATTERNS = ["uniform", "equal_major", "equal_minor", "major_only", "ties8"]
+
+
+def _words(n, rng):
+    return rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+
+
+def make_pairs(pattern, n, rng):
+    minor, major = _words(n, rng), _words(n, rng)
+    if pattern == "equal_major":                              # the minor word alone decides
+        major[:] = major[0]
+    elif pattern == "equal_minor":
+        minor[:] = minor[0]
+    elif pattern == "major_only":                             # neighbours in the input that differ in bit 0 of the major word and nowhere else:
+        minor, major = minor[np.arange(n) // 2], major[np.arange(n) // 2] & np.uint32(0xFFFFFFFE)   # the minor sort leaves them adjacent
+        major = major | ((np.arange(n) & 1) ^ rng.integers(0, 2, n)[np.arange(n) // 2]).astype(np.uint32)
+    elif pattern == "ties8":                                  # eight distinct pairs: stability is what orders the rest
+        pick = rng.integers(0, 8, n)
+        minor, major = _words(8, rng)[pick], (_words(8, rng) & np.uint32(0xFFFFFFF8) | np.arange(8, dtype=np.uint32))[pick]
+    else:
+        assert pattern == "uniform", pattern
+    return np.ascontiguousarray(minor), np.ascontiguousarray(major)
+
+
+def ref_pair_perm(minor, major, bits):
+    mask = [np.uint32(0xFFFFFFFF >> (32 - b)) for b in bits]
+    return np.lexsort((minor & mask[0], major & mask[1]))   # stable: ties keep input order
+
+
+def call_sort_2x(minor, major, bits, n=None, m=None, temp_short=0):
+    """One call.  minor / major: host arrays of the capacity `n` (default: their length); m: the device-side count or None.  Returns
+    (rc, major_sorted, perm, untouched) after asserting guards and untouched inputs; untouched: no byte of the outputs, the three scratch
+    arrays or temp was written."""
+    L = _lib()
+    n = len(minor) if n is None else n
+    d_minor, d_major = _upload(minor), _upload(major)
+    d_m = None if m is None else torch.tensor([m], dtype=torch.int64).to(torch.int32).to(DEV)
+    temp_bytes = L.sortcheck_sort_temp_bytes(n) - temp_short
+    temp = Guarded(temp_bytes, TEMP_BYTE)
+    outs = [Guarded(len(minor) * 4, OUT_BYTE) for _ in range(5)]      # major_sorted, perm, s0, s1, s2
+    rc = L.sortcheck_sort_2xu32(temp.ptr, temp_bytes, _ptr(d_minor), _ptr(d_major), *[o.ptr for o in outs], n, bits[0], bits[1], _stream(), _ptr(d_m))
+    if DEV != "cpu":
+        torch.cuda.synchronize()
+    assert temp.guards_intact(), "temp guards overwritten"
+    for name, o in zip(("major_sorted", "perm", "s0", "s1", "s2"), outs):
+        assert o.guards_intact(), name + " guards overwritten"
+    assert _unchanged(d_minor, minor), "minor modified"
+    assert _unchanged(d_major, major), "major modified"
+    assert d_m is None or int(d_m.cpu()[0]) == np.int32(np.uint32(m)), "n_dev modified"
+    untouched = bool((temp.host() == TEMP_BYTE).all()) and all(bool((o.host() == OUT_BYTE).all()) for o in outs)
+    return rc, outs[0].host(np.uint32), outs[1].host(np.uint32), untouched
+
+
+def check_sort_2x(minor, major, bits, perm, m=None):
+    rc, major_sorted, perm_out, _ = call_sort_2x(minor, major, bits, m=m)
+    assert rc == 0, "hip error %d" % rc
+    cnt = len(perm)
+    bad = np.flatnonzero(perm_out[:cnt] != perm.astype(np.uint32))
+    assert bad.size == 0, "perm differs at %d of %d positions, first %d (a stable order keeps ties in input order)" % (bad.size, cnt, bad[0])
+    bad = np.flatnonzero(major_sorted[:cnt] != major[perm])
+    assert bad.size == 0, "major_sorted differs at %d of %d positions, first %d" % (bad.size, cnt, bad[0])
+
+
+@pytest.mark.parametrize("pattern", PAIR_PATTERNS)
+@pytest.mark.parametrize("bits", PAIR_BITS, ids=lambda b: "bits%d_%d" % b)
+def test_sort_2xu32(bits, pattern):
+    """n = 1, a ragged wave, around one block, and three blocks with a ragged tail (the carry across blocks)."""
+    rng = np.random.default_rng(_seed("2xu32", bits, pattern))
+    for n in PAIR_SIZES:
+        minor, major = make_pairs(pattern, n, rng)
+        try:
+            check_sort_2x(minor, major, bits, ref_pair_perm(minor, major, bits))
+        except AssertionError as e:
+            raise AssertionError("n=%d: %s" % (n, e)) from None
+
+
+@pytest.mark.parametrize("bits", PAIR_BITS, ids=lambda b: "bits%d_%d" % b)
+def test_sort_2xu32_device_side_count(bits):
+    """n is a capacity and the count m is read on the device: the first min(m, cap) outputs are the order of the first min(m, cap) pairs,
+    whatever lies behind them in the input."""
+    cap = 2049
+    rng = np.random.default_rng(_seed("2xu32", bits, "n_dev"))
+    minor, major = make_pairs("uniform", cap, rng)           # random all the way: the pairs past m are the poison
+    for m in (0, 1, 2048, 2049, 3049):
+        cnt = min(m, cap)
+        try:
+            check_sort_2x(minor, major, bits, ref_pair_perm(minor[:cnt], major[:cnt], bits), m=m)
+        except AssertionError as e:
+            raise AssertionError("cap=%d m=%d: %s" % (cap, m, e)) from None
+
+
+def test_sort_2xu32_host_side_answers():
+    """Answers given before anything is launched: n = 0, a temp buffer one byte short, an end bit outside 1 .. 32."""
+    minor, major = make_pairs("uniform", 1000, np.random.default_rng(5))
+    rc, _, _, untouched = call_sort_2x(minor, major, (17, 21), n=0)
+    assert rc == 0 and untouched
+    rc, _, _, untouched = call_sort_2x(minor, major, (17, 21), temp_short=1)
+    assert rc == HIP_ERROR_INVALID_VALUE and untouched
+    for bits in ((0, 21), (33, 21), (17, 0), (17, 33)):
+        rc, _, _, untouched = call_sort_2x(minor, major, bits)
+        assert rc == HIP_ERROR_INVALID_VALUE and untouched, bits
 
 
 # ---------------------------------------------------------------- scan ----------------------------------------------------------------

@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ("radegs_tetmesh_plan_bytes", "radegs_tetmesh_plan", "radegs_tetmesh_emit", "radegs_tetra_points", "radegs_cull_alpha_accumulate",
            "radegs_cull_alpha_finish", "radegs_tetmesh_bisect", "radegs_tetmesh_filter_plan_bytes", "radegs_tetmesh_filter_plan",
            "radegs_tetmesh_filter_apply")
-KERNELS = ("occ_pack_kernel", "classify_kernel", "emit_edges_kernel", "gather_kernel", "head_kernel", "scatter_ids_kernel", "vertex_kernel",
+KERNELS = ("occ_pack_kernel", "classify_kernel", "emit_edges_kernel", "head_kernel", "scatter_ids_kernel", "vertex_kernel",
            "face_kernel", "tetra_points_kernel", "cull_alpha_kernel", "cull_finish_kernel", "bisect_kernel", "keep_vertex_kernel", "keep_face_kernel",
            "filter_counts_kernel", "filter_apply_kernel")
 
@@ -132,3 +132,9 @@ def test_tetmesh_kernels_use_no_scratch(code_objects):  # noqa: F811
         assert r["scratch"] == 0, (hits[0], r)
         assert r["vgpr"] <= 64, (hits[0], r)    # streaming kernels: nothing may cost them the 8 waves per SIMD
     assert len(found) == len(KERNELS), sorted(found)
+    # the gather between the two sorts of the edge pairs lives with rg::radix_sort_order_2xu32 (radegs_sort.hip): the same two limits
+    hits = [k for k in code_objects if k.startswith("_ZN2rg") and "13gather_kernelE" in k]
+    assert len(hits) == 1, hits
+    r = code_objects[hits[0]][0]
+    assert r["scratch"] == 0, (hits[0], r)
+    assert r["vgpr"] <= 64, (hits[0], r)
