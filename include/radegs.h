@@ -664,6 +664,51 @@ int radegs_tsdf_extract_emit(long long n, const unsigned long long* keys, const 
                              float voxel_size, const void* workspace, long long V, long long F, float* vertices, long long* faces, float* colors,
                              void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Tanks-and-Temples evaluation: eval_tnt/run.py with registration.py and evaluation.py, which
+ * upstream hands to Open3D on the CPU.  Conventions as above: device pointers unless marked (host), 0 or a negative
+ * RADEGS_ERR_*, work enqueued on `stream`, nothing read back, sizes of 0 legal.  All geometry is float64, one
+ * rounding per operation, in the order written here.  Nearest neighbours are radegs_mesheval_grid_build / _nearest.
+ *
+ * radegs_tnteval_centroids (run.py:97): out [F,3] = ((a + b) + c) / 3 per face; a face with an index outside
+ *   [0, V) yields NaN.
+ * radegs_tnteval_transform: matrix12 (host): rows 0-2 of a 4x4 by rows, finite; out = ((m0 x + m1 y) + m2 z) + m3
+ *   per row.  out may be points.
+ * radegs_tnteval_crop: the selection polygon volume.  orthogonal_axis 0 / 1 / 2 = "X" / "Y" / "Z"; (u, v, w) =
+ *   (1, 2, 0), (0, 2, 1), (0, 1, 2).  polygon_uv [n_polygon,2]: the polygon's u and v coordinates, 3 to 1024
+ *   vertices.  keep[i] = 0 if p[w] < axis_min or p[w] > axis_max; otherwise every edge (i, j = (i + 1) % n) with
+ *   (poly[i].v > p[v]) != (poly[j].v > p[v]) yields the node
+ *   poly[i].u + (p[v] - poly[i].v) / (poly[j].v - poly[i].v) * (poly[j].u - poly[i].u), and keep[i] = 1 iff the
+ *   number of nodes < p[u] is odd.
+ * radegs_tnteval_voxel_plan / _emit: index = floor((p - origin) / voxel) per axis (origin3 (host): the caller
+ *   passes min - 0.5 voxel), each in [0, 2^21); key = ix << 42 | iy << 21 | iz, sorted (stable); counts2 (device) =
+ *   {number of occupied voxels M, 1 if an index lay outside the 21 bits: refuse the call}.  emit: means [M,3] = the
+ *   voxel's points added in index order, divided by their number; counts [M]; voxels ascending by (ix, iy, iz).
+ *   workspace: radegs_tnteval_voxel_bytes(N), 16-byte aligned, untouched until emit has run.
+ * radegs_tnteval_pair_sums: over the pairs q with 0 <= index[q] < NT, s = moved[q], t = target[index[q]]:
+ *   out18 = {count, sum s [3], sum t [3], sum (dx^2 + dy^2) + dz^2 of s - t, sum (t - mt)(s - ms)^T [3][3] by rows,
+ *   sum |s - ms|^2}, ms = sum s / count and mt likewise, formed on the device.  Fixed order: repeatable bit for
+ *   bit.  workspace: radegs_tnteval_sums_bytes(), 16-byte aligned.
+ * radegs_tnteval_histogram: numpy.histogram over explicit ascending edges [n_edges] (2 to 4096): hist [n_edges - 1],
+ *   bin b = edges[b] <= d < edges[b + 1], the last bin closed on both sides, NaN in no bin; below[0] = the number
+ *   of d < threshold.  Both are zeroed by the call.
+ * --------------------------------------------------------------------------------------------------------------- */
+int radegs_tnteval_centroids(long long V, long long F, const double* vertices /* [V,3] */, const long long* faces /* [F,3] */, double* out /* [F,3] */,
+                             void* stream);
+int radegs_tnteval_transform(long long N, const double* points /* [N,3] */, const double* matrix12, double* out /* [N,3] */, void* stream);
+int radegs_tnteval_crop(long long N, const double* points, int orthogonal_axis, double axis_min, double axis_max, int n_polygon, const double* polygon_uv,
+                        unsigned char* keep /* [N] */, void* stream);
+size_t radegs_tnteval_voxel_bytes(long long N);
+int radegs_tnteval_voxel_plan(long long N, const double* points, const double* origin3, double voxel, void* workspace, size_t workspace_bytes,
+                              long long* counts2, void* stream);
+int radegs_tnteval_voxel_emit(long long N, const double* points, const void* workspace, long long M, double* means /* [M,3] */, int* counts /* [M] */,
+                              void* stream);
+size_t radegs_tnteval_sums_bytes(void);
+int radegs_tnteval_pair_sums(long long Q, const double* moved /* [Q,3] */, long long NT, const double* target /* [NT,3] */, const long long* index /* [Q] */,
+                             void* workspace, size_t workspace_bytes, double* out18, void* stream);
+int radegs_tnteval_histogram(long long N, const double* dist, int n_edges, const double* edges, double threshold, long long* hist, long long* below,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -103,7 +103,11 @@ EXPORTED_SYMBOLS = ("radegs_forward", "radegs_backward", "radegs_backward_ordere
                     "radegs_mesheval_cull_vertices", "radegs_tetmesh_filter_plan_flags",
                     # TSDF fusion (bound in tsdf.py)
                     "radegs_tsdf_unique_bytes", "radegs_tsdf_touch", "radegs_tsdf_unique_plan", "radegs_tsdf_unique_emit", "radegs_tsdf_insert_apply",
-                    "radegs_tsdf_integrate", "radegs_tsdf_extract_bytes", "radegs_tsdf_extract_plan", "radegs_tsdf_extract_emit")
+                    "radegs_tsdf_integrate", "radegs_tsdf_extract_bytes", "radegs_tsdf_extract_plan", "radegs_tsdf_extract_emit",
+                    # Tanks-and-Temples evaluation (bound in tnt_eval.py)
+                    "radegs_tnteval_centroids", "radegs_tnteval_transform", "radegs_tnteval_crop", "radegs_tnteval_voxel_bytes",
+                    "radegs_tnteval_voxel_plan", "radegs_tnteval_voxel_emit", "radegs_tnteval_sums_bytes", "radegs_tnteval_pair_sums",
+                    "radegs_tnteval_histogram")
 
 _lib = None
 # test hook: when True, the per-Gaussian accumulation scratch of the last backward is kept in LAST_ACC
