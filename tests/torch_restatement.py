@@ -171,6 +171,9 @@ def render(means3D, opacities, viewmatrix, projmatrix, campos, tanfovx, tanfovy,
         G = torch.exp(power)
         G.retain_grad()
         G_list.append((i, G, dx, dy))
+        # clamp_max's autograd GATES the gradient where op G > 0.99; the reference's backward does not (backward.cu:852 min(0.99f, ...), then
+        # :979 dL_dG = con_o.w * dL_dalpha with no gate).  This restatement is therefore silent, or wrong, for clamped pairs -- the scenes it
+        # is used on have next to none.  tests/blend_cases.py::restate is the float64 reference with the straight-through clamp.
         alpha = torch.clamp_max(op[i] * G, f32(0.99))
         ok = in_rect & ~done & ~(power > 0) & ~(alpha < float(np.float32(1.0) / np.float32(255.0)))
         test_T = T * (1 - alpha)
