@@ -709,6 +709,54 @@ int radegs_tnteval_pair_sums(long long Q, const double* moved /* [Q,3] */, long 
 int radegs_tnteval_histogram(long long N, const double* dist, int n_edges, const double* edges, double threshold, long long* hist, long long* below,
                              void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Tanks-and-Temples mesh culling: eval_tnt/cull_mesh.py, which upstream hands to pyrender / EGL
+ * (the depth maps) and to eager torch (Mesher.point_masks).  Conventions as above: device pointers, 0 or a negative
+ * RADEGS_ERR_*, work enqueued on `stream`, nothing read back, sizes of 0 legal.  The faces are then filtered with
+ * radegs_tetmesh_filter_plan_flags / radegs_tetmesh_filter_apply.
+ *
+ * radegs_tntcull_render_begin / _finish: depth [B,H,W] of the mesh as B cameras see it; a pixel no triangle covers
+ *   reads 0.  float64, one rounding per operation, in the order written here (DESIGN.md 11 N11 gives the reasons).
+ *   w2c [B,12]: rows 0-2 of each world-to-camera matrix by rows; the camera looks down -z, +y is up, image row 0 is
+ *   at the top.  Per vertex: X = ((m0 x + m1 y) + m2 z) + m3, Y and Z likewise, d = -Z.
+ *   Near clip: Sutherland-Hodgman against d >= znear in camera space, vertex order kept, walking 0 -> 1 -> 2 -> 0; a
+ *   quad is fanned from its first vertex.  Where an edge meets the plane: from the end a that is smaller in
+ *   (X, then Y, then d), t = (znear - d_a) / (d_b - d_a), X = X_a + t (X_b - X_a), Y likewise, d = znear.
+ *   Window: x = fx X / d + cx, y = cy - fy Y / d; pixel (i, j) is sampled at (j + 0.5, i + 0.5).
+ *   Edge a -> b at p: from the end that is smaller in (x, then y), (bx - ax)(py - ay) - (by - ay)(px - ax), negated if
+ *   that end is b.  area = the edge 0 -> 1 at vertex 2; area == 0 (or NaN): skipped; area < 0: all three values are
+ *   negated.  Candidates: the pixel centres of the closed bounding box, j in [ceil(xmin - 0.5), floor(xmax - 0.5)]
+ *   cut to [0, W - 1], rows likewise.  Covered iff E0, E1, E2 >= 0 (Ek: the edge opposite vertex k) and
+ *   (E0 + E1) + E2 > 0; d = ((E0 + E1) + E2) / ((E0 / d0 + E1 / d1) + E2 / d2); kept iff znear <= d <= zfar; rounded
+ *   to float32; a pixel keeps the minimum (a 32-bit unsigned atomic minimum on the bits: independent of face order).
+ *   begin clears the maps, sets every triangle up and draws the boxes of at most 256 pixel centres; larger boxes go
+ *   to a queue in the workspace, in chunks of 1024 pixel centres; finish drains the queue and resolves untouched
+ *   pixels to 0.  Both take the same arguments; depth is not to be read in between.  A chunk that finds the queue
+ *   full is drawn by begin itself: any workspace of at least radegs_tntcull_render_bytes(0, 0) bytes (the header)
+ *   gives the same maps, radegs_tntcull_render_bytes(F, B) is the size that keeps begin fast.  16-byte aligned.
+ *   stats4 (device, may be NULL): {queue chunks asked for, triangles drawn by begin, triangles queued, chunks begin
+ *   drew because the queue was full}.  znear > 0, zfar > znear, 2 <= H, W <= 32768, B <= 65535, V, F < 2^31; faces with
+ *   an index outside [0, V) draw nothing.
+ * radegs_tntcull_count_views (cull_mesh.py:132-170 at forecast_radius 0): counts[i] += the number of the B cameras
+ *   that see point i.  float32, one rounding per operation.  w2c [B,12] float32.  Per camera:
+ *   cam = ((m0 x + m1 y) + m2 z) + m3 per row; z = z_c + 1e-8; u = (fx x_c + cx z_c) / z, v = (fy y_c + cy z_c) / z;
+ *   in_frustum = 0 <= u <= W - 1 and 0 <= v <= H - 1 and z > 0; the depth map [H,W] is sampled bilinearly at
+ *   ix = min(W - 1, max(((u / (W - 1) * 2 - 1) + 1) / 2 * (W - 1), 0)), iy likewise (grid_sample, align_corners = True,
+ *   border padding): x0 = floor(ix), weights nw = (x0 + 1 - ix)(y0 + 1 - iy), ne = (ix - x0)(y0 + 1 - iy),
+ *   sw = (x0 + 1 - ix)(iy - y0), se = (ix - x0)(iy - y0), s = (((0 + nw D[y0][x0]) + ne D[y0][x0 + 1]) +
+ *   sw D[y0 + 1][x0]) + se D[y0 + 1][x0 + 1], a neighbour outside the image left out;
+ *   seen = in_frustum and (s > 0 ? z < s + eps : true).
+ * --------------------------------------------------------------------------------------------------------------- */
+size_t radegs_tntcull_render_bytes(long long F, int B);
+int radegs_tntcull_render_begin(long long V, long long F, const double* vertices /* [V,3] */, const long long* faces /* [F,3] */, int B,
+                                const double* w2c /* [B,12] */, int H, int W, double fx, double fy, double cx, double cy, double znear, double zfar,
+                                void* workspace, size_t workspace_bytes, float* depth /* [B,H,W] */, void* stream);
+int radegs_tntcull_render_finish(long long V, long long F, const double* vertices, const long long* faces, int B, const double* w2c, int H, int W,
+                                 double fx, double fy, double cx, double cy, double znear, double zfar, const void* workspace, size_t workspace_bytes,
+                                 float* depth, long long* stats4, void* stream);
+int radegs_tntcull_count_views(long long N, const float* points /* [N,3] */, int B, int H, int W, const float* depths /* [B,H,W] */,
+                               const float* w2c /* [B,12] */, float fx, float fy, float cx, float cy, float eps, int* counts /* [N] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -107,7 +107,9 @@ EXPORTED_SYMBOLS = ("radegs_forward", "radegs_backward", "radegs_backward_ordere
                     # Tanks-and-Temples evaluation (bound in tnt_eval.py)
                     "radegs_tnteval_centroids", "radegs_tnteval_transform", "radegs_tnteval_crop", "radegs_tnteval_voxel_bytes",
                     "radegs_tnteval_voxel_plan", "radegs_tnteval_voxel_emit", "radegs_tnteval_sums_bytes", "radegs_tnteval_pair_sums",
-                    "radegs_tnteval_histogram")
+                    "radegs_tnteval_histogram",
+                    # Tanks-and-Temples mesh culling (bound in tnt_cull.py)
+                    "radegs_tntcull_render_bytes", "radegs_tntcull_render_begin", "radegs_tntcull_render_finish", "radegs_tntcull_count_views")
 
 _lib = None
 # test hook: when True, the per-Gaussian accumulation scratch of the last backward is kept in LAST_ACC
