@@ -24,6 +24,7 @@
 #include <math.h>
 
 #include "../../include/radegs.h"
+#include "rg_reduce.h"
 
 namespace rgap {
 
@@ -240,16 +241,11 @@ __global__ void __launch_bounds__(NT) appearance_head_fwd_kernel(const Geo g, co
 }
 
 __global__ void __launch_bounds__(256) appearance_loss_final_kernel(const double* __restrict__ partial, int n, double inv_n, float* __restrict__ loss) {
-  __shared__ double s[256];
-  double a = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) a += partial[i];
-  s[threadIdx.x] = a;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) loss[0] = (float)(s[0] * inv_n);
+  __shared__ double sh[256];
+  double a[1] = {0.0};
+  rg::add_partials(partial, n, a);
+  rg::block_sum(a, sh);
+  if (threadIdx.x == 0) loss[0] = (float)(a[0] * inv_n);
 }
 
 // ---- backward, by full-resolution tile: d image, dZ2, partial dW2 / db2 / dW3 / db3 -----------------------------------------------

@@ -20,13 +20,13 @@
 
 #include "../../include/radegs.h"
 #include "rg_prims.h"
+#include "rg_reduce.h"
 #include "rg_workspace.h"
 
 namespace rgme {
 
 using rg::kMaxItems;
 constexpr double kMaxSubdiv = 30000.0;   // n1, n2 beyond this: the per-triangle count would leave 32 bits
-constexpr int kSumBlocks = 1024;
 
 // ---------------------------------------------------------------- triangle sampling ----------------------------------------------------------------
 struct Tri {
@@ -270,37 +270,23 @@ __global__ void __launch_bounds__(256) nearest_kernel(uint32_t N, const uint32_t
   index[q] = hit ? (long long)best_i : -1ll;
 }
 
-// sum and count of dist < max_dist in a fixed order: per-block partials over a grid-stride loop, then one block over the partials
-__device__ __forceinline__ void block_reduce2(double& s, double& n, double* sh) {
-  sh[threadIdx.x] = s;
-  sh[256 + threadIdx.x] = n;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) {
-      sh[threadIdx.x] += sh[threadIdx.x + w];
-      sh[256 + threadIdx.x] += sh[256 + threadIdx.x + w];
-    }
-    __syncthreads();
-  }
-  s = sh[0];
-  n = sh[256];
-}
+// sum and count of dist < max_dist in the fixed order of rg_reduce.h: per-block partials over a grid-stride loop, then one block over them
 __global__ void __launch_bounds__(256) below_partial_kernel(long long Q, const double* __restrict__ dist, double max_dist, double* __restrict__ partial) {
   __shared__ double sh[512];
-  double s = 0.0, n = 0.0;
+  double a[2] = {0.0, 0.0};
   for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < Q; q += (long long)gridDim.x * 256) {
     const double d = dist[q];
-    if (d < max_dist) { s += d; n += 1.0; }
+    if (d < max_dist) { a[0] += d; a[1] += 1.0; }
   }
-  block_reduce2(s, n, sh);
-  if (threadIdx.x == 0) { partial[2 * blockIdx.x] = s; partial[2 * blockIdx.x + 1] = n; }
+  rg::block_sum(a, sh);
+  if (threadIdx.x == 0) { partial[2 * blockIdx.x] = a[0]; partial[2 * blockIdx.x + 1] = a[1]; }
 }
 __global__ void __launch_bounds__(256) below_final_kernel(int nblocks, const double* __restrict__ partial, double* __restrict__ out2) {
   __shared__ double sh[512];
-  double s = 0.0, n = 0.0;
-  for (int b = threadIdx.x; b < nblocks; b += 256) { s += partial[2 * b]; n += partial[2 * b + 1]; }
-  block_reduce2(s, n, sh);
-  if (threadIdx.x == 0) { out2[0] = s; out2[1] = n; }
+  double a[2] = {0.0, 0.0};
+  rg::add_partials(partial, nblocks, a);
+  rg::block_sum(a, sh);
+  if (threadIdx.x == 0) { out2[0] = a[0]; out2[1] = a[1]; }
 }
 
 // ---------------------------------------------------------------------- masks ----------------------------------------------------------------------
@@ -474,15 +460,14 @@ int radegs_mesheval_nearest(long long N, const void* grid_workspace, const doubl
   return rg::launch_status();
 }
 
-size_t radegs_mesheval_sum_bytes(void) { return rg::align256(2 * rgme::kSumBlocks * sizeof(double)); }
+size_t radegs_mesheval_sum_bytes(void) { return rg::align256(2 * rg::kSumBlocks * sizeof(double)); }
 
 int radegs_mesheval_sum_below(long long Q, const double* dist, double max_dist, void* workspace, size_t workspace_bytes, double* out2, void* stream_v) {
   if (Q < 0 || !out2) return RADEGS_ERR_INVALID_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream_v);
   if (Q == 0) return hipMemsetAsync(out2, 0, 2 * sizeof(double), s) == hipSuccess ? 0 : RADEGS_ERR_HIP;
   if (!dist || !workspace || workspace_bytes < radegs_mesheval_sum_bytes() || (reinterpret_cast<uintptr_t>(workspace) & 7)) return RADEGS_ERR_INVALID_ARG;
-  const size_t want = (size_t)((Q + 255) / 256);
-  const int nb = (int)(want < (size_t)rgme::kSumBlocks ? want : (size_t)rgme::kSumBlocks);
+  const int nb = rg::sum_blocks(Q);
   double* partial = static_cast<double*>(workspace);
   hipLaunchKernelGGL(rgme::below_partial_kernel, dim3(nb), dim3(256), 0, s, Q, dist, max_dist, partial);
   hipLaunchKernelGGL(rgme::below_final_kernel, dim3(1), dim3(256), 0, s, nb, partial, out2);

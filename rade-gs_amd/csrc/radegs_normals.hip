@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "../../include/radegs.h"
+#include "rg_reduce.h"
 
 namespace rgn {
 
@@ -178,17 +179,12 @@ __global__ void __launch_bounds__(256) normal_loss_fwd_kernel(const Maps m, cons
 
 __global__ void __launch_bounds__(256) normal_loss_final_kernel(const double* __restrict__ partial, int nblocks, double inv_hw, float r,
                                                                float* __restrict__ loss /* [3]: loss, mean err0, mean err1 */) {
-  __shared__ double s0[256], s1[256];
-  double a = 0.0, b = 0.0;
-  for (int i = threadIdx.x; i < nblocks; i += 256) { a += partial[2 * (size_t)i]; b += partial[2 * (size_t)i + 1]; }
-  s0[threadIdx.x] = a; s1[threadIdx.x] = b;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) { s0[threadIdx.x] += s0[threadIdx.x + o]; s1[threadIdx.x] += s1[threadIdx.x + o]; }
-    __syncthreads();
-  }
+  __shared__ double sh[512];
+  double a[2] = {0.0, 0.0};
+  rg::add_partials(partial, nblocks, a);
+  rg::block_sum(a, sh);
   if (threadIdx.x == 0) {
-    const float m0 = (float)(s0[0] * inv_hw), m1 = (float)(s1[0] * inv_hw);
+    const float m0 = (float)(a[0] * inv_hw), m1 = (float)(a[1] * inv_hw);
     loss[0] = (1.0f - r) * m0 + r * m1;
     loss[1] = m0; loss[2] = m1;
   }

@@ -15,6 +15,7 @@
 #include <math.h>
 
 #include "../../include/radegs.h"
+#include "rg_reduce.h"
 
 namespace rgp {
 
@@ -93,17 +94,12 @@ __global__ void __launch_bounds__(256) photometric_fwd_kernel(const Img im, cons
 
 __global__ void __launch_bounds__(256) photometric_final_kernel(const double* __restrict__ partial, int nblocks, double inv_n, float lambda,
                                                                float* __restrict__ out3 /* loss, l1, ssim */) {
-  __shared__ double s0[256], s1[256];
-  double a = 0.0, b = 0.0;
-  for (int i = threadIdx.x; i < nblocks; i += 256) { a += partial[2 * (size_t)i]; b += partial[2 * (size_t)i + 1]; }
-  s0[threadIdx.x] = a; s1[threadIdx.x] = b;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) { s0[threadIdx.x] += s0[threadIdx.x + o]; s1[threadIdx.x] += s1[threadIdx.x + o]; }
-    __syncthreads();
-  }
+  __shared__ double sh[512];
+  double a[2] = {0.0, 0.0};
+  rg::add_partials(partial, nblocks, a);
+  rg::block_sum(a, sh);
   if (threadIdx.x == 0) {
-    const float l1 = (float)(s0[0] * inv_n), ss = (float)(s1[0] * inv_n);
+    const float l1 = (float)(a[0] * inv_n), ss = (float)(a[1] * inv_n);
     out3[0] = (1.0f - lambda) * l1 + lambda * (1.0f - ss);
     out3[1] = l1; out3[2] = ss;
   }

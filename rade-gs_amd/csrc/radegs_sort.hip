@@ -434,20 +434,32 @@ __global__ void __launch_bounds__(256) gather_kernel(uint32_t cap, const uint32_
   if (i >= cap || (n_dev && i >= *n_dev)) return;
   dst[i] = src[idx[i]];
 }
+// joined[i] = the i-th pair in order as one 64-bit key, the raw words, over the same range.  major_sorted[i] is major[perm[i]]: the
+// second sort moved the whole word.
+__global__ void __launch_bounds__(256) join_kernel(uint32_t cap, const uint32_t* __restrict__ n_dev, const uint32_t* __restrict__ major_sorted,
+                                                   const uint32_t* __restrict__ lo, const uint32_t* __restrict__ perm,
+                                                   unsigned long long* __restrict__ joined) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= cap || (n_dev && i >= *n_dev)) return;
+  joined[i] = ((unsigned long long)major_sorted[i] << 32) | lo[perm[i]];
+}
 }  // namespace
 
 // The order of (major, minor) word pairs (rg_prims.h): two stable sorts, the minor word first, with one gather of the major word through
-// the first permutation in between.
+// the first permutation in between; then, if asked for, the join of the two words.
 hipError_t radix_sort_order_2xu32(void* temp, size_t temp_bytes, const uint32_t* minor, const uint32_t* major, uint32_t* major_sorted,
                                   uint32_t* perm, uint32_t* s0, uint32_t* s1, uint32_t* s2, size_t n, int minor_end_bit, int major_end_bit,
-                                  hipStream_t stream, const uint32_t* n_dev) {
+                                  hipStream_t stream, const uint32_t* n_dev, unsigned long long* joined) {
   if (n == 0) return hipSuccess;
   if (minor_end_bit < 1 || minor_end_bit > 32 || major_end_bit < 1 || major_end_bit > 32 || temp_bytes < sort_temp_bytes(n) || n > kMaxItems)
     return hipErrorInvalidValue;
   hipError_t e = radix_sort_pairs_u32(temp, temp_bytes, minor, s0, nullptr, s1, n, minor_end_bit, stream, n_dev);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(gather_kernel, dim3(blocks_of(n)), dim3(256), 0, stream, (uint32_t)n, n_dev, major, s1, s2);
-  return radix_sort_pairs_u32(temp, temp_bytes, s2, major_sorted, s1, perm, n, major_end_bit, stream, n_dev);
+  e = radix_sort_pairs_u32(temp, temp_bytes, s2, major_sorted, s1, perm, n, major_end_bit, stream, n_dev);
+  if (e != hipSuccess || !joined) return e;
+  hipLaunchKernelGGL(join_kernel, dim3(blocks_of(n)), dim3(256), 0, stream, (uint32_t)n, n_dev, major_sorted, minor, perm, joined);
+  return hipGetLastError();
 }
 
 }  // namespace rg

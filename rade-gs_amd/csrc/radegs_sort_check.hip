@@ -27,11 +27,20 @@ int sortcheck_sort_u32_27(void* temp, size_t temp_bytes, const uint32_t* keys_in
   return (int)rg::radix_sort_pairs_u32_27(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, n, key_base, (hipStream_t)stream, items);
 }
 
+// Two entry points, because a C symbol cannot take an optional argument: a caller written for the 14-argument form would leave `joined` to
+// whatever the stack holds, and the sort would write there.  The first keeps that form (no joined key), the second passes the pointer through
+// (null allowed).
 int sortcheck_sort_2xu32(void* temp, size_t temp_bytes, const uint32_t* minor, const uint32_t* major, uint32_t* major_sorted, uint32_t* perm,
                          uint32_t* s0, uint32_t* s1, uint32_t* s2, size_t n, int minor_end_bit, int major_end_bit, void* stream,
                          const uint32_t* n_dev) {
   return (int)rg::radix_sort_order_2xu32(temp, temp_bytes, minor, major, major_sorted, perm, s0, s1, s2, n, minor_end_bit, major_end_bit,
                                          (hipStream_t)stream, n_dev);
+}
+int sortcheck_sort_2xu32_joined(void* temp, size_t temp_bytes, const uint32_t* minor, const uint32_t* major, uint32_t* major_sorted, uint32_t* perm,
+                                uint32_t* s0, uint32_t* s1, uint32_t* s2, size_t n, int minor_end_bit, int major_end_bit, void* stream,
+                                const uint32_t* n_dev, unsigned long long* joined) {
+  return (int)rg::radix_sort_order_2xu32(temp, temp_bytes, minor, major, major_sorted, perm, s0, s1, s2, n, minor_end_bit, major_end_bit,
+                                         (hipStream_t)stream, n_dev, joined);
 }
 
 int sortcheck_scan(void* temp, size_t temp_bytes, const uint32_t* vals, const uint32_t* idx, uint32_t* out, size_t n, void* stream,

@@ -2,7 +2,7 @@
 // registration.py and evaluation.py, which upstream hands to Open3D on the CPU.
 //     run.py:94-108                        vertices + face centroids                centroid_kernel
 //     registration.py:113-131              transform, crop, voxel / uniform thinning transform_kernel, crop_kernel, voxel_key_kernel -> the two-word
-//                                                                                   sort -> join / first -> scan -> voxel_emit_kernel
+//                                                                                   sort (with the joined key) -> first -> scan -> voxel_emit_kernel
 //     registration.py:154-161, 193-200     ICP, point to point with scaling         transform_kernel, (mesh_eval's grid), pair_sums / pair_moments
 //     evaluation.py:96-98, 173-196         distances, histogram, F-score            (mesh_eval's grid), histogram_kernel
 //
@@ -19,6 +19,7 @@
 
 #include "../../include/radegs.h"
 #include "rg_prims.h"
+#include "rg_reduce.h"
 #include "rg_workspace.h"
 
 namespace rgte {
@@ -27,7 +28,6 @@ using rg::blocks_of;
 using rg::kMaxItems;
 constexpr int kMaxPolygon = 1024;        // vertices of the crop polygon staged in LDS (16 KB)
 constexpr int kMaxEdges = 4096;          // histogram edges staged in LDS (32 KB) next to their counters (16 KB)
-constexpr int kSumBlocks = 1024;
 constexpr int kVoxelBits = 21;
 constexpr unsigned long long kNoKey = ~0ull;
 
@@ -99,12 +99,6 @@ __global__ void __launch_bounds__(256) voxel_key_kernel(uint32_t N, const double
   if (!fits) *flag = 1u;
 }
 
-__global__ void __launch_bounds__(256) join_first_kernel(uint32_t N, const uint32_t* __restrict__ hi_sorted, const uint32_t* __restrict__ lo,
-                                                         const uint32_t* __restrict__ perm, unsigned long long* __restrict__ sorted) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i < N) sorted[i] = ((unsigned long long)hi_sorted[i] << 32) | lo[perm[i]];
-}
-
 __global__ void __launch_bounds__(256) first_kernel(uint32_t N, const unsigned long long* __restrict__ sorted, uint32_t* __restrict__ first) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i < N) first[i] = i == 0 || sorted[i] != sorted[i - 1];
@@ -159,24 +153,7 @@ static VoxelView voxel_carve(long long N, void* base) {
 }
 
 // ------------------------------------------------------------ sums over the matched pairs ------------------------------------------------------------
-// K sums in a fixed order, the pattern of radegs_mesheval.hip's below_partial / below_final: per-block partials over a grid-stride loop, a
-// tree over the block in LDS, then one block over the partials.
-template <int K>
-__device__ __forceinline__ void block_reduce(double (&v)[K], double* sh) {
-#pragma unroll
-  for (int k = 0; k < K; k++) sh[k * 256 + threadIdx.x] = v[k];
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) {
-#pragma unroll
-      for (int k = 0; k < K; k++) sh[k * 256 + threadIdx.x] += sh[k * 256 + threadIdx.x + w];
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int k = 0; k < K; k++) v[k] = sh[k * 256];
-}
-
+// K sums in the fixed order of rg_reduce.h: per-block partials over a grid-stride loop, then one block over the partials.
 // a pair: query q with index[q] in [0, NT); s = moved[q], t = target[index[q]]
 struct Pair {
   double s[3], t[3];
@@ -210,18 +187,15 @@ __global__ void __launch_bounds__(256) pair_sums_partial_kernel(long long Q, con
     }
     a[7] += (dx * dx + dy * dy) + dz * dz;
   }
-  block_reduce<8>(a, sh);
+  rg::block_sum(a, sh);
   if (threadIdx.x < 8) partial[8 * blockIdx.x + threadIdx.x] = a[threadIdx.x];
 }
 // out[0..8) = the sums; means6 = sum s / count, sum t / count (zeros without a pair)
 __global__ void __launch_bounds__(256) pair_sums_final_kernel(int nblocks, const double* __restrict__ partial, double* __restrict__ out, double* __restrict__ means6) {
   __shared__ double sh[8 * 256];
   double a[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int b = threadIdx.x; b < nblocks; b += 256) {
-#pragma unroll
-    for (int k = 0; k < 8; k++) a[k] += partial[8 * b + k];
-  }
-  block_reduce<8>(a, sh);
+  rg::add_partials(partial, nblocks, a);
+  rg::block_sum(a, sh);
   if (threadIdx.x < 8) out[threadIdx.x] = a[threadIdx.x];
   if (threadIdx.x < 6) means6[threadIdx.x] = a[0] > 0.0 ? a[1 + threadIdx.x] / a[0] : 0.0;
 }
@@ -243,17 +217,14 @@ __global__ void __launch_bounds__(256) pair_moments_partial_kernel(long long Q, 
       for (int c = 0; c < 3; c++) a[3 * r + c] += dt[r] * ds[c];
     a[9] += (ds[0] * ds[0] + ds[1] * ds[1]) + ds[2] * ds[2];
   }
-  block_reduce<10>(a, sh);
+  rg::block_sum(a, sh);
   if (threadIdx.x < 10) partial[10 * blockIdx.x + threadIdx.x] = a[threadIdx.x];
 }
 __global__ void __launch_bounds__(256) pair_moments_final_kernel(int nblocks, const double* __restrict__ partial, double* __restrict__ out) {
   __shared__ double sh[10 * 256];
   double a[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int b = threadIdx.x; b < nblocks; b += 256) {
-#pragma unroll
-    for (int k = 0; k < 10; k++) a[k] += partial[10 * b + k];
-  }
-  block_reduce<10>(a, sh);
+  rg::add_partials(partial, nblocks, a);
+  rg::block_sum(a, sh);
   if (threadIdx.x < 10) out[threadIdx.x] = a[threadIdx.x];
 }
 
@@ -264,7 +235,7 @@ struct SumsView {
 static SumsView sums_carve(void* base) {
   rg::Carver c(base);
   SumsView v;
-  v.partial = c.take<double>(10 * (size_t)kSumBlocks);
+  v.partial = c.take<double>(10 * (size_t)rg::kSumBlocks);
   v.means6 = c.take<double>(6);
   v.bytes = c.off;
   return v;
@@ -361,9 +332,9 @@ int radegs_tnteval_voxel_plan(long long N, const double* points, const double* o
   const unsigned nb = rg::blocks_of((size_t)N);
   if (hipMemsetAsync(w.flag, 0, sizeof(uint32_t), s) != hipSuccess) return RADEGS_ERR_HIP;
   hipLaunchKernelGGL(rgte::voxel_key_kernel, dim3(nb), dim3(256), 0, s, n, points, origin3[0], origin3[1], origin3[2], voxel, w.lo, w.hi, w.flag);
-  if (rg::radix_sort_order_2xu32(w.temp, w.temp_bytes, w.lo, w.hi, w.hi_sorted, w.perm, w.first, w.incl, w.spare, (size_t)N, 32, 32, s) != hipSuccess)
+  if (rg::radix_sort_order_2xu32(w.temp, w.temp_bytes, w.lo, w.hi, w.hi_sorted, w.perm, w.first, w.incl, w.spare, (size_t)N, 32, 32, s, nullptr,
+                                 w.sorted) != hipSuccess)
     return RADEGS_ERR_HIP;
-  hipLaunchKernelGGL(rgte::join_first_kernel, dim3(nb), dim3(256), 0, s, n, w.hi_sorted, w.lo, w.perm, w.sorted);
   hipLaunchKernelGGL(rgte::first_kernel, dim3(nb), dim3(256), 0, s, n, w.sorted, w.first);
   if (rg::inclusive_scan_gather_u32(w.temp, w.temp_bytes, w.first, nullptr, w.incl, (size_t)N, s) != hipSuccess) return RADEGS_ERR_HIP;
   hipLaunchKernelGGL(rgte::voxel_counts_kernel, dim3(1), dim3(1), 0, s, n, w.incl, w.flag, counts2);
@@ -390,8 +361,7 @@ int radegs_tnteval_pair_sums(long long Q, const double* moved, long long NT, con
   if (Q == 0 || NT == 0) return hipMemsetAsync(out18, 0, 18 * sizeof(double), s) == hipSuccess ? 0 : RADEGS_ERR_HIP;
   if (!moved || !target || !index || !workspace || workspace_bytes < radegs_tnteval_sums_bytes() || !rg::aligned16(workspace)) return RADEGS_ERR_INVALID_ARG;
   const rgte::SumsView w = rgte::sums_carve(workspace);
-  const size_t want = (size_t)((Q + 255) / 256);
-  const int nb = (int)(want < (size_t)rgte::kSumBlocks ? want : (size_t)rgte::kSumBlocks);
+  const int nb = rg::sum_blocks(Q);
   hipLaunchKernelGGL(rgte::pair_sums_partial_kernel, dim3(nb), dim3(256), 0, s, Q, moved, target, NT, index, w.partial);
   hipLaunchKernelGGL(rgte::pair_sums_final_kernel, dim3(1), dim3(256), 0, s, nb, w.partial, out18, w.means6);
   hipLaunchKernelGGL(rgte::pair_moments_partial_kernel, dim3(nb), dim3(256), 0, s, Q, moved, target, NT, index, w.means6, w.partial);
@@ -408,8 +378,7 @@ int radegs_tnteval_histogram(long long N, const double* dist, int n_edges, const
     return RADEGS_ERR_HIP;
   if (N == 0) return 0;
   if (!dist) return RADEGS_ERR_INVALID_ARG;
-  const size_t want = (size_t)((N + 255) / 256);
-  const int nb = (int)(want < (size_t)rgte::kSumBlocks ? want : (size_t)rgte::kSumBlocks);
+  const int nb = rg::sum_blocks(N);
   hipLaunchKernelGGL(rgte::histogram_kernel, dim3(nb), dim3(256), 0, s, N, dist, n_edges, edges, threshold, reinterpret_cast<unsigned long long*>(hist),
                      reinterpret_cast<unsigned long long*>(below));
   return rg::launch_status();

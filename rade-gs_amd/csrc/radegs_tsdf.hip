@@ -1,8 +1,8 @@
 // radegs_tsdf.hip -- TSDF fusion: the step between the renderer's median depth maps and recon.ply on the reference's DTU
 // route, mesh_extract.py:51-105, which upstream hands to Open3D's VoxelBlockGrid on the CPU.
-//     compute_unique_block_coordinates     touch_keys_kernel (the key as two words) -> rg::radix_sort_order_2xu32 -> join_keys_kernel ->
-//                                          first_kernel -> scans -> unique_emit_kernel
-//     integrate                            coords_keys_kernel -> the same sort and join, first_kernel against the grid -> insert_old /
+//     compute_unique_block_coordinates     touch_keys_kernel (the key as two words) -> rg::radix_sort_order_2xu32 (with the joined
+//                                          key) -> first_kernel -> scans -> unique_emit_kernel
+//     integrate                            coords_keys_kernel -> the same sort, first_kernel against the grid -> insert_old /
 //                                          insert_new_kernel (the merged key array), fuse_view_kernel
 //     extract_triangle_mesh                extract_count_kernel -> scans over the blocks -> extract_vertices_kernel, extract_faces_kernel
 //
@@ -101,13 +101,6 @@ __global__ void __launch_bounds__(256) coords_keys_kernel(uint32_t n, const int*
 }
 
 // ------------------------------------------------------------------- sort, unique, insert -------------------------------------------------------------------
-// The sorted keys from what rg::radix_sort_order_2xu32 leaves: the high words in order, the low words through the permutation.
-__global__ void __launch_bounds__(256) join_keys_kernel(uint32_t n, const uint32_t* __restrict__ hi_sorted, const uint32_t* __restrict__ lo,
-                                                        const uint32_t* __restrict__ perm, unsigned long long* __restrict__ sorted) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i < n) sorted[i] = ((unsigned long long)hi_sorted[i] << 32) | lo[perm[i]];
-}
-
 // first[j]: sorted[j] is a real key and differs from its predecessor.  Against the grid: pos[j] = how many grid keys are smaller,
 // fresh[j] = first and not in the grid.
 __global__ void __launch_bounds__(256) first_kernel(uint32_t n, const unsigned long long* __restrict__ sorted, uint32_t ngrid,
@@ -215,9 +208,9 @@ static UniqueView unique_carve(long long N, void* base) {
 // leave the counts
 static int unique_run(uint32_t n, const UniqueView& w, uint32_t ngrid, const unsigned long long* grid_keys, long long* counts3, hipStream_t s) {
   const unsigned nb = blocks_of(n);
-  if (rg::radix_sort_order_2xu32(w.temp, w.temp_bytes, w.lo, w.hi, w.hi_sorted, w.perm, w.first, w.fresh, w.pos, n, 32, 32, s) != hipSuccess)
+  if (rg::radix_sort_order_2xu32(w.temp, w.temp_bytes, w.lo, w.hi, w.hi_sorted, w.perm, w.first, w.fresh, w.pos, n, 32, 32, s, nullptr, w.sorted) !=
+      hipSuccess)
     return RADEGS_ERR_HIP;
-  hipLaunchKernelGGL(join_keys_kernel, dim3(nb), dim3(256), 0, s, n, w.hi_sorted, w.lo, w.perm, w.sorted);
   hipLaunchKernelGGL(first_kernel, dim3(nb), dim3(256), 0, s, n, w.sorted, ngrid, grid_keys, w.first, w.fresh, w.pos);
   if (rg::inclusive_scan_gather_u32(w.temp, w.temp_bytes, w.first, nullptr, w.first_incl, n, s) != hipSuccess) return RADEGS_ERR_HIP;
   if (rg::inclusive_scan_gather_u32(w.temp, w.temp_bytes, w.fresh, nullptr, w.fresh_incl, n, s) != hipSuccess) return RADEGS_ERR_HIP;

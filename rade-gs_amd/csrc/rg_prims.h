@@ -36,9 +36,11 @@ hipError_t radix_sort_pairs_u16(void* temp, size_t temp_bytes, const uint16_t* k
 // Stable ascending order of n (major, minor) pairs of u32 words, LSD: minor first.  On return perm[i] is the input index of the i-th pair
 // and major_sorted[i] == major[perm[i]].  minor / major are not written.  s0, s1, s2: three caller arrays of n words each, undefined
 // afterwards and free for the caller's stream-ordered reuse.  temp: sort_temp_bytes(n).  n_dev as in radix_sort_pairs_u32 (n is then a capacity).
+// joined != nullptr: one more kernel writes joined[i] = major[perm[i]] << 32 | minor[perm[i]], the whole raw words whatever the end bits, for
+// i < n (i < min(n, *n_dev) under n_dev) and nothing past that.
 hipError_t radix_sort_order_2xu32(void* temp, size_t temp_bytes, const uint32_t* minor, const uint32_t* major, uint32_t* major_sorted,
                                   uint32_t* perm, uint32_t* s0, uint32_t* s1, uint32_t* s2, size_t n, int minor_end_bit, int major_end_bit,
-                                  hipStream_t stream, const uint32_t* n_dev = nullptr);
+                                  hipStream_t stream, const uint32_t* n_dev = nullptr, unsigned long long* joined = nullptr);
 hipError_t inclusive_scan_gather_u32(void* temp, size_t temp_bytes, const uint32_t* vals, const uint32_t* idx, uint32_t* out, size_t n,
                                      hipStream_t stream, uint32_t* packed_out = nullptr, unsigned long long* sq_sum = nullptr, int items_override = 0);
 

@@ -1,0 +1,76 @@
+"""The host layer the geometry modules share (tetmesh, mesh_eval, tsdf, tnt_eval, tnt_cull): binding a module's table of C signatures to
+libradegs_hip.so, the return-code check, the workspace buffer, and the argument checks that refuse rather than convert."""
+import ctypes
+import math
+
+import torch
+
+from diff_gaussian_rasterization import _C
+
+ERR_TOO_LARGE = -6   # RADEGS_ERR_TOO_LARGE (include/radegs.h)
+# the C types of the signature tables
+vp, ll, i32, sz, f32, f64 = ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_size_t, ctypes.c_float, ctypes.c_double
+pf32, pf64 = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)
+_bound = set()
+
+
+def bind(signatures):
+    """sets {"radegs_x": (restype, [argtypes...]), ...} on the library, each name once, and returns the library"""
+    L = _C.library()
+    for name in signatures.keys() - _bound:
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = signatures[name]
+        _bound.add(name)
+    return L
+
+
+def check(rc, what):
+    if rc == ERR_TOO_LARGE:
+        raise RuntimeError(f"{what}: the input is larger than the 32-bit sort / scan primitives address (include/radegs.h)")
+    if rc != 0:
+        raise RuntimeError(f"{what} failed ({rc})")
+
+
+def workspace(nbytes, dev):
+    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
+
+
+def doubles(values):
+    return (ctypes.c_double * len(values))(*[float(v) for v in values])
+
+
+def positive(value, name):
+    if not (isinstance(value, (int, float)) and not isinstance(value, bool) and math.isfinite(value) and value > 0):
+        raise RuntimeError(f"`{name}` must be a positive finite number")
+    return float(value)
+
+
+def points(t, name, dtype=torch.float64):
+    """a contiguous [N,3] GPU tensor of the kernels' type; anything else is refused, nothing is converted silently"""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.size(1) != 3:
+        raise RuntimeError(f"`{name}` must be a tensor of shape (N,3)" + (f", got {tuple(t.shape)}" if isinstance(t, torch.Tensor) else ""))
+    if t.dtype != dtype:
+        raise RuntimeError(f"`{name}` must be {str(dtype).replace('torch.', '')}, got {str(t.dtype).replace('torch.', '')}")
+    _C._require_gpu(t, name)
+    return t.detach().contiguous()
+
+
+def finite(t, name):
+    if t.numel() and not bool(torch.isfinite(t).all()):
+        raise RuntimeError(f"`{name}` holds non-finite values")
+
+
+def faces_type(faces):
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.size(1) != 3 or faces.dtype not in (torch.int32, torch.int64):
+        raise RuntimeError("`faces` must be an int32 or int64 tensor of shape (F,3)")
+
+
+def faces(faces, V):
+    faces_type(faces)
+    _C._require_gpu(faces, "faces")
+    if faces.numel():
+        lo, hi = torch.aminmax(faces)
+        lo, hi = int(lo), int(hi)
+        if lo < 0 or hi >= V:
+            raise RuntimeError(f"`faces` holds indices in [{lo}, {hi}], outside the {V} vertices")
+    return faces.detach().to(torch.int64).contiguous()

@@ -9,11 +9,10 @@ import math
 import numpy as np
 import torch
 
+import geom_host as gh
 from diff_gaussian_rasterization import _C
-from tetmesh import ERR_TOO_LARGE, _check, _workspace
-from tetmesh import _lib as _tetmesh_lib
+from geom_host import f64, i32, ll, pf64, sz, vp
 
-_bound = False
 CELL_SLACK = 1.0 + 1e-6      # thinning grid: cell = radius * CELL_SLACK, so that rounding in floor((p - origin) / cell) cannot put two
                              # points within the radius more than one cell apart
 NN_CELLS_PER_MAX_DIST = 8    # dtu_chamfer's nearest-neighbour grids: cell = max_dist / 8
@@ -23,78 +22,28 @@ ROUNDS_PER_READ = 8          # thinning rounds enqueued between two reads of the
 class RadegsCullCamera(ctypes.Structure):
     _fields_ = [("m", ctypes.c_float * 12), ("W", ctypes.c_int), ("H", ctypes.c_int), ("mask_offset", ctypes.c_longlong)]
 
+_SIGNATURES = {
+    "radegs_mesheval_sample_bytes": (sz, [ll]),
+    "radegs_mesheval_sample_count": (i32, [ll, ll, vp, vp, f64, vp, sz, vp, vp, vp]),
+    "radegs_mesheval_sample_emit": (i32, [ll, ll, vp, vp, f64, vp, ll, vp, vp]),
+    "radegs_mesheval_grid_bytes": (sz, [ll]),
+    "radegs_mesheval_grid_build": (i32, [ll, vp, pf64, f64, vp, sz, vp]),
+    "radegs_mesheval_thin_rounds": (i32, [ll, vp, pf64, f64, f64, i32, vp, vp, vp]),
+    "radegs_mesheval_nearest": (i32, [ll, vp, pf64, f64, ll, vp, f64, vp, vp, vp]),
+    "radegs_mesheval_sum_bytes": (sz, []),
+    "radegs_mesheval_sum_below": (i32, [ll, vp, f64, vp, sz, vp, vp]),
+    "radegs_mesheval_obs_mask": (i32, [ll, vp, pf64, ctypes.POINTER(ctypes.c_int), vp, vp, vp, vp, vp]),
+    "radegs_mesheval_above_plane": (i32, [ll, vp, pf64, vp, vp]),
+    "radegs_mesheval_dilate": (i32, [i32, i32, vp, i32, vp, vp]),
+    "radegs_mesheval_cull_vertices": (i32, [ll, vp, i32, vp, vp, vp, vp]),
+    "radegs_tetmesh_filter_plan_flags": (i32, [ll, ll, vp, vp, vp, sz, vp, vp]),
+    "radegs_tetmesh_filter_plan_bytes": (sz, [ll, ll]),
+    "radegs_tetmesh_filter_apply": (i32, [ll, ll, vp, vp, vp, ll, ll, vp, vp, vp]),
+}
+
 
 def _lib():
-    global _bound
-    L = _tetmesh_lib()
-    if not _bound:
-        vp, ll, i32, sz, f64 = ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_size_t, ctypes.c_double
-        d3 = ctypes.POINTER(ctypes.c_double)
-        L.radegs_mesheval_sample_bytes.restype = sz
-        L.radegs_mesheval_sample_bytes.argtypes = [ll]
-        L.radegs_mesheval_sample_count.restype = i32
-        L.radegs_mesheval_sample_count.argtypes = [ll, ll, vp, vp, f64, vp, sz, vp, vp, vp]
-        L.radegs_mesheval_sample_emit.restype = i32
-        L.radegs_mesheval_sample_emit.argtypes = [ll, ll, vp, vp, f64, vp, ll, vp, vp]
-        L.radegs_mesheval_grid_bytes.restype = sz
-        L.radegs_mesheval_grid_bytes.argtypes = [ll]
-        L.radegs_mesheval_grid_build.restype = i32
-        L.radegs_mesheval_grid_build.argtypes = [ll, vp, d3, f64, vp, sz, vp]
-        L.radegs_mesheval_thin_rounds.restype = i32
-        L.radegs_mesheval_thin_rounds.argtypes = [ll, vp, d3, f64, f64, i32, vp, vp, vp]
-        L.radegs_mesheval_nearest.restype = i32
-        L.radegs_mesheval_nearest.argtypes = [ll, vp, d3, f64, ll, vp, f64, vp, vp, vp]
-        L.radegs_mesheval_sum_bytes.restype = sz
-        L.radegs_mesheval_sum_bytes.argtypes = []
-        L.radegs_mesheval_sum_below.restype = i32
-        L.radegs_mesheval_sum_below.argtypes = [ll, vp, f64, vp, sz, vp, vp]
-        L.radegs_mesheval_obs_mask.restype = i32
-        L.radegs_mesheval_obs_mask.argtypes = [ll, vp, d3, ctypes.POINTER(ctypes.c_int), vp, vp, vp, vp, vp]
-        L.radegs_mesheval_above_plane.restype = i32
-        L.radegs_mesheval_above_plane.argtypes = [ll, vp, d3, vp, vp]
-        L.radegs_mesheval_dilate.restype = i32
-        L.radegs_mesheval_dilate.argtypes = [i32, i32, vp, i32, vp, vp]
-        L.radegs_mesheval_cull_vertices.restype = i32
-        L.radegs_mesheval_cull_vertices.argtypes = [ll, vp, i32, vp, vp, vp, vp]
-        L.radegs_tetmesh_filter_plan_flags.restype = i32
-        L.radegs_tetmesh_filter_plan_flags.argtypes = [ll, ll, vp, vp, vp, sz, vp, vp]
-        _bound = True
-    return L
-
-
-def _doubles(values):
-    return (ctypes.c_double * len(values))(*[float(v) for v in values])
-
-
-def _points(t, name, dtype=torch.float64):
-    """a contiguous [N,3] GPU tensor of the kernels' type; anything else is refused, nothing is converted silently"""
-    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.size(1) != 3:
-        raise RuntimeError(f"`{name}` must be a tensor of shape (N,3)" + (f", got {tuple(t.shape)}" if isinstance(t, torch.Tensor) else ""))
-    if t.dtype != dtype:
-        raise RuntimeError(f"`{name}` must be {str(dtype).replace('torch.', '')}, got {str(t.dtype).replace('torch.', '')}")
-    _C._require_gpu(t, name)
-    return t.detach().contiguous()
-
-
-def _finite(t, name):
-    if t.numel() and not bool(torch.isfinite(t).all()):
-        raise RuntimeError(f"`{name}` holds non-finite values")
-
-
-def _faces_type(faces):
-    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.size(1) != 3 or faces.dtype not in (torch.int32, torch.int64):
-        raise RuntimeError("`faces` must be an int32 or int64 tensor of shape (F,3)")
-
-
-def _faces(faces, V):
-    _faces_type(faces)
-    _C._require_gpu(faces, "faces")
-    if faces.numel():
-        lo, hi = torch.aminmax(faces)
-        lo, hi = int(lo), int(hi)
-        if lo < 0 or hi >= V:
-            raise RuntimeError(f"`faces` holds indices in [{lo}, {hi}], outside the {V} vertices")
-    return faces.detach().to(torch.int64).contiguous()
+    return gh.bind(_SIGNATURES)
 
 
 # ------------------------------------------------------------------ triangle sampling ------------------------------------------------------------------
@@ -102,31 +51,30 @@ def _faces(faces, V):
 def sample_mesh_points(vertices, faces, density=0.2):
     """eval.py:50-71.  `vertices` float64 [V,3], `faces` int [F,3] on the GPU.  Returns (cloud float64 [V+M,3]: the vertices followed by the
     samples, triangles in input order, i major, j minor; counts int32 [F]: samples per triangle, 0 for a dropped one)."""
-    _faces_type(faces)
-    v = _points(vertices, "vertices")
-    f = _faces(faces, v.shape[0])
-    if not (isinstance(density, (int, float)) and math.isfinite(density) and density > 0):
-        raise RuntimeError("`density` must be a positive finite number")
-    _finite(v, "vertices")
+    gh.faces_type(faces)
+    v = gh.points(vertices, "vertices")
+    f = gh.faces(faces, v.shape[0])
+    gh.positive(density, "density")
+    gh.finite(v, "vertices")
     V, F, dev = v.shape[0], f.shape[0], v.device
     L = _lib()
     nbytes = L.radegs_mesheval_sample_bytes(F)
-    ws = _workspace(nbytes, dev)
+    ws = gh.workspace(nbytes, dev)
     counts = torch.zeros(F, dtype=torch.int32, device=dev)
     totals = torch.zeros(2, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
         stream = _C._stream(dev)
-        _check(L.radegs_mesheval_sample_count(V, F, _C._ptr(v), _C._ptr(f), float(density), _C._ptr(ws), nbytes, _C._ptr(counts), _C._ptr(totals), stream),
-               "radegs_mesheval_sample_count")
+        gh.check(L.radegs_mesheval_sample_count(V, F, _C._ptr(v), _C._ptr(f), float(density), _C._ptr(ws), nbytes, _C._ptr(counts), _C._ptr(totals), stream),
+                 "radegs_mesheval_sample_count")
         M, too_fine = totals.tolist()          # the one host read
         if too_fine:
             raise RuntimeError(f"sample_mesh_points: {too_fine} triangles are subdivided more than 30 000 times along an edge at density {density}")
         if M >= 2 ** 32 - 1:
-            _check(ERR_TOO_LARGE, "sample_mesh_points")
+            gh.check(gh.ERR_TOO_LARGE, "sample_mesh_points")
         out = torch.empty((V + M, 3), dtype=torch.float64, device=dev)
         out[:V].copy_(v)
-        _check(L.radegs_mesheval_sample_emit(V, F, _C._ptr(v), _C._ptr(f), float(density), _C._ptr(ws), M, ctypes.c_void_p(out.data_ptr() + 24 * V), stream),
-               "radegs_mesheval_sample_emit")
+        gh.check(L.radegs_mesheval_sample_emit(V, F, _C._ptr(v), _C._ptr(f), float(density), _C._ptr(ws), M, ctypes.c_void_p(out.data_ptr() + 24 * V), stream),
+                 "radegs_mesheval_sample_emit")
     return out, counts
 
 
@@ -135,39 +83,37 @@ class PointGrid:
     """A uniform grid of `cell` over `points` (float64 [N,3], N >= 1, kept by reference).  .nearest() answers eval.py's kneighbors calls."""
 
     def __init__(self, points, cell):
-        self.points = _points(points, "points")
-        if not (isinstance(cell, (int, float)) and math.isfinite(cell) and cell > 0):
-            raise RuntimeError("`cell` must be a positive finite number")
+        self.points = gh.points(points, "points")
+        gh.positive(cell, "cell")
         if self.points.shape[0] == 0:
             raise RuntimeError("`points` is empty: a grid needs at least one point")
-        _finite(self.points, "points")
+        gh.finite(self.points, "points")
         self.cell, self.n, self.device = float(cell), self.points.shape[0], self.points.device
-        self.origin = _doubles(self.points.amin(dim=0).tolist())
+        self.origin = gh.doubles(self.points.amin(dim=0).tolist())
         L = _lib()
         self.nbytes = L.radegs_mesheval_grid_bytes(self.n)
         if self.nbytes == 0:
-            _check(ERR_TOO_LARGE, "PointGrid")
-        self.ws = _workspace(self.nbytes, self.device)
+            gh.check(gh.ERR_TOO_LARGE, "PointGrid")
+        self.ws = gh.workspace(self.nbytes, self.device)
         with torch.cuda.device(self.device):
-            _check(L.radegs_mesheval_grid_build(self.n, _C._ptr(self.points), self.origin, self.cell, _C._ptr(self.ws), self.nbytes, _C._stream(self.device)),
-                   "radegs_mesheval_grid_build")
+            gh.check(L.radegs_mesheval_grid_build(self.n, _C._ptr(self.points), self.origin, self.cell, _C._ptr(self.ws), self.nbytes, _C._stream(self.device)),
+                     "radegs_mesheval_grid_build")
 
     @torch.no_grad()
     def nearest(self, queries, max_dist):
         """(dist float64 [Q], index int64 [Q]) of the nearest grid point where its distance is < max_dist, else (inf, -1)"""
-        q = _points(queries, "queries")
+        q = gh.points(queries, "queries")
         if q.device != self.device:
             raise RuntimeError("`queries` must be on the grid's device")
-        if not (isinstance(max_dist, (int, float)) and math.isfinite(max_dist) and max_dist > 0):
-            raise RuntimeError("`max_dist` must be a positive finite number")
+        gh.positive(max_dist, "max_dist")
         if math.ceil(max_dist / self.cell) > 511:
             raise RuntimeError("`max_dist` is more than 511 cells: build the grid with a larger cell")
         Q = q.shape[0]
         dist = torch.empty(Q, dtype=torch.float64, device=self.device)
         index = torch.empty(Q, dtype=torch.int64, device=self.device)
         with torch.cuda.device(self.device):
-            _check(_lib().radegs_mesheval_nearest(self.n, _C._ptr(self.ws), self.origin, self.cell, Q, _C._ptr(q), float(max_dist), _C._ptr(dist),
-                                                  _C._ptr(index), _C._stream(self.device)), "radegs_mesheval_nearest")
+            gh.check(_lib().radegs_mesheval_nearest(self.n, _C._ptr(self.ws), self.origin, self.cell, Q, _C._ptr(q), float(max_dist), _C._ptr(dist),
+                                                    _C._ptr(index), _C._stream(self.device)), "radegs_mesheval_nearest")
         return dist, index
 
 
@@ -180,11 +126,11 @@ def mean_below(dist, max_dist):
     d, dev = dist.contiguous(), dist.device
     L = _lib()
     nbytes = L.radegs_mesheval_sum_bytes()
-    ws = _workspace(nbytes, dev)
+    ws = gh.workspace(nbytes, dev)
     out = torch.empty(2, dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        _check(L.radegs_mesheval_sum_below(d.shape[0], _C._ptr(d), float(max_dist), _C._ptr(ws), nbytes, _C._ptr(out), _C._stream(dev)),
-               "radegs_mesheval_sum_below")
+        gh.check(L.radegs_mesheval_sum_below(d.shape[0], _C._ptr(d), float(max_dist), _C._ptr(ws), nbytes, _C._ptr(out), _C._stream(dev)),
+                 "radegs_mesheval_sum_below")
     return out
 
 
@@ -194,9 +140,8 @@ def downsample_points(points, radius, perm=None, generator=None):
     """eval.py:80-94.  Shuffles `points` (float64 [N,3]) by `perm` (int64 [N]; drawn from `generator`, or torch's global one, when None), then
     keeps the lexicographically first maximal independent set of the graph d^2 <= radius^2 in shuffled order -- what the reference's
     sequential loop keeps.  Returns (kept points in shuffled order, keep mask bool [N] in shuffled order, perm)."""
-    p = _points(points, "points")
-    if not (isinstance(radius, (int, float)) and math.isfinite(radius) and radius > 0):
-        raise RuntimeError("`radius` must be a positive finite number")
+    p = gh.points(points, "points")
+    gh.positive(radius, "radius")
     N, dev = p.shape[0], p.device
     if perm is None:
         g = generator
@@ -217,8 +162,8 @@ def downsample_points(points, radius, perm=None, generator=None):
     with torch.cuda.device(dev):
         stream = _C._stream(dev)
         while True:                            # no cap: a cloud ordered along a line needs as many rounds as it has points
-            _check(L.radegs_mesheval_thin_rounds(N, _C._ptr(grid.ws), grid.origin, grid.cell, float(radius), ROUNDS_PER_READ, _C._ptr(state),
-                                                 _C._ptr(undecided), stream), "radegs_mesheval_thin_rounds")
+            gh.check(L.radegs_mesheval_thin_rounds(N, _C._ptr(grid.ws), grid.origin, grid.cell, float(radius), ROUNDS_PER_READ, _C._ptr(state),
+                                                   _C._ptr(undecided), stream), "radegs_mesheval_thin_rounds")
             if int(undecided.item()) == 0:     # one host read per batch of rounds
                 break
     keep = state == 1
@@ -232,7 +177,7 @@ def obs_mask_select(points, obs_mask, BB, Res, patch=60):
     loadmat returns it); `BB` [2,3] (taken to float32 as the reference does), `Res` a scalar.  Returns three bool [N] masks over `points`:
     inbound; inbound and inside the volume's index range; that and ObsMask set -- the reference's `inbound`, `grid_inbound` and `in_obs`
     scattered back to full length."""
-    p = _points(points, "points")
+    p = gh.points(points, "points")
     dev = p.device
     if isinstance(obs_mask, np.ndarray):
         obs_mask = torch.from_numpy(np.ascontiguousarray(obs_mask != 0).view(np.uint8)).to(dev)
@@ -246,26 +191,26 @@ def obs_mask_select(points, obs_mask, BB, Res, patch=60):
         raise RuntimeError("`BB` must be a finite (2,3) array and `Res` a positive number")
     patch = float(patch)                               # a Python scalar leaves the sums below in float32, as the reference's
     lo, hi = bb[0] - patch, bb[1] + patch * 2
-    box = _doubles(list(lo.astype(np.float64)) + list(hi.astype(np.float64)) + list(bb[0].astype(np.float64)) + [res])
+    box = gh.doubles(list(lo.astype(np.float64)) + list(hi.astype(np.float64)) + list(bb[0].astype(np.float64)) + [res])
     dims = (ctypes.c_int * 3)(*vol.shape)
     N = p.shape[0]
     out = torch.zeros((3, N), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        _check(_lib().radegs_mesheval_obs_mask(N, _C._ptr(p), box, dims, _C._ptr(vol), _C._ptr(out[0]), _C._ptr(out[1]), _C._ptr(out[2]), _C._stream(dev)),
-               "radegs_mesheval_obs_mask")
+        gh.check(_lib().radegs_mesheval_obs_mask(N, _C._ptr(p), box, dims, _C._ptr(vol), _C._ptr(out[0]), _C._ptr(out[1]), _C._ptr(out[2]), _C._stream(dev)),
+                 "radegs_mesheval_obs_mask")
     return out[0].bool(), out[1].bool(), out[2].bool()
 
 
 @torch.no_grad()
 def above_plane(points, plane):
     """eval.py:128-130: (P . [x, y, z, 1]) > 0 as a bool [N] mask"""
-    p = _points(points, "points")
+    p = gh.points(points, "points")
     pl = np.asarray(plane.cpu() if isinstance(plane, torch.Tensor) else plane, dtype=np.float64).reshape(-1)
     if pl.shape != (4,) or not np.isfinite(pl).all():
         raise RuntimeError("`plane` must hold four finite numbers")
     out = torch.zeros(p.shape[0], dtype=torch.uint8, device=p.device)
     with torch.cuda.device(p.device):
-        _check(_lib().radegs_mesheval_above_plane(p.shape[0], _C._ptr(p), _doubles(pl), _C._ptr(out), _C._stream(p.device)), "radegs_mesheval_above_plane")
+        gh.check(_lib().radegs_mesheval_above_plane(p.shape[0], _C._ptr(p), gh.doubles(pl), _C._ptr(out), _C._stream(p.device)), "radegs_mesheval_above_plane")
     return out.bool()
 
 
@@ -276,10 +221,10 @@ def dtu_chamfer(vertices, faces, stl_points, obs_mask, BB, Res, plane, *, densit
     the reference's visualisation step consumes: data_pcd, perm, keep (shuffled order), data_down, inbound / grid_inbound / in_obs (over
     data_down), data_in, data_in_obs, dist_d2s / idx_d2s (over data_in_obs, indices into stl_points), above (over stl_points), stl_above,
     dist_s2d / idx_s2d (over stl_above, indices into data_in).  Distances of max_dist or more read inf, their index -1."""
-    stl = _points(stl_points, "stl_points")
+    stl = gh.points(stl_points, "stl_points")
     if stl.shape[0] == 0:
         raise RuntimeError("`stl_points` is empty")
-    _finite(stl, "stl_points")
+    gh.finite(stl, "stl_points")
     data_pcd, counts = sample_mesh_points(vertices, faces, density)
     data_down, keep, perm = downsample_points(data_pcd, density, perm=perm, generator=generator)
     inbound, grid_inbound, in_obs = obs_mask_select(data_down, obs_mask, BB, Res, patch_size)
@@ -318,7 +263,7 @@ def dilate_mask(mask, radius=6):
         raise RuntimeError("`radius` must be an integer in [0, 64]")
     out = torch.empty_like(m)
     with torch.cuda.device(m.device):
-        _check(_lib().radegs_mesheval_dilate(m.shape[1], m.shape[0], _C._ptr(m), radius, _C._ptr(out), _C._stream(m.device)), "radegs_mesheval_dilate")
+        gh.check(_lib().radegs_mesheval_dilate(m.shape[1], m.shape[0], _C._ptr(m), radius, _C._ptr(out), _C._stream(m.device)), "radegs_mesheval_dilate")
     return out.bool()
 
 
@@ -346,10 +291,10 @@ def cull_mesh(vertices, faces, cameras, masks=None, dilation=6):
     gt_mask, or tuples (w2c, fx, fy, W, H, mask); `masks[i]` replaces camera i's mask.  Returns (vertices, faces int64)."""
     if not isinstance(vertices, torch.Tensor) or vertices.dtype not in (torch.float32, torch.float64):
         raise RuntimeError("`vertices` must be a float32 or float64 tensor")
-    _faces_type(faces)
-    v_in = _points(vertices, "vertices", vertices.dtype)
-    f = _faces(faces, v_in.shape[0])
-    _finite(v_in, "vertices")
+    gh.faces_type(faces)
+    v_in = gh.points(vertices, "vertices", vertices.dtype)
+    f = gh.faces(faces, v_in.shape[0])
+    gh.finite(v_in, "vertices")
     dev, NV, NF = v_in.device, v_in.shape[0], f.shape[0]
     v32 = v_in.float()
     table, dilated, offset = (RadegsCullCamera * max(len(cameras), 1))(), [], 0
@@ -367,22 +312,22 @@ def cull_mesh(vertices, faces, cameras, masks=None, dilation=6):
     L = _lib()
     flags = torch.ones(NV, dtype=torch.int32, device=dev)
     nbytes = L.radegs_tetmesh_filter_plan_bytes(NV, NF)
-    ws = _workspace(nbytes, dev)
+    ws = gh.workspace(nbytes, dev)
     counts = torch.zeros(2, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
         stream = _C._stream(dev)
         if cameras:
             cam_dev = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
             all_masks = torch.cat(dilated)
-            _check(L.radegs_mesheval_cull_vertices(NV, _C._ptr(v32), len(cameras), _C._ptr(cam_dev), _C._ptr(all_masks), _C._ptr(flags), stream),
-                   "radegs_mesheval_cull_vertices")
-        _check(L.radegs_tetmesh_filter_plan_flags(NV, NF, _C._ptr(flags), _C._ptr(f), _C._ptr(ws), nbytes, _C._ptr(counts), stream),
-               "radegs_tetmesh_filter_plan_flags")
+            gh.check(L.radegs_mesheval_cull_vertices(NV, _C._ptr(v32), len(cameras), _C._ptr(cam_dev), _C._ptr(all_masks), _C._ptr(flags), stream),
+                     "radegs_mesheval_cull_vertices")
+        gh.check(L.radegs_tetmesh_filter_plan_flags(NV, NF, _C._ptr(flags), _C._ptr(f), _C._ptr(ws), nbytes, _C._ptr(counts), stream),
+                 "radegs_tetmesh_filter_plan_flags")
         nv, nf = counts.tolist()               # the one host read
         out_v = torch.empty((nv, 3), dtype=torch.float32, device=dev)
         out_f = torch.empty((nf, 3), dtype=torch.int64, device=dev)
-        _check(L.radegs_tetmesh_filter_apply(NV, NF, _C._ptr(v32), _C._ptr(f), _C._ptr(ws), nv, nf, _C._ptr(out_v), _C._ptr(out_f), stream),
-               "radegs_tetmesh_filter_apply")
+        gh.check(L.radegs_tetmesh_filter_apply(NV, NF, _C._ptr(v32), _C._ptr(f), _C._ptr(ws), nv, nf, _C._ptr(out_v), _C._ptr(out_f), stream),
+                 "radegs_tetmesh_filter_apply")
     if v_in.dtype == torch.float64:            # the kept rows of the caller's own precision
         out_v = v_in[flags.bool()]
     return out_v, out_f

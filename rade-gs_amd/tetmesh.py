@@ -3,51 +3,29 @@ GaussianRasterizer.integrate -- marching tetrahedra (utils/tetmesh.py), Gaussian
 accumulation of evaluage_cull_alpha, the bisection along every crossing edge and the final vertex / face filter.  GPU only:
 upstream moves marching tetrahedra to the CPU to save memory; here it is a sort over the crossing edges on the device.
 The Delaunay triangulation (`cells`) is an input."""
-import ctypes
-
 import numpy as np
 import torch
 
+import geom_host as gh
 from diff_gaussian_rasterization import _C
+from geom_host import i32, ll, sz, vp
 
-_bound = False
-ERR_TOO_LARGE = -6   # RADEGS_ERR_TOO_LARGE (include/radegs.h)
+_SIGNATURES = {
+    "radegs_tetmesh_plan_bytes": (sz, [i32, ll]),
+    "radegs_tetmesh_plan": (i32, [i32, ll, vp, vp, vp, sz, vp, vp]),
+    "radegs_tetmesh_emit": (i32, [i32, ll, vp, vp, vp, vp, vp, ll, ll, vp, vp, vp, vp, vp, vp]),
+    "radegs_tetra_points": (i32, [i32, vp, vp, vp, vp, vp, vp]),
+    "radegs_cull_alpha_accumulate": (i32, [ll, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]),
+    "radegs_cull_alpha_finish": (i32, [ll, vp, vp, vp, vp]),
+    "radegs_tetmesh_bisect": (i32, [ll, vp, vp, vp, vp, vp, vp, vp]),
+    "radegs_tetmesh_filter_plan_bytes": (sz, [ll, ll]),
+    "radegs_tetmesh_filter_plan": (i32, [ll, ll, vp, vp, vp, vp, sz, vp, vp]),
+    "radegs_tetmesh_filter_apply": (i32, [ll, ll, vp, vp, vp, ll, ll, vp, vp, vp]),
+}
 
 
 def _lib():
-    global _bound
-    L = _C.library()
-    if not _bound:
-        vp, ll, i32, sz = ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_size_t
-        L.radegs_tetmesh_plan_bytes.restype = sz
-        L.radegs_tetmesh_plan_bytes.argtypes = [i32, ll]
-        L.radegs_tetmesh_plan.restype = i32
-        L.radegs_tetmesh_plan.argtypes = [i32, ll, vp, vp, vp, sz, vp, vp]
-        L.radegs_tetmesh_emit.restype = i32
-        L.radegs_tetmesh_emit.argtypes = [i32, ll, vp, vp, vp, vp, vp, ll, ll, vp, vp, vp, vp, vp, vp]
-        L.radegs_tetra_points.restype = i32
-        L.radegs_tetra_points.argtypes = [i32, vp, vp, vp, vp, vp, vp]
-        L.radegs_cull_alpha_accumulate.restype = i32
-        L.radegs_cull_alpha_accumulate.argtypes = [ll, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]
-        L.radegs_cull_alpha_finish.restype = i32
-        L.radegs_cull_alpha_finish.argtypes = [ll, vp, vp, vp, vp]
-        L.radegs_tetmesh_bisect.restype = i32
-        L.radegs_tetmesh_bisect.argtypes = [ll, vp, vp, vp, vp, vp, vp, vp]
-        L.radegs_tetmesh_filter_plan_bytes.restype = sz
-        L.radegs_tetmesh_filter_plan_bytes.argtypes = [ll, ll]
-        L.radegs_tetmesh_filter_plan.restype = i32
-        L.radegs_tetmesh_filter_plan.argtypes = [ll, ll, vp, vp, vp, vp, sz, vp, vp]
-        L.radegs_tetmesh_filter_apply.restype = i32
-        L.radegs_tetmesh_filter_apply.argtypes = [ll, ll, vp, vp, vp, ll, ll, vp, vp, vp]
-        _bound = True
-    return L
-
-
-def _check(rc, what):
-    if rc == ERR_TOO_LARGE:
-        raise RuntimeError(f"{what}: the input is larger than the 32-bit sort / scan primitives address (include/radegs.h)")
-    if rc != 0:
-        raise RuntimeError(f"{what} failed ({rc})")
+    return gh.bind(_SIGNATURES)
 
 
 def _f32(t, name, shape=None):
@@ -59,10 +37,6 @@ def _f32(t, name, shape=None):
     if shape is not None and (t.dim() != len(shape) or any(s != -1 and s != d for s, d in zip(shape, t.shape))):
         raise RuntimeError(f"`{name}` must have shape {tuple(shape)}, got {tuple(t.shape)}")
     return t.contiguous()
-
-
-def _workspace(nbytes, dev):
-    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
 
 
 # ------------------------------------------------------------ marching tetrahedra ------------------------------------------------------------
@@ -85,20 +59,20 @@ def _unbatched_marching_tetrahedra(vertices, tets32, sdf, scales):
         raise RuntimeError("marching_tetrahedra: more than 2^31 - 1 vertices")
     L = _lib()
     nbytes = L.radegs_tetmesh_plan_bytes(V, T)
-    ws = _workspace(nbytes, dev)
+    ws = gh.workspace(nbytes, dev)
     counts = torch.zeros(2, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
         stream = _C._stream(dev)
-        _check(L.radegs_tetmesh_plan(V, T, _C._ptr(tets32), _C._ptr(sdf), _C._ptr(ws), nbytes, _C._ptr(counts), stream), "radegs_tetmesh_plan")
+        gh.check(L.radegs_tetmesh_plan(V, T, _C._ptr(tets32), _C._ptr(sdf), _C._ptr(ws), nbytes, _C._ptr(counts), stream), "radegs_tetmesh_plan")
         nv, nf = counts.tolist()          # the one host read: the two sizes
         end_points = torch.empty((nv, 2, 3), dtype=torch.float32, device=dev)
         end_sdf = torch.empty((nv, 2, 1), dtype=torch.float32, device=dev)
         end_scales = torch.empty((nv, 2, 1), dtype=torch.float32, device=dev)
         faces = torch.empty((nf, 3), dtype=torch.int64, device=dev)
         interp_v = torch.empty((nv, 2), dtype=torch.int64, device=dev)
-        _check(L.radegs_tetmesh_emit(V, T, _C._ptr(tets32), _C._ptr(sdf), _C._ptr(vertices), _C._ptr(scales), _C._ptr(ws), nv, nf,
-                                     _C._ptr(end_points), _C._ptr(end_sdf), _C._ptr(end_scales), _C._ptr(faces), _C._ptr(interp_v), stream),
-               "radegs_tetmesh_emit")
+        gh.check(L.radegs_tetmesh_emit(V, T, _C._ptr(tets32), _C._ptr(sdf), _C._ptr(vertices), _C._ptr(scales), _C._ptr(ws), nv, nf,
+                                       _C._ptr(end_points), _C._ptr(end_sdf), _C._ptr(end_scales), _C._ptr(faces), _C._ptr(interp_v), stream),
+                 "radegs_tetmesh_emit")
     return (end_points, end_sdf), end_scales, faces, interp_v
 
 
@@ -133,7 +107,7 @@ def tetra_points(xyz, scales3, rotation_raw):
     pts = torch.empty((9 * P, 3), dtype=torch.float32, device=x.device)
     sc = torch.empty((9 * P, 1), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        _check(_lib().radegs_tetra_points(P, _C._ptr(x), _C._ptr(s), _C._ptr(q), _C._ptr(pts), _C._ptr(sc), _C._stream(x.device)), "radegs_tetra_points")
+        gh.check(_lib().radegs_tetra_points(P, _C._ptr(x), _C._ptr(s), _C._ptr(q), _C._ptr(pts), _C._ptr(sc), _C._stream(x.device)), "radegs_tetra_points")
     return pts, sc
 
 
@@ -173,16 +147,16 @@ class CullAlpha:
         gt = None if gt is None else _f32(gt.reshape(H, W), "gt_mask", (H, W))
         extra = None if extra_mask is None else _f32(extra_mask.reshape(H, W), "extra_mask", (H, W))
         with torch.cuda.device(self.device):
-            _check(_lib().radegs_cull_alpha_accumulate(self.n, _C._ptr(alpha), _C._ptr(coord), _C._ptr(mask), _C._ptr(gt), _C._ptr(extra), W, H,
-                                                       _C._ptr(self.final_sdf), _C._ptr(self.weight), _C._stream(self.device)),
-                   "radegs_cull_alpha_accumulate")
+            gh.check(_lib().radegs_cull_alpha_accumulate(self.n, _C._ptr(alpha), _C._ptr(coord), _C._ptr(mask), _C._ptr(gt), _C._ptr(extra), W, H,
+                                                         _C._ptr(self.final_sdf), _C._ptr(self.weight), _C._stream(self.device)),
+                     "radegs_cull_alpha_accumulate")
 
     @torch.no_grad()
     def sdf(self):
         out = torch.empty(self.n, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            _check(_lib().radegs_cull_alpha_finish(self.n, _C._ptr(self.final_sdf), _C._ptr(self.weight), _C._ptr(out), _C._stream(self.device)),
-                   "radegs_cull_alpha_finish")
+            gh.check(_lib().radegs_cull_alpha_finish(self.n, _C._ptr(self.final_sdf), _C._ptr(self.weight), _C._ptr(out), _C._stream(self.device)),
+                     "radegs_cull_alpha_finish")
         return out
 
 
@@ -208,8 +182,8 @@ def bisect_step(left_pts, right_pts, left_sdf, right_sdf, mid_sdf, mid_pts_out=N
     mid = _f32(mid_sdf.reshape(-1), "mid_sdf", (N,))
     out = torch.empty_like(left_pts) if mid_pts_out is None else mid_pts_out
     with torch.cuda.device(left_pts.device):
-        _check(_lib().radegs_tetmesh_bisect(N, _C._ptr(left_pts), _C._ptr(right_pts), _C._ptr(left_sdf), _C._ptr(right_sdf), _C._ptr(mid), _C._ptr(out),
-                                            _C._stream(left_pts.device)), "radegs_tetmesh_bisect")
+        gh.check(_lib().radegs_tetmesh_bisect(N, _C._ptr(left_pts), _C._ptr(right_pts), _C._ptr(left_sdf), _C._ptr(right_sdf), _C._ptr(mid), _C._ptr(out),
+                                              _C._stream(left_pts.device)), "radegs_tetmesh_bisect")
     return out
 
 
@@ -225,17 +199,17 @@ def filter_mesh(end_points, end_scales, points, faces):
     NF, dev = f.shape[0], ep.device
     L = _lib()
     nbytes = L.radegs_tetmesh_filter_plan_bytes(NV, NF)
-    ws = _workspace(nbytes, dev)
+    ws = gh.workspace(nbytes, dev)
     counts = torch.zeros(2, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
         stream = _C._stream(dev)
-        _check(L.radegs_tetmesh_filter_plan(NV, NF, _C._ptr(ep), _C._ptr(es), _C._ptr(f), _C._ptr(ws), nbytes, _C._ptr(counts), stream),
-               "radegs_tetmesh_filter_plan")
+        gh.check(L.radegs_tetmesh_filter_plan(NV, NF, _C._ptr(ep), _C._ptr(es), _C._ptr(f), _C._ptr(ws), nbytes, _C._ptr(counts), stream),
+                 "radegs_tetmesh_filter_plan")
         nv, nf = counts.tolist()          # the one host read
         out_v = torch.empty((nv, 3), dtype=torch.float32, device=dev)
         out_f = torch.empty((nf, 3), dtype=torch.int64, device=dev)
-        _check(L.radegs_tetmesh_filter_apply(NV, NF, _C._ptr(pts), _C._ptr(f), _C._ptr(ws), nv, nf, _C._ptr(out_v), _C._ptr(out_f), stream),
-               "radegs_tetmesh_filter_apply")
+        gh.check(L.radegs_tetmesh_filter_apply(NV, NF, _C._ptr(pts), _C._ptr(f), _C._ptr(ws), nv, nf, _C._ptr(out_v), _C._ptr(out_f), stream),
+                 "radegs_tetmesh_filter_apply")
     return out_v, out_f
 
 

@@ -3,39 +3,33 @@ tnt_eval.evaluate -- one depth map of the mesh per camera (upstream: pyrender / 
 (Mesher.point_masks at forecast_radius 0), and the faces whose three vertices at least `min_views` cameras see.  GPU only.  The rasterizer
 is float64 and pinned to a written rule set (include/radegs.h); the vertex test is float32, as upstream's.  Reading the
 trajectory, trimesh's load / merge_vertices, the forecast branch and get_connected_mesh stay with the caller."""
-import ctypes
 import math
 
 import numpy as np
 import torch
 
+import geom_host as gh
 from diff_gaussian_rasterization import _C
-from mesh_eval import _faces, _faces_type, _finite, _points
-from mesh_eval import _lib as _mesheval_lib
-from tetmesh import _check, _workspace
+from geom_host import f32, f64, i32, ll, sz, vp
 
-_bound = False
 MAX_SIDE, MAX_VIEWS = 32768, 65535
 DEFAULT_VIEW_BATCH = 8            # eight 1080p maps are 66 MB
 QUEUE_ENTRIES = None              # test hook: the number of queue entries render_depth's workspace holds (None: radegs_tntcull_render_bytes)
 POSES = ("opengl", "opencv")
 
+_SIGNATURES = {
+    "radegs_tntcull_render_bytes": (sz, [ll, i32]),
+    "radegs_tntcull_render_begin": (i32, [ll, ll, vp, vp, i32, vp, i32, i32, f64, f64, f64, f64, f64, f64, vp, sz, vp, vp]),
+    "radegs_tntcull_render_finish": (i32, [ll, ll, vp, vp, i32, vp, i32, i32, f64, f64, f64, f64, f64, f64, vp, sz, vp, vp, vp]),
+    "radegs_tntcull_count_views": (i32, [ll, vp, i32, i32, i32, vp, vp, f32, f32, f32, f32, f32, vp, vp]),
+    "radegs_tetmesh_filter_plan_bytes": (sz, [ll, ll]),
+    "radegs_tetmesh_filter_plan_flags": (i32, [ll, ll, vp, vp, vp, sz, vp, vp]),
+    "radegs_tetmesh_filter_apply": (i32, [ll, ll, vp, vp, vp, ll, ll, vp, vp, vp]),
+}
+
 
 def _lib():
-    global _bound
-    L = _mesheval_lib()
-    if not _bound:
-        vp, ll, i32, sz, f64, f32 = ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_size_t, ctypes.c_double, ctypes.c_float
-        L.radegs_tntcull_render_bytes.restype = sz
-        L.radegs_tntcull_render_bytes.argtypes = [ll, i32]
-        L.radegs_tntcull_render_begin.restype = i32
-        L.radegs_tntcull_render_begin.argtypes = [ll, ll, vp, vp, i32, vp, i32, i32, f64, f64, f64, f64, f64, f64, vp, sz, vp, vp]
-        L.radegs_tntcull_render_finish.restype = i32
-        L.radegs_tntcull_render_finish.argtypes = [ll, ll, vp, vp, i32, vp, i32, i32, f64, f64, f64, f64, f64, f64, vp, sz, vp, vp, vp]
-        L.radegs_tntcull_count_views.restype = i32
-        L.radegs_tntcull_count_views.argtypes = [ll, vp, i32, i32, i32, vp, vp, f32, f32, f32, f32, f32, vp, vp]
-        _bound = True
-    return L
+    return gh.bind(_SIGNATURES)
 
 
 # ------------------------------------------------------------------------- arguments -------------------------------------------------------------------------
@@ -112,15 +106,15 @@ def _world_to_camera(c2w, pose="opengl"):
 def _mesh(vertices, faces):
     if not isinstance(vertices, torch.Tensor) or vertices.dtype not in (torch.float32, torch.float64):
         raise RuntimeError("`vertices` must be a float32 or float64 tensor")
-    _faces_type(faces)
-    v = _points(vertices, "vertices", vertices.dtype)
+    gh.faces_type(faces)
+    v = gh.points(vertices, "vertices", vertices.dtype)
     _C._require_gpu(faces, "faces")
     if faces.device != v.device:
         raise RuntimeError("`vertices` and `faces` must be on the same device")
     if v.shape[0] >= 2 ** 31 or faces.shape[0] >= 2 ** 31:
         raise RuntimeError("the mesh has 2^31 vertices or faces, or more")
-    f = _faces(faces, v.shape[0])
-    _finite(v, "vertices")
+    f = gh.faces(faces, v.shape[0])
+    gh.finite(v, "vertices")
     return v, f
 
 
@@ -137,13 +131,13 @@ def _render(v64, f, w2c, H, W, K, znear, zfar, stats=None):
         return depth
     L = _lib()
     nbytes = L.radegs_tntcull_render_bytes(F, B) if QUEUE_ENTRIES is None else L.radegs_tntcull_render_bytes(0, 0) + 16 * int(QUEUE_ENTRIES)
-    ws = _workspace(nbytes, dev)
+    ws = gh.workspace(nbytes, dev)
     cams = _cameras_to(dev, w2c, torch.float64)
     with torch.cuda.device(dev):
         stream = _C._stream(dev)
         args = (V, F, _C._ptr(v64), _C._ptr(f), B, _C._ptr(cams), H, W, *K, znear, zfar, _C._ptr(ws), nbytes, _C._ptr(depth))
-        _check(L.radegs_tntcull_render_begin(*args, stream), "radegs_tntcull_render_begin")
-        _check(L.radegs_tntcull_render_finish(*args, _C._ptr(stats), stream), "radegs_tntcull_render_finish")
+        gh.check(L.radegs_tntcull_render_begin(*args, stream), "radegs_tntcull_render_begin")
+        gh.check(L.radegs_tntcull_render_finish(*args, _C._ptr(stats), stream), "radegs_tntcull_render_finish")
     return depth
 
 
@@ -168,8 +162,8 @@ def _count(p32, depths, w2c, K, eps, counts):
     dev = p32.device
     cams = _cameras_to(dev, w2c, torch.float32)      # inverted in float64, rounded once: upstream inverts in float32
     with torch.cuda.device(dev):
-        _check(_lib().radegs_tntcull_count_views(p32.shape[0], _C._ptr(p32), B, H, W, _C._ptr(depths), _C._ptr(cams), *K, eps, _C._ptr(counts),
-                                                 _C._stream(dev)), "radegs_tntcull_count_views")
+        gh.check(_lib().radegs_tntcull_count_views(p32.shape[0], _C._ptr(p32), B, H, W, _C._ptr(depths), _C._ptr(cams), *K, eps, _C._ptr(counts),
+                                                   _C._stream(dev)), "radegs_tntcull_count_views")
 
 
 def _min_views(min_views):
@@ -188,7 +182,7 @@ def point_masks(points, depths, c2w, fx, fy, cx, cy, eps=0.005, min_views=20):
     w2c = _world_to_camera(c2w)
     if not isinstance(points, torch.Tensor) or points.dtype not in (torch.float32, torch.float64):
         raise RuntimeError("`points` must be a float32 or float64 tensor")
-    p = _points(points, "points", points.dtype)
+    p = gh.points(points, "points", points.dtype)
     _C._require_gpu(depths, "depths")
     if depths.dim() != 3 or depths.dtype != torch.float32:
         raise RuntimeError("`depths` must be a float32 tensor of shape (B,H,W)")
@@ -198,8 +192,8 @@ def point_masks(points, depths, c2w, fx, fy, cx, cy, eps=0.005, min_views=20):
     if B != w2c.shape[0]:
         raise RuntimeError(f"`depths` holds {B} maps for {w2c.shape[0]} poses")
     _side(H, "H"), _side(W, "W")
-    _finite(p, "points")
-    _finite(depths, "depths")
+    gh.finite(p, "points")
+    gh.finite(depths, "depths")
     counts = torch.zeros(p.shape[0], dtype=torch.int32, device=p.device)
     _count(p.float(), depths.detach().contiguous(), w2c, K, eps, counts)
     return counts >= min_views, counts
@@ -231,17 +225,17 @@ def cull_mesh(vertices, faces, c2w, H=1080, W=1920, fx=1163.8678928442187, fy=11
     flags = (counts >= min_views).to(torch.int32)
     L = _lib()
     nbytes = L.radegs_tetmesh_filter_plan_bytes(NV, NF)
-    ws = _workspace(nbytes, dev)
+    ws = gh.workspace(nbytes, dev)
     counts2 = torch.zeros(2, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
         stream = _C._stream(dev)
-        _check(L.radegs_tetmesh_filter_plan_flags(NV, NF, _C._ptr(flags), _C._ptr(f), _C._ptr(ws), nbytes, _C._ptr(counts2), stream),
-               "radegs_tetmesh_filter_plan_flags")
+        gh.check(L.radegs_tetmesh_filter_plan_flags(NV, NF, _C._ptr(flags), _C._ptr(f), _C._ptr(ws), nbytes, _C._ptr(counts2), stream),
+                 "radegs_tetmesh_filter_plan_flags")
         nv, nf = counts2.tolist()              # the one host read
         out_v = torch.empty((nv, 3), dtype=torch.float32, device=dev)
         out_f = torch.empty((nf, 3), dtype=torch.int64, device=dev)
-        _check(L.radegs_tetmesh_filter_apply(NV, NF, _C._ptr(v32), _C._ptr(f), _C._ptr(ws), nv, nf, _C._ptr(out_v), _C._ptr(out_f), stream),
-               "radegs_tetmesh_filter_apply")
+        gh.check(L.radegs_tetmesh_filter_apply(NV, NF, _C._ptr(v32), _C._ptr(f), _C._ptr(ws), nv, nf, _C._ptr(out_v), _C._ptr(out_f), stream),
+                 "radegs_tetmesh_filter_apply")
     if v_in.dtype == torch.float64:            # the kept rows of the caller's own precision
         out_v = v_in[flags.bool()]
     return out_v, out_f

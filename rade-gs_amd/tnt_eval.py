@@ -10,49 +10,30 @@ import math
 import numpy as np
 import torch
 
+import geom_host as gh
 from diff_gaussian_rasterization import _C
-from mesh_eval import PointGrid, _doubles, _faces, _faces_type, _finite, _points
-from mesh_eval import _lib as _mesheval_lib
-from tetmesh import ERR_TOO_LARGE, _check, _workspace
+from geom_host import f64, i32, ll, pf64, sz, vp
+from mesh_eval import PointGrid
 
-_bound = False
 MAX_POINT_NUMBER = 4e6            # registration.py:42
 NN_CELLS_PER_MAX_DIST = 8         # the grids' cell = max_dist / 8 unless the caller passes one
 MAX_POLYGON, MAX_EDGES = 1024, 4096
 
+_SIGNATURES = {
+    "radegs_tnteval_centroids": (i32, [ll, ll, vp, vp, vp, vp]),
+    "radegs_tnteval_transform": (i32, [ll, vp, pf64, vp, vp]),
+    "radegs_tnteval_crop": (i32, [ll, vp, i32, f64, f64, i32, vp, vp, vp]),
+    "radegs_tnteval_voxel_bytes": (sz, [ll]),
+    "radegs_tnteval_voxel_plan": (i32, [ll, vp, pf64, f64, vp, sz, vp, vp]),
+    "radegs_tnteval_voxel_emit": (i32, [ll, vp, vp, ll, vp, vp, vp]),
+    "radegs_tnteval_sums_bytes": (sz, []),
+    "radegs_tnteval_pair_sums": (i32, [ll, vp, ll, vp, vp, vp, sz, vp, vp]),
+    "radegs_tnteval_histogram": (i32, [ll, vp, i32, vp, f64, vp, vp, vp]),
+}
+
 
 def _lib():
-    global _bound
-    L = _mesheval_lib()
-    if not _bound:
-        vp, ll, i32, sz, f64 = ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_size_t, ctypes.c_double
-        d3 = ctypes.POINTER(ctypes.c_double)
-        L.radegs_tnteval_centroids.restype = i32
-        L.radegs_tnteval_centroids.argtypes = [ll, ll, vp, vp, vp, vp]
-        L.radegs_tnteval_transform.restype = i32
-        L.radegs_tnteval_transform.argtypes = [ll, vp, d3, vp, vp]
-        L.radegs_tnteval_crop.restype = i32
-        L.radegs_tnteval_crop.argtypes = [ll, vp, i32, f64, f64, i32, vp, vp, vp]
-        L.radegs_tnteval_voxel_bytes.restype = sz
-        L.radegs_tnteval_voxel_bytes.argtypes = [ll]
-        L.radegs_tnteval_voxel_plan.restype = i32
-        L.radegs_tnteval_voxel_plan.argtypes = [ll, vp, d3, f64, vp, sz, vp, vp]
-        L.radegs_tnteval_voxel_emit.restype = i32
-        L.radegs_tnteval_voxel_emit.argtypes = [ll, vp, vp, ll, vp, vp, vp]
-        L.radegs_tnteval_sums_bytes.restype = sz
-        L.radegs_tnteval_sums_bytes.argtypes = []
-        L.radegs_tnteval_pair_sums.restype = i32
-        L.radegs_tnteval_pair_sums.argtypes = [ll, vp, ll, vp, vp, vp, sz, vp, vp]
-        L.radegs_tnteval_histogram.restype = i32
-        L.radegs_tnteval_histogram.argtypes = [ll, vp, i32, vp, f64, vp, vp, vp]
-        _bound = True
-    return L
-
-
-def _positive(x, name):
-    if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x) or not x > 0:
-        raise RuntimeError(f"`{name}` must be a positive finite number")
-    return float(x)
+    return gh.bind(_SIGNATURES)
 
 
 def _matrix(transform, name="transform"):
@@ -78,16 +59,16 @@ def _vector(t, name):
 @torch.no_grad()
 def mesh_points(vertices, faces):
     """run.py:94-108: the vertices followed by the face centroids ((a + b) + c) / 3.  `vertices` float64 [V,3], `faces` int [F,3] -> [V+F,3]"""
-    _faces_type(faces)
-    v = _points(vertices, "vertices")
-    f = _faces(faces, v.shape[0])
-    _finite(v, "vertices")
+    gh.faces_type(faces)
+    v = gh.points(vertices, "vertices")
+    f = gh.faces(faces, v.shape[0])
+    gh.finite(v, "vertices")
     V, F = v.shape[0], f.shape[0]
     out = torch.empty((V + F, 3), dtype=torch.float64, device=v.device)
     out[:V].copy_(v)
     with torch.cuda.device(v.device):
-        _check(_lib().radegs_tnteval_centroids(V, F, _C._ptr(v), _C._ptr(f), ctypes.c_void_p(out.data_ptr() + 24 * V), _C._stream(v.device)),
-               "radegs_tnteval_centroids")
+        gh.check(_lib().radegs_tnteval_centroids(V, F, _C._ptr(v), _C._ptr(f), ctypes.c_void_p(out.data_ptr() + 24 * V), _C._stream(v.device)),
+                 "radegs_tnteval_centroids")
     return out
 
 
@@ -95,13 +76,13 @@ def mesh_points(vertices, faces):
 def transform_points(points, transform):
     """T (x, y, z, 1) per point, rows evaluated as ((m0 x + m1 y) + m2 z) + m3; `transform` None returns the points themselves"""
     m = _matrix(transform)
-    p = _points(points, "points")
+    p = gh.points(points, "points")
     if m is None:
         return p
     out = torch.empty_like(p)
     with torch.cuda.device(p.device):
-        _check(_lib().radegs_tnteval_transform(p.shape[0], _C._ptr(p), _doubles(m[:3].reshape(-1)), _C._ptr(out), _C._stream(p.device)),
-               "radegs_tnteval_transform")
+        gh.check(_lib().radegs_tnteval_transform(p.shape[0], _C._ptr(p), gh.doubles(m[:3].reshape(-1)), _C._ptr(out), _C._stream(p.device)),
+                 "radegs_tnteval_transform")
     return out
 
 
@@ -144,14 +125,14 @@ def crop_points(points, volume, transform=None):
     if not isinstance(volume, CropVolume):
         raise RuntimeError("`volume` must be a CropVolume")
     p = transform_points(points, transform)
-    _finite(p, "points")
+    gh.finite(p, "points")
     N, dev = p.shape[0], p.device
     u, v, w = volume.axes
     poly = torch.from_numpy(np.ascontiguousarray(volume.bounding_polygon[:, [u, v]])).to(dev)
     keep = torch.zeros(N, dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        _check(_lib().radegs_tnteval_crop(N, _C._ptr(p), w, volume.axis_min, volume.axis_max, poly.shape[0], _C._ptr(poly), _C._ptr(keep), _C._stream(dev)),
-               "radegs_tnteval_crop")
+        gh.check(_lib().radegs_tnteval_crop(N, _C._ptr(p), w, volume.axis_min, volume.axis_max, poly.shape[0], _C._ptr(poly), _C._ptr(keep), _C._stream(dev)),
+                 "radegs_tnteval_crop")
     keep = keep.bool()
     return p[keep], keep
 
@@ -161,9 +142,9 @@ def crop_points(points, volume, transform=None):
 def voxel_down_sample(points, voxel):
     """Open3D's voxel_down_sample: the mean of the points of every occupied voxel of the grid with origin min - voxel / 2.  Returns (means
     float64 [M,3], counts int32 [M]), voxels ascending by (ix, iy, iz) -- Open3D's own order is that of a hash map."""
-    voxel = _positive(voxel, "voxel")
-    p = _points(points, "points")
-    _finite(p, "points")
+    voxel = gh.positive(voxel, "voxel")
+    p = gh.points(points, "points")
+    gh.finite(p, "points")
     N, dev = p.shape[0], p.device
     if N == 0:
         return torch.empty((0, 3), dtype=torch.float64, device=dev), torch.empty(0, dtype=torch.int32, device=dev)
@@ -171,18 +152,18 @@ def voxel_down_sample(points, voxel):
     L = _lib()
     nbytes = L.radegs_tnteval_voxel_bytes(N)
     if nbytes == 0:
-        _check(ERR_TOO_LARGE, "voxel_down_sample")
-    ws = _workspace(nbytes, dev)
+        gh.check(gh.ERR_TOO_LARGE, "voxel_down_sample")
+    ws = gh.workspace(nbytes, dev)
     counts2 = torch.zeros(2, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
         stream = _C._stream(dev)
-        _check(L.radegs_tnteval_voxel_plan(N, _C._ptr(p), _doubles(origin), voxel, _C._ptr(ws), nbytes, _C._ptr(counts2), stream), "radegs_tnteval_voxel_plan")
+        gh.check(L.radegs_tnteval_voxel_plan(N, _C._ptr(p), gh.doubles(origin), voxel, _C._ptr(ws), nbytes, _C._ptr(counts2), stream), "radegs_tnteval_voxel_plan")
         M, outside = counts2.tolist()          # the one host read
         if outside:
-            raise RuntimeError(f"voxel_down_sample ({ERR_TOO_LARGE}): the cloud spans more than 2^21 voxels of {voxel} along an axis")
+            raise RuntimeError(f"voxel_down_sample ({gh.ERR_TOO_LARGE}): the cloud spans more than 2^21 voxels of {voxel} along an axis")
         means = torch.empty((M, 3), dtype=torch.float64, device=dev)
         counts = torch.empty(M, dtype=torch.int32, device=dev)
-        _check(L.radegs_tnteval_voxel_emit(N, _C._ptr(p), _C._ptr(ws), M, _C._ptr(means), _C._ptr(counts), stream), "radegs_tnteval_voxel_emit")
+        gh.check(L.radegs_tnteval_voxel_emit(N, _C._ptr(p), _C._ptr(ws), M, _C._ptr(means), _C._ptr(counts), stream), "radegs_tnteval_voxel_emit")
     return means, counts
 
 
@@ -191,7 +172,7 @@ def uniform_down_sample(points, k):
     """every k-th point, from the first"""
     if isinstance(k, bool) or not isinstance(k, int) or k < 1:
         raise RuntimeError("`k` must be a positive integer")
-    return _points(points, "points")[::k].contiguous()
+    return gh.points(points, "points")[::k].contiguous()
 
 
 # ------------------------------------------------------------------------------ ICP ------------------------------------------------------------------------------
@@ -217,7 +198,7 @@ def umeyama(sums):
 
 
 def _cell(cell, max_dist):
-    return float(max_dist) / NN_CELLS_PER_MAX_DIST if cell is None else _positive(cell, "cell")
+    return float(max_dist) / NN_CELLS_PER_MAX_DIST if cell is None else gh.positive(cell, "cell")
 
 
 @torch.no_grad()
@@ -227,14 +208,14 @@ def icp(source, target, max_dist, max_iter=20, relative_fitness=1e-6, relative_r
     transformation (numpy [4,4]), fitness, inlier_rmse, iterations (updates applied), history (per evaluation: count, fitness, inlier_rmse),
     correspondence (int64 [|source|] indices into target, -1 without one).  Every evaluation moves the ORIGINAL source by the accumulated
     transformation."""
-    max_dist = _positive(max_dist, "max_dist")
+    max_dist = gh.positive(max_dist, "max_dist")
     if isinstance(max_iter, bool) or not isinstance(max_iter, int) or max_iter < 0:
         raise RuntimeError("`max_iter` must be a non-negative integer")
     cell = _cell(cell, max_dist)
-    src, tgt = _points(source, "source"), _points(target, "target")
+    src, tgt = gh.points(source, "source"), gh.points(target, "target")
     if src.device != tgt.device:
         raise RuntimeError("`source` and `target` must be on the same device")
-    _finite(src, "source")
+    gh.finite(src, "source")
     Q, NT, dev = src.shape[0], tgt.shape[0], src.device
     T = np.eye(4)
     if Q == 0 or NT == 0:
@@ -244,7 +225,7 @@ def icp(source, target, max_dist, max_iter=20, relative_fitness=1e-6, relative_r
     grid = PointGrid(tgt, cell)                      # built once; refuses a non-finite target
     L = _lib()
     nbytes = L.radegs_tnteval_sums_bytes()
-    ws = _workspace(nbytes, dev)
+    ws = gh.workspace(nbytes, dev)
     out = torch.empty(18, dtype=torch.float64, device=dev)
     moved = torch.empty_like(src)
     state = {}
@@ -252,10 +233,10 @@ def icp(source, target, max_dist, max_iter=20, relative_fitness=1e-6, relative_r
     def evaluate():
         with torch.cuda.device(dev):
             stream = _C._stream(dev)
-            _check(L.radegs_tnteval_transform(Q, _C._ptr(src), _doubles(T[:3].reshape(-1)), _C._ptr(moved), stream), "radegs_tnteval_transform")
+            gh.check(L.radegs_tnteval_transform(Q, _C._ptr(src), gh.doubles(T[:3].reshape(-1)), _C._ptr(moved), stream), "radegs_tnteval_transform")
             _, index = grid.nearest(moved, max_dist)
-            _check(L.radegs_tnteval_pair_sums(Q, _C._ptr(moved), NT, _C._ptr(tgt), _C._ptr(index), _C._ptr(ws), nbytes, _C._ptr(out), stream),
-                   "radegs_tnteval_pair_sums")
+            gh.check(L.radegs_tnteval_pair_sums(Q, _C._ptr(moved), NT, _C._ptr(tgt), _C._ptr(index), _C._ptr(ws), nbytes, _C._ptr(out), stream),
+                     "radegs_tnteval_pair_sums")
         sums = out.cpu().numpy()                     # the one host read of an evaluation
         n = int(sums[0])
         state["index"] = index
@@ -317,8 +298,8 @@ def precision_recall(dist_s, dist_t, threshold, plot_stretch=5):
     """evaluation.get_f1_score_histo2 on float64 GPU vectors (inf allowed: in no bin, not below the threshold).  Returns (precision, recall,
     fscore, edges_source, cum_source, edges_target, cum_target), the scores Python floats and the rest numpy, value for value the reference's
     -- its zeros for an empty input included."""
-    threshold = _positive(threshold, "threshold")
-    _positive(plot_stretch, "plot_stretch")
+    threshold = gh.positive(threshold, "threshold")
+    gh.positive(plot_stretch, "plot_stretch")
     d1, d2 = _vector(dist_s, "dist_s"), _vector(dist_t, "dist_t")
     if not (len(d1) and len(d2)):
         return 0, 0, 0, np.array([0]), np.array([0]), np.array([0]), np.array([0])
@@ -330,8 +311,8 @@ def precision_recall(dist_s, dist_t, threshold, plot_stretch=5):
     out = torch.empty((2, edges.shape[0]), dtype=torch.int64, device=dev)      # per side: the bins, then the count below the threshold
     with torch.cuda.device(dev):
         for row, d in zip(out, (d1, d2)):
-            _check(_lib().radegs_tnteval_histogram(d.shape[0], _C._ptr(d), edges.shape[0], _C._ptr(e), threshold, _C._ptr(row),
-                                                   ctypes.c_void_p(row.data_ptr() + 8 * (edges.shape[0] - 1)), _C._stream(dev)), "radegs_tnteval_histogram")
+            gh.check(_lib().radegs_tnteval_histogram(d.shape[0], _C._ptr(d), edges.shape[0], _C._ptr(e), threshold, _C._ptr(row),
+                                                     ctypes.c_void_p(row.data_ptr() + 8 * (edges.shape[0] - 1)), _C._stream(dev)), "radegs_tnteval_histogram")
     h = out.cpu().numpy()                                                        # the one host read
     precision, recall = float(h[0, -1]) / float(len(d1)), float(h[1, -1]) / float(len(d2))
     fscore = 2 * recall * precision / (recall + precision) if recall + precision else float("nan")   # upstream divides by zero there
@@ -349,8 +330,8 @@ def distance_cut(threshold, plot_stretch=5):
 @torch.no_grad()
 def cloud_distances(queries, cloud, cut, cell=None):
     """compute_point_cloud_distance cut at `cut`: (dist float64 [Q], index int64 [Q]), inf and -1 where the nearest point is not closer"""
-    cut = _positive(cut, "cut")
-    q, c = _points(queries, "queries"), _points(cloud, "cloud")
+    cut = gh.positive(cut, "cut")
+    q, c = gh.points(queries, "queries"), gh.points(cloud, "cloud")
     if c.shape[0] == 0 or q.shape[0] == 0:
         return (torch.full((q.shape[0],), math.inf, dtype=torch.float64, device=q.device), torch.full((q.shape[0],), -1, dtype=torch.int64, device=q.device))
     return PointGrid(c, _cell(cell, cut)).nearest(q, cut)
@@ -362,14 +343,14 @@ def evaluate(vertices, faces, gt_points, init_transform, volume, tau, plot_stret
     distance at which the two nearest-neighbour passes give up (default distance_cut(tau, plot_stretch); no score depends on it).  Returns
     a dict: precision, recall, fscore, edges_source, cum_source, edges_target, cum_target, r2, r3, r (the registrations), transformation,
     s, t (the two evaluated clouds), dist1 / idx1 (s to t), dist2 / idx2 (t to s)."""
-    tau = _positive(tau, "tau")
-    _positive(plot_stretch, "plot_stretch")
+    tau = gh.positive(tau, "tau")
+    gh.positive(plot_stretch, "plot_stretch")
     init = _matrix(init_transform, "init_transform")
     if init is None:
         raise RuntimeError("`init_transform` must be a 4x4 matrix")
     if not isinstance(volume, CropVolume):
         raise RuntimeError("`volume` must be a CropVolume")
-    gt = _points(gt_points, "gt_points")
+    gt = gh.points(gt_points, "gt_points")
     pcd = mesh_points(vertices, faces)
     r2 = registration_vol_ds(pcd, gt, init, volume, tau, tau * 80, 20)
     r3 = registration_vol_ds(pcd, gt, r2["transformation"], volume, tau / 2.0, tau * 20, 20)
@@ -382,7 +363,7 @@ def evaluate(vertices, faces, gt_points, init_transform, volume, tau, plot_stret
 @torch.no_grad()
 def evaluate_histo(source, target, trans, volume, voxel_size, threshold, plot_stretch=5, cut=None):
     """evaluation.EvaluateHisto without its normals and files: move, crop and voxel-thin both clouds, distances both ways, the scores"""
-    cut = distance_cut(threshold, plot_stretch) if cut is None else _positive(cut, "cut")
+    cut = distance_cut(threshold, plot_stretch) if cut is None else gh.positive(cut, "cut")
     s = voxel_down_sample(crop_points(source, volume, _matrix(trans, "trans"))[0], voxel_size)[0]
     t = voxel_down_sample(crop_points(target, volume)[0], voxel_size)[0]
     dist1, idx1 = cloud_distances(s, t, cut)

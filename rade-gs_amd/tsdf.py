@@ -9,48 +9,29 @@ import math
 import numpy as np
 import torch
 
+import geom_host as gh
 from diff_gaussian_rasterization import _C
-from tetmesh import ERR_TOO_LARGE, _check, _workspace
-from tetmesh import _lib as _tetmesh_lib
+from geom_host import f32, i32, ll, pf32, sz, vp
 
-_bound = False
 BLOCK_RESOLUTION = 16        # the kernels' block: 16^3 voxels, one workgroup of 256 threads walks it in 16 steps
 COORD_LIMIT = 1 << 20        # block coordinates live in [-2^20, 2^20): 21 bits per axis of the 63-bit key
 MAX_BLOCKS = (1 << 19) - 1   # radegs_tsdf_extract_*: every voxel index below 2^31
 
+_SIGNATURES = {
+    "radegs_tsdf_unique_bytes": (sz, [ll]),
+    "radegs_tsdf_touch": (i32, [i32, i32, vp, pf32, f32, f32, f32, f32, vp, sz, vp, vp]),
+    "radegs_tsdf_unique_plan": (i32, [ll, vp, ll, vp, vp, sz, vp, vp]),
+    "radegs_tsdf_unique_emit": (i32, [ll, vp, ll, vp, vp]),
+    "radegs_tsdf_insert_apply": (i32, [ll, vp, ll, vp, vp, ll, ll, vp, vp, vp, vp, vp]),
+    "radegs_tsdf_integrate": (i32, [ll, vp, vp, ll, i32, i32, vp, vp, pf32, f32, f32, f32, vp, vp, vp, vp]),
+    "radegs_tsdf_extract_bytes": (sz, [ll]),
+    "radegs_tsdf_extract_plan": (i32, [ll, vp, vp, vp, vp, f32, vp, sz, vp, vp]),
+    "radegs_tsdf_extract_emit": (i32, [ll, vp, vp, vp, vp, f32, vp, ll, ll, vp, vp, vp, vp]),
+}
+
 
 def _lib():
-    global _bound
-    L = _tetmesh_lib()
-    if not _bound:
-        vp, ll, i32, sz, f32 = ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_size_t, ctypes.c_float
-        cam = ctypes.POINTER(ctypes.c_float)
-        L.radegs_tsdf_unique_bytes.restype = sz
-        L.radegs_tsdf_unique_bytes.argtypes = [ll]
-        L.radegs_tsdf_touch.restype = i32
-        L.radegs_tsdf_touch.argtypes = [i32, i32, vp, cam, f32, f32, f32, f32, vp, sz, vp, vp]
-        L.radegs_tsdf_unique_plan.restype = i32
-        L.radegs_tsdf_unique_plan.argtypes = [ll, vp, ll, vp, vp, sz, vp, vp]
-        L.radegs_tsdf_unique_emit.restype = i32
-        L.radegs_tsdf_unique_emit.argtypes = [ll, vp, ll, vp, vp]
-        L.radegs_tsdf_insert_apply.restype = i32
-        L.radegs_tsdf_insert_apply.argtypes = [ll, vp, ll, vp, vp, ll, ll, vp, vp, vp, vp, vp]
-        L.radegs_tsdf_integrate.restype = i32
-        L.radegs_tsdf_integrate.argtypes = [ll, vp, vp, ll, i32, i32, vp, vp, cam, f32, f32, f32, vp, vp, vp, vp]
-        L.radegs_tsdf_extract_bytes.restype = sz
-        L.radegs_tsdf_extract_bytes.argtypes = [ll]
-        L.radegs_tsdf_extract_plan.restype = i32
-        L.radegs_tsdf_extract_plan.argtypes = [ll, vp, vp, vp, vp, f32, vp, sz, vp, vp]
-        L.radegs_tsdf_extract_emit.restype = i32
-        L.radegs_tsdf_extract_emit.argtypes = [ll, vp, vp, vp, vp, f32, vp, ll, ll, vp, vp, vp, vp]
-        _bound = True
-    return L
-
-
-def _positive(value, name):
-    if not (isinstance(value, (int, float)) and not isinstance(value, bool) and math.isfinite(value) and value > 0):
-        raise RuntimeError(f"`{name}` must be a positive finite number")
-    return float(value)
+    return gh.bind(_SIGNATURES)
 
 
 def _matrix(m, name, shape):
@@ -110,17 +91,17 @@ def unique_block_coordinates(coords):
     L = _lib()
     nbytes = L.radegs_tsdf_unique_bytes(n)
     if n and nbytes == 0:
-        _check(ERR_TOO_LARGE, "unique_block_coordinates")
-    ws = _workspace(nbytes, dev)
+        gh.check(gh.ERR_TOO_LARGE, "unique_block_coordinates")
+    ws = gh.workspace(nbytes, dev)
     counts = torch.zeros(3, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
         stream = _C._stream(dev)
-        _check(L.radegs_tsdf_unique_plan(n, _C._ptr(c), 0, None, _C._ptr(ws), nbytes, _C._ptr(counts), stream), "radegs_tsdf_unique_plan")
+        gh.check(L.radegs_tsdf_unique_plan(n, _C._ptr(c), 0, None, _C._ptr(ws), nbytes, _C._ptr(counts), stream), "radegs_tsdf_unique_plan")
         n_unique, _, bad = counts.tolist()          # the one host read
         if bad:
             _range_error("unique_block_coordinates")
         out = torch.empty((n_unique, 3), dtype=torch.int32, device=dev)
-        _check(L.radegs_tsdf_unique_emit(n, _C._ptr(ws), n_unique, _C._ptr(out), stream), "radegs_tsdf_unique_emit")
+        gh.check(L.radegs_tsdf_unique_emit(n, _C._ptr(ws), n_unique, _C._ptr(out), stream), "radegs_tsdf_unique_emit")
     return out
 
 
@@ -130,7 +111,7 @@ class VoxelBlockGrid:
     The grid: `keys` int64 [n] ascending, `slots` int32 [n] into `tsdf` / `weight` [capacity,4096] and `color` [capacity,4096,3]."""
 
     def __init__(self, voxel_size=0.002, block_resolution=16, block_count=50000, with_color=True, device="cuda:0"):
-        self.voxel_size = _positive(voxel_size, "voxel_size")
+        self.voxel_size = gh.positive(voxel_size, "voxel_size")
         if block_resolution != BLOCK_RESOLUTION:
             raise RuntimeError(f"`block_resolution` must be {BLOCK_RESOLUTION}: the kernels are written for 16^3 blocks, got {block_resolution}")
         if not isinstance(block_count, int) or isinstance(block_count, bool) or not 1 <= block_count <= MAX_BLOCKS:
@@ -168,8 +149,8 @@ class VoxelBlockGrid:
             self._allocate(capacity)
 
     def _params(self, depth_scale, depth_max, trunc_voxel_multiplier):
-        return (_positive(depth_scale, "depth_scale"), _positive(depth_max, "depth_max"),
-                self.voxel_size * _positive(trunc_voxel_multiplier, "trunc_voxel_multiplier"))
+        return (gh.positive(depth_scale, "depth_scale"), gh.positive(depth_max, "depth_max"),
+                self.voxel_size * gh.positive(trunc_voxel_multiplier, "trunc_voxel_multiplier"))
 
     def block_coordinates(self):
         """the grid's block coordinates, int32 [n,3] in key order"""
@@ -197,17 +178,17 @@ class VoxelBlockGrid:
         n = 4 * (H // 4) * (W // 4)
         L = _lib()
         nbytes = L.radegs_tsdf_unique_bytes(n)
-        ws = _workspace(nbytes, self.device)
+        ws = gh.workspace(nbytes, self.device)
         counts = torch.zeros(3, dtype=torch.int64, device=self.device)
         with torch.cuda.device(self.device):
             stream = _C._stream(self.device)
-            _check(L.radegs_tsdf_touch(W, H, _C._ptr(d), cam, scale, dmax, trunc, self.block_size, _C._ptr(ws), nbytes, _C._ptr(counts), stream),
-                   "radegs_tsdf_touch")
+            gh.check(L.radegs_tsdf_touch(W, H, _C._ptr(d), cam, scale, dmax, trunc, self.block_size, _C._ptr(ws), nbytes, _C._ptr(counts), stream),
+                     "radegs_tsdf_touch")
             n_unique, _, bad = counts.tolist()      # the one host read
             if bad:
                 _range_error("compute_unique_block_coordinates")
             out = torch.empty((n_unique, 3), dtype=torch.int32, device=self.device)
-            _check(L.radegs_tsdf_unique_emit(n, _C._ptr(ws), n_unique, _C._ptr(out), stream), "radegs_tsdf_unique_emit")
+            gh.check(L.radegs_tsdf_unique_emit(n, _C._ptr(ws), n_unique, _C._ptr(out), stream), "radegs_tsdf_unique_emit")
         return out
 
     # ---------------------------------------------------------------- integrate ----------------------------------------------------------------
@@ -235,13 +216,13 @@ class VoxelBlockGrid:
         L = _lib()
         nbytes = L.radegs_tsdf_unique_bytes(n)
         if nbytes == 0:
-            _check(ERR_TOO_LARGE, "integrate")
-        ws = _workspace(nbytes, self.device)
+            gh.check(gh.ERR_TOO_LARGE, "integrate")
+        ws = gh.workspace(nbytes, self.device)
         counts = torch.zeros(3, dtype=torch.int64, device=self.device)
         with torch.cuda.device(self.device):
             stream = _C._stream(self.device)
-            _check(L.radegs_tsdf_unique_plan(n, _C._ptr(coords), self.n, _C._ptr(self.keys), _C._ptr(ws), nbytes, _C._ptr(counts), stream),
-                   "radegs_tsdf_unique_plan")
+            gh.check(L.radegs_tsdf_unique_plan(n, _C._ptr(coords), self.n, _C._ptr(self.keys), _C._ptr(ws), nbytes, _C._ptr(counts), stream),
+                     "radegs_tsdf_unique_plan")
             n_unique, n_new, bad = counts.tolist()  # the one host read
             if bad:
                 _range_error("integrate")
@@ -250,17 +231,17 @@ class VoxelBlockGrid:
             slots = torch.empty(self.n + n_new, dtype=torch.int32, device=self.device)
             active_slots = torch.empty(n_unique, dtype=torch.int32, device=self.device)
             active_coords = torch.empty((n_unique, 3), dtype=torch.int32, device=self.device)
-            _check(L.radegs_tsdf_insert_apply(n, _C._ptr(ws), self.n, _C._ptr(self.keys), _C._ptr(self.slots), n_unique, n_new, _C._ptr(keys),
-                                              _C._ptr(slots), _C._ptr(active_slots), _C._ptr(active_coords), stream), "radegs_tsdf_insert_apply")
+            gh.check(L.radegs_tsdf_insert_apply(n, _C._ptr(ws), self.n, _C._ptr(self.keys), _C._ptr(self.slots), n_unique, n_new, _C._ptr(keys),
+                                                _C._ptr(slots), _C._ptr(active_slots), _C._ptr(active_coords), stream), "radegs_tsdf_insert_apply")
             if n_new:                               # the new blocks' slots are one range of the storage
                 self.tsdf[self.n:self.n + n_new].zero_()
                 self.weight[self.n:self.n + n_new].zero_()
                 if self.with_color:
                     self.color[self.n:self.n + n_new].zero_()
             self.keys, self.slots, self.n = keys, slots, self.n + n_new
-            _check(L.radegs_tsdf_integrate(n_unique, _C._ptr(active_slots), _C._ptr(active_coords), self.capacity, W, H, _C._ptr(d), _C._ptr(c), cam,
-                                           scale, dmax, trunc, _C._ptr(self.tsdf), _C._ptr(self.weight), _C._ptr(self.color), stream),
-                   "radegs_tsdf_integrate")
+            gh.check(L.radegs_tsdf_integrate(n_unique, _C._ptr(active_slots), _C._ptr(active_coords), self.capacity, W, H, _C._ptr(d), _C._ptr(c), cam,
+                                             scale, dmax, trunc, _C._ptr(self.tsdf), _C._ptr(self.weight), _C._ptr(self.color), stream),
+                     "radegs_tsdf_integrate")
 
     # ----------------------------------------------------------------- extract -----------------------------------------------------------------
     @torch.no_grad()
@@ -275,20 +256,20 @@ class VoxelBlockGrid:
                     torch.empty((0, 3), dtype=torch.float32, device=dev) if self.with_color else None)
         L = _lib()
         nbytes = L.radegs_tsdf_extract_bytes(self.n)
-        ws = _workspace(nbytes, dev)
+        ws = gh.workspace(nbytes, dev)
         counts = torch.zeros(2, dtype=torch.int64, device=dev)
         with torch.cuda.device(dev):
             stream = _C._stream(dev)
-            _check(L.radegs_tsdf_extract_plan(self.n, _C._ptr(self.keys), _C._ptr(self.slots), _C._ptr(self.tsdf), _C._ptr(self.weight),
-                                              float(weight_threshold), _C._ptr(ws), nbytes, _C._ptr(counts), stream), "radegs_tsdf_extract_plan")
+            gh.check(L.radegs_tsdf_extract_plan(self.n, _C._ptr(self.keys), _C._ptr(self.slots), _C._ptr(self.tsdf), _C._ptr(self.weight),
+                                                float(weight_threshold), _C._ptr(ws), nbytes, _C._ptr(counts), stream), "radegs_tsdf_extract_plan")
             V, F = counts.tolist()                  # the one host read: the two sizes
             if V >= 2 ** 32 - 1 or F >= 2 ** 32 - 1:
-                _check(ERR_TOO_LARGE, "extract_triangle_mesh")
+                gh.check(gh.ERR_TOO_LARGE, "extract_triangle_mesh")
             vertices = torch.empty((V, 3), dtype=torch.float32, device=dev)
             faces = torch.empty((F, 3), dtype=torch.int64, device=dev)
             colors = torch.empty((V, 3), dtype=torch.float32, device=dev) if self.with_color else None
-            _check(L.radegs_tsdf_extract_emit(self.n, _C._ptr(self.keys), _C._ptr(self.slots), _C._ptr(self.tsdf), _C._ptr(self.color), self.voxel_size,
-                                              _C._ptr(ws), V, F, _C._ptr(vertices), _C._ptr(faces), _C._ptr(colors), stream), "radegs_tsdf_extract_emit")
+            gh.check(L.radegs_tsdf_extract_emit(self.n, _C._ptr(self.keys), _C._ptr(self.slots), _C._ptr(self.tsdf), _C._ptr(self.color), self.voxel_size,
+                                                _C._ptr(ws), V, F, _C._ptr(vertices), _C._ptr(faces), _C._ptr(colors), stream), "radegs_tsdf_extract_emit")
         return vertices, faces, colors
 
 

@@ -102,6 +102,60 @@ def nearest(cloud, queries, max_dist):
     return dist, index
 
 
+SUM_THREADS, SUM_BLOCKS = 256, 1024
+SUM_MAX_DIST = 10.0 ** 4.8
+
+
+def _halving_tree(a):
+    """the 256-wide tree over axis 1: level w adds element t + w onto element t for t < w, w = 128 .. 1 -> element 0"""
+    a = a.copy()
+    w = SUM_THREADS // 2
+    while w > 0:
+        a[:, :w] += a[:, w:2 * w]
+        w >>= 1
+    return a[:, 0]
+
+
+def _strided_rows(x, lanes):
+    """[n, K] -> [steps, lanes, K]: step j holds rows j * lanes .. ; what is past the end is 0.0, and adding it changes nothing"""
+    steps = max(1, -(-x.shape[0] // lanes))
+    padded = np.zeros((steps * lanes, x.shape[1]))
+    padded[:x.shape[0]] = x
+    return padded.reshape(steps, lanes, x.shape[1])
+
+
+def fixed_order_sum(values, K, max_blocks=SUM_BLOCKS):
+    """The library's two-stage fp64 sum of the [n, K] rows, addition by addition.  nb = min(ceil(n / 256), max_blocks) blocks of 256 threads:
+    thread t of block b adds rows b * 256 + t, + nb * 256, ... in that order, the block's 256 values go through the halving tree; then
+    thread t of one block adds the partials of blocks t, t + 256, ... and the tree runs again.  A row the kernel skips is a row of zeros."""
+    x = np.asarray(values, np.float64).reshape(-1, K)
+    nb = min(max(1, -(-x.shape[0] // SUM_THREADS)), max_blocks)
+    acc = np.zeros((nb * SUM_THREADS, K))
+    for step in _strided_rows(x, nb * SUM_THREADS):
+        acc = acc + step
+    partial = _halving_tree(acc.reshape(nb, SUM_THREADS, K))            # [nb, K]
+    acc = np.zeros((SUM_THREADS, K))
+    for step in _strided_rows(partial, SUM_THREADS):
+        acc = acc + step
+    return _halving_tree(acc[None])[0]
+
+
+def sum_case(n):
+    """The seeded distances of the sum tests: 10 ** U(-6, 6), about a tenth of them at or above SUM_MAX_DIST, a few infinite.  The seed is
+    picked, not arbitrary: tree-shaped sums are accurate to a fraction of the total's last bit, so two of them differ on about one seed in
+    seven only (8 of the seeds 1 .. 59 at n = 600 001), and tests/test_mesheval_restatement.py asserts that this one tells them apart."""
+    rng = np.random.default_rng(8)
+    d = 10.0 ** rng.uniform(-6.0, 6.0, n)
+    d[rng.random(n) < 0.002] = np.inf
+    return d
+
+
+def sum_below(dist, max_dist):
+    """mean_below's (sum, count) of dist < max_dist in the library's order"""
+    below = dist < max_dist
+    return fixed_order_sum(np.stack([np.where(below, dist, 0.0), below.astype(np.float64)], 1), 2)
+
+
 def obs_masks(points, obs_mask, BB, Res, patch=60):
     """three full-length masks: inside the padded box; also inside the volume's index range; also ObsMask set there"""
     points = np.asarray(points, np.float64)

@@ -94,6 +94,18 @@ def test_chamfer_fixture_end_to_end(chamfer_fx):
     assert np.array_equal(host(out["data_in"]), host(out["data_down"])[got["inbound"]]) and out["stl_above"].shape[0] == got["above"].sum()
 
 
+# --------------------------------------------------------------------------- sums ---------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 262144, 262145, 600001])
+def test_mean_below_equals_the_fixed_order_restatement_bit_for_bit(n):
+    """Around the one-block boundary, the last size with one row per thread (1024 x 256), the first with a second stride, and a ragged large
+    one.  Both outputs with ==: the order of the additions is the contract (tests/test_mesheval_restatement.py shows other orders differ)."""
+    import mesh_eval as me
+    d = mr.sum_case(n)
+    got = host(me.mean_below(dev(d), mr.SUM_MAX_DIST))
+    want = mr.sum_below(d, mr.SUM_MAX_DIST)
+    assert got.dtype == np.float64 and got[0] == want[0] and got[1] == want[1], (got, want)
+
+
 # ------------------------------------------------------------------------- sampling -------------------------------------------------------------------------
 def test_sampling_empty_and_degenerate_meshes():
     cloud, counts = sample(np.zeros((0, 3)), np.zeros((0, 3), np.int64))
@@ -141,6 +153,9 @@ def test_sampling_refuses_bad_meshes():
     bad[2, 1] = float("nan")
     with pytest.raises(RuntimeError, match="non-finite"):
         me.sample_mesh_points(bad, torch.tensor([[0, 1, 2]], device=DEV))
+    for density in (True, 0.0, float("inf")):
+        with pytest.raises(RuntimeError, match="`density` must be a positive finite number"):
+            me.sample_mesh_points(v, torch.tensor([[0, 1, 2]], device=DEV), density)
 
 
 # ------------------------------------------------------------------------- thinning -------------------------------------------------------------------------

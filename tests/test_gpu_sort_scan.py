@@ -46,6 +46,8 @@ def _lib():
         L.sortcheck_sort_u32_27.argtypes = [vp, sz, vp, vp, vp, vp, sz, u32, vp, ci]
         L.sortcheck_sort_2xu32.restype = ci                      # temp, temp_bytes, minor, major, major_sorted, perm, s0, s1, s2, n, end bits, stream, n_dev
         L.sortcheck_sort_2xu32.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, sz, ci, ci, vp, vp]
+        L.sortcheck_sort_2xu32_joined.restype = ci               # the same and joined
+        L.sortcheck_sort_2xu32_joined.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, sz, ci, ci, vp, vp, vp]
         L.sortcheck_scan.restype = ci                            # temp, temp_bytes, vals, idx, out, n, stream, packed_out, sq_sum, items
         L.sortcheck_scan.argtypes = [vp, sz, vp, vp, vp, sz, vp, vp, vp, ci]
         _LIB = L
@@ -357,10 +359,10 @@ def ref_pair_perm(minor, major, bits):
     return np.lexsort((minor & mask[0], major & mask[1]))   # stable: ties keep input order
 
 
-def call_sort_2x(minor, major, bits, n=None, m=None, temp_short=0):
-    """One call.  minor / major: host arrays of the capacity `n` (default: their length); m: the device-side count or None.  Returns
-    (rc, major_sorted, perm, untouched) after asserting guards and untouched inputs; untouched: no byte of the outputs, the three scratch
-    arrays or temp was written."""
+def call_sort_2x(minor, major, bits, n=None, m=None, temp_short=0, join=True):
+    """One call.  minor / major: host arrays of the capacity `n` (default: their length); m: the device-side count or None; join=False
+    passes a null `joined`, join=None calls the entry point that has no such argument.  Returns (rc, major_sorted, perm, untouched, joined) after asserting guards and untouched inputs; untouched: no
+    byte of the outputs, the three scratch arrays or temp was written; joined: the 8-byte-per-item output as raw bytes."""
     L = _lib()
     n = len(minor) if n is None else n
     d_minor, d_major = _upload(minor), _upload(major)
@@ -368,23 +370,30 @@ def call_sort_2x(minor, major, bits, n=None, m=None, temp_short=0):
     temp_bytes = L.sortcheck_sort_temp_bytes(n) - temp_short
     temp = Guarded(temp_bytes, TEMP_BYTE)
     outs = [Guarded(len(minor) * 4, OUT_BYTE) for _ in range(5)]      # major_sorted, perm, s0, s1, s2
-    rc = L.sortcheck_sort_2xu32(temp.ptr, temp_bytes, _ptr(d_minor), _ptr(d_major), *[o.ptr for o in outs], n, bits[0], bits[1], _stream(), _ptr(d_m))
+    joined = Guarded(len(minor) * 8, OUT_BYTE)
+    args = (temp.ptr, temp_bytes, _ptr(d_minor), _ptr(d_major), *[o.ptr for o in outs], n, bits[0], bits[1], _stream(), _ptr(d_m))
+    rc = L.sortcheck_sort_2xu32(*args) if join is None else L.sortcheck_sort_2xu32_joined(*args, joined.ptr if join else None)
     if DEV != "cpu":
         torch.cuda.synchronize()
     assert temp.guards_intact(), "temp guards overwritten"
     for name, o in zip(("major_sorted", "perm", "s0", "s1", "s2"), outs):
         assert o.guards_intact(), name + " guards overwritten"
+    assert joined.guards_intact(), "joined guards overwritten"
     assert _unchanged(d_minor, minor), "minor modified"
     assert _unchanged(d_major, major), "major modified"
     assert d_m is None or int(d_m.cpu()[0]) == np.int32(np.uint32(m)), "n_dev modified"
     untouched = bool((temp.host() == TEMP_BYTE).all()) and all(bool((o.host() == OUT_BYTE).all()) for o in outs)
-    return rc, outs[0].host(np.uint32), outs[1].host(np.uint32), untouched
+    return rc, outs[0].host(np.uint32), outs[1].host(np.uint32), untouched, joined.host()
 
 
 def check_sort_2x(minor, major, bits, perm, m=None):
-    rc, major_sorted, perm_out, _ = call_sort_2x(minor, major, bits, m=m)
+    rc, major_sorted, perm_out, _, joined = call_sort_2x(minor, major, bits, m=m)
     assert rc == 0, "hip error %d" % rc
     cnt = len(perm)
+    want = major[perm].astype(np.uint64) << np.uint64(32) | minor[perm].astype(np.uint64)      # the raw words, the bits above the end bits too
+    bad = np.flatnonzero(joined[:8 * cnt].view(np.uint64) != want)
+    assert bad.size == 0, "joined differs at %d of %d positions, first %d" % (bad.size, cnt, bad[0])
+    assert (joined[8 * cnt:] == OUT_BYTE).all(), "joined written past the first %d positions" % cnt
     bad = np.flatnonzero(perm_out[:cnt] != perm.astype(np.uint32))
     assert bad.size == 0, "perm differs at %d of %d positions, first %d (a stable order keeps ties in input order)" % (bad.size, cnt, bad[0])
     bad = np.flatnonzero(major_sorted[:cnt] != major[perm])
@@ -422,13 +431,27 @@ def test_sort_2xu32_device_side_count(bits):
 def test_sort_2xu32_host_side_answers():
     """Answers given before anything is launched: n = 0, a temp buffer one byte short, an end bit outside 1 .. 32."""
     minor, major = make_pairs("uniform", 1000, np.random.default_rng(5))
-    rc, _, _, untouched = call_sort_2x(minor, major, (17, 21), n=0)
-    assert rc == 0 and untouched
-    rc, _, _, untouched = call_sort_2x(minor, major, (17, 21), temp_short=1)
-    assert rc == HIP_ERROR_INVALID_VALUE and untouched
+    rc, _, _, untouched, joined = call_sort_2x(minor, major, (17, 21), n=0)
+    assert rc == 0 and untouched and (joined == OUT_BYTE).all()
+    rc, _, _, untouched, joined = call_sort_2x(minor, major, (17, 21), temp_short=1)
+    assert rc == HIP_ERROR_INVALID_VALUE and untouched and (joined == OUT_BYTE).all()
     for bits in ((0, 21), (33, 21), (17, 0), (17, 33)):
-        rc, _, _, untouched = call_sort_2x(minor, major, bits)
-        assert rc == HIP_ERROR_INVALID_VALUE and untouched, bits
+        rc, _, _, untouched, joined = call_sort_2x(minor, major, bits)
+        assert rc == HIP_ERROR_INVALID_VALUE and untouched and (joined == OUT_BYTE).all(), bits
+
+
+def test_sort_2xu32_without_join():
+    """A null `joined`, and the entry point without the argument: nothing is written there, and perm and major_sorted are what the call
+    with it gives."""
+    minor, major = make_pairs("uniform", 2049, np.random.default_rng(6))
+    with_join = call_sort_2x(minor, major, (17, 21))
+    assert with_join[0] == 0
+    for join in (False, None):
+        rc, major_sorted, perm, _, joined = call_sort_2x(minor, major, (17, 21), join=join)
+        assert rc == 0
+        assert (joined == OUT_BYTE).all()
+        assert np.array_equal(perm, with_join[2]) and np.array_equal(perm, ref_pair_perm(minor, major, (17, 21)).astype(np.uint32))
+        assert np.array_equal(major_sorted, with_join[1]) and np.array_equal(major_sorted, major[perm])
 
 
 # ---------------------------------------------------------------- scan ----------------------------------------------------------------

@@ -152,6 +152,34 @@ def test_voxel_down_sample_refuses_more_than_2_21_cells(axis):
 
 
 # -------------------------------------------------------------------------------- ICP --------------------------------------------------------------------------------
+@pytest.mark.parametrize("Q", [1, 257, 262145])
+def test_pair_sums_equal_the_fixed_order_restatement_bit_for_bit(Q):
+    """One block, two blocks, and the first size with a second stride (1024 blocks of 256 threads, one query more); about one index in twenty
+    is -1 or past the target and adds nothing.  All 18 outputs with ==: the sums are the same additions in the same order."""
+    import tnt_eval as te
+    from diff_gaussian_rasterization import _C
+    rng = np.random.default_rng(100 + Q)
+    NT = 1000
+    target = rng.normal(0.0, 3.0, (NT, 3)) + [40.0, -25.0, 7.0]
+    index = rng.integers(0, NT, Q)
+    skipped = rng.random(Q) < 0.05
+    index[skipped] = np.where(rng.random(Q) < 0.5, -1, NT + rng.integers(0, 5, Q))[skipped]
+    if Q == 1:
+        index[0] = 3
+    moved = target[np.clip(index, 0, NT - 1)] + rng.normal(0.0, 0.05, (Q, 3))
+    want = tr.pair_sums(moved, target, index)
+    assert want[0] == np.count_nonzero((index >= 0) & (index < NT)) > 0
+    L = te._lib()
+    nbytes = L.radegs_tnteval_sums_bytes()
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
+    out = torch.full((18,), float("nan"), dtype=torch.float64, device=DEV)
+    m, t, i = dev(moved), dev(target), dev(index)
+    rc = L.radegs_tnteval_pair_sums(Q, m.data_ptr(), NT, t.data_ptr(), i.data_ptr(), ws.data_ptr(), nbytes, out.data_ptr(), _C._stream(torch.device(DEV)))
+    assert rc == 0
+    got = host(out)
+    assert np.array_equal(got, want), (np.flatnonzero(got != want), got, want)
+
+
 def check_icp(got, want, init=None):
     assert got["iterations"] == want["iterations"] and len(got["history"]) == len(want["history"])
     assert [h["count"] for h in got["history"]] == [h["count"] for h in want["history"]]

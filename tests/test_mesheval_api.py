@@ -139,6 +139,11 @@ def test_bad_arguments_raise_before_any_launch():
         me.dtu_chamfer(v, f, v, torch.ones(2, 2, 2, dtype=torch.uint8), [[0, 0, 0], [1, 1, 1]], 0.5, [0, 0, 1, 0])
     with pytest.raises(RuntimeError, match="no CPU implementation"):
         me.dilate_mask(torch.ones(5, 5))
+    import geom_host
+    for bad in (True, 0, -1.0, float("nan"), float("inf"), "1", None):       # density, cell, max_dist, radius: bools are no numbers here
+        with pytest.raises(RuntimeError, match="`density` must be a positive finite number"):
+            geom_host.positive(bad, "density")
+    assert geom_host.positive(3, "density") == 3.0
     with pytest.raises(RuntimeError, match="float32 or float64"):
         me.cull_mesh(v.half(), f, [])
     with pytest.raises(RuntimeError, match="no CPU implementation"):

@@ -122,6 +122,26 @@ def test_write_ply_round_trips_through_a_numpy_reader(tmp_path):
         tetmesh.write_ply(path, v, f + 40)
 
 
+@pytest.mark.parametrize("name", ["tetmesh", "mesh_eval", "tsdf", "tnt_eval", "tnt_cull"])
+def test_geometry_modules_bind_their_own_table(name):
+    """every geometry module binds its own signature table through geom_host, any number of times, and borrows no private name from a sibling"""
+    import importlib
+    mod = importlib.import_module(name)
+    L = mod._lib()
+    assert mod._lib() is L
+    assert mod._SIGNATURES, name
+    for sym, (restype, argtypes) in mod._SIGNATURES.items():
+        fn = getattr(L, sym)
+        assert fn.argtypes is not None and list(fn.argtypes) == list(argtypes), sym
+        assert fn.restype is restype, sym
+    src = inspect.getsource(mod)
+    assert not re.search(r"\b_bound\b", src), name
+    siblings = "geom_host|tetmesh|mesh_eval|tsdf|tnt_eval|tnt_cull"
+    for m in re.finditer(r"^from (%s) import (.+)$" % siblings, src, re.M):
+        assert not [n for n in re.split(r"[,\s()]+", m.group(2)) if n.startswith("_")], m.group(0)
+    assert not re.search(r"\b(gh|%s)\._[a-z]" % siblings, src), name
+
+
 @_needs_llvm_tools
 def test_tetmesh_kernels_use_no_scratch(code_objects):  # noqa: F811
     found = {k: v[0] for k, v in code_objects.items() if "3rgt" in k}          # namespace rgt: radegs_tetmesh.hip
@@ -132,9 +152,11 @@ def test_tetmesh_kernels_use_no_scratch(code_objects):  # noqa: F811
         assert r["scratch"] == 0, (hits[0], r)
         assert r["vgpr"] <= 64, (hits[0], r)    # streaming kernels: nothing may cost them the 8 waves per SIMD
     assert len(found) == len(KERNELS), sorted(found)
-    # the gather between the two sorts of the edge pairs lives with rg::radix_sort_order_2xu32 (radegs_sort.hip): the same two limits
-    hits = [k for k in code_objects if k.startswith("_ZN2rg") and "13gather_kernelE" in k]
-    assert len(hits) == 1, hits
-    r = code_objects[hits[0]][0]
-    assert r["scratch"] == 0, (hits[0], r)
-    assert r["vgpr"] <= 64, (hits[0], r)
+    # the gather between the two sorts of the edge pairs and the join of the sorted words live with rg::radix_sort_order_2xu32
+    # (radegs_sort.hip): the same two limits
+    for part in ("13gather_kernelE", "11join_kernelE"):
+        hits = [k for k in code_objects if k.startswith("_ZN2rg") and part in k]
+        assert len(hits) == 1, hits
+        r = code_objects[hits[0]][0]
+        assert r["scratch"] == 0, (hits[0], r)
+        assert r["vgpr"] <= 64, (hits[0], r)

@@ -18,7 +18,7 @@ from test_kernel_resources import pytestmark as _needs_llvm_tools
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ("radegs_tnteval_centroids", "radegs_tnteval_transform", "radegs_tnteval_crop", "radegs_tnteval_voxel_bytes", "radegs_tnteval_voxel_plan",
            "radegs_tnteval_voxel_emit", "radegs_tnteval_sums_bytes", "radegs_tnteval_pair_sums", "radegs_tnteval_histogram")
-KERNELS = ("centroid_kernel", "transform_kernel", "crop_kernel", "voxel_key_kernel", "join_first_kernel", "first_kernel", "voxel_counts_kernel",
+KERNELS = ("centroid_kernel", "transform_kernel", "crop_kernel", "voxel_key_kernel", "first_kernel", "voxel_counts_kernel",
            "voxel_emit_kernel", "pair_sums_partial_kernel", "pair_sums_final_kernel", "pair_moments_partial_kernel", "pair_moments_final_kernel",
            "histogram_kernel")
 POLY = [[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [0.0, 0.0, 1.0]]

@@ -8,6 +8,8 @@ must still decide alike and the comparison can be exact.  Makers of inputs redra
 import numpy as np
 from scipy.spatial import cKDTree
 
+from mesheval_restatement import fixed_order_sum
+
 REL = 1e-9          # distances against max_dist / tau / a bin edge, first against second neighbour, points against polygon edges and bounds
 VOXEL_MARGIN = 1e-6  # of a voxel, from a voxel face
 MAX_POINT_NUMBER = 4e6
@@ -166,6 +168,24 @@ def umeyama(s, t):
     T = np.eye(4)
     T[:3, :3], T[:3, 3] = c * R, mu_t - c * (R @ mu_s)
     return T
+
+
+def pair_sums(moved, target, index):
+    """radegs_tnteval_pair_sums' 18 outputs, from the kernel comments of radegs_tnteval.hip, in the library's order of additions.  A pair is a
+    query q with index[q] in [0, NT): s = moved[q], t = target[index[q]]; every other query adds nothing.
+        [0, 8)   count, sum s, sum t, sum (dx dx + dy dy) + dz dz   with d = s - t
+        means6 = sum s / count, sum t / count   (zeros without a pair)
+        [8, 18)  sum dt[r] ds[c] by rows, sum (ds0 ds0 + ds1 ds1) + ds2 ds2   with ds = s - mean s, dt = t - mean t"""
+    moved, target, index = np.asarray(moved, np.float64).reshape(-1, 3), np.asarray(target, np.float64).reshape(-1, 3), np.asarray(index, np.int64)
+    pair = (index >= 0) & (index < target.shape[0])
+    s, t = moved, target[np.where(pair, index, 0)]
+    d = s - t
+    rows = np.concatenate([np.ones((s.shape[0], 1)), s, t, ((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])[:, None]], 1)
+    sums = fixed_order_sum(np.where(pair[:, None], rows, 0.0), 8)
+    means6 = sums[1:7] / sums[0] if sums[0] > 0.0 else np.zeros(6)
+    ds, dt = s - means6[:3], t - means6[3:]
+    rows = np.concatenate([(dt[:, :, None] * ds[:, None, :]).reshape(-1, 9), ((ds[:, 0] * ds[:, 0] + ds[:, 1] * ds[:, 1]) + ds[:, 2] * ds[:, 2])[:, None]], 1)
+    return np.concatenate([sums, fixed_order_sum(np.where(pair[:, None], rows, 0.0), 10)])
 
 
 def icp(source, target, max_dist, max_iter=20, relative_fitness=1e-6, relative_rmse=1e-6, check=True):
