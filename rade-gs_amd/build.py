@@ -39,7 +39,7 @@ UNITS = {
     "radegs_prims": ["radegs_prims.hip"],
     "radegs_sort": ["radegs_sort.hip", "rg_prims.h", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
     "radegs_kernels": ["radegs_kernels.hip", "rg_launch.inc", "rg_streams.inc", "rg_integrate.inc", "rg_per_gaussian.inc", "rg_blend_bwd_body.inc", "rg_math.h", "rg_blend.h", "rg_preprocess.h", "rg_preprocess_bwd.h",
-                       "rg_layout.h", "rg_prims.h", os.path.join("..", "..", "include", "radegs.h")],
+                       "rg_layout.h", "rg_prims.h", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
     "radegs_normals": ["radegs_normals.hip", "rg_reduce.h", os.path.join("..", "..", "include", "radegs.h")],
     "radegs_filter3d": ["radegs_filter3d.hip", os.path.join("..", "..", "include", "radegs.h")],
     "radegs_photometric": ["radegs_photometric.hip", "rg_reduce.h", os.path.join("..", "..", "include", "radegs.h")],
@@ -51,7 +51,7 @@ UNITS = {
     "radegs_tsdf": ["radegs_tsdf.hip", "rg_mc_tables.h", "rg_prims.h", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
     "radegs_tnteval": ["radegs_tnteval.hip", "rg_prims.h", "rg_reduce.h", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
     "radegs_tntcull": ["radegs_tntcull.hip", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
-    "radegs_appearance": ["radegs_appearance.hip", "rg_reduce.h", os.path.join("..", "..", "include", "radegs.h")],
+    "radegs_appearance": ["radegs_appearance.hip", "rg_reduce.h", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
 }
 # Units outside the rasterizer's decision chain have no bit-exactness contract with the oracle: let them contract to fma.
 # radegs_filter3d calls expf: under `fast` the compiler also contracts INSIDE expf's expansion (x*log2e - round(x*log2e) becomes one fma and

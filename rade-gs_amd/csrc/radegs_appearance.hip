@@ -25,6 +25,7 @@
 
 #include "../../include/radegs.h"
 #include "rg_reduce.h"
+#include "rg_workspace.h"
 
 namespace rgap {
 
@@ -553,10 +554,9 @@ static bool make_dgeo(int origH, int origW, DGeo& g) {
   return true;
 }
 
-static size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 constexpr size_t PACK_BYTES = PACK_FLOATS * sizeof(float);
 constexpr size_t FWD_BYTES = PACK_BYTES + MAXB * sizeof(double);
-static size_t wpartial_bytes() { return align256((size_t)MAXB * NWG * sizeof(float)); }
+static size_t wpartial_bytes() { return rg::align256((size_t)MAXB * NWG * sizeof(float)); }
 
 }  // namespace rgap
 

@@ -117,7 +117,9 @@ __global__ void __launch_bounds__(kSortThreads) scatter_kernel(const K* __restri
   __shared__ uint32_t local_start[BINS];      // position of each digit's first item in the block-local sorted order
   // 16-bit counters (a wave's run has at most 64 * ITEMS = 2 048 items, a block 8 192): with ITEMS = 32 and 16-bit keys the workgroup's LDS
   // is 53.3 KB instead of 55.3 -- THREE workgroups per CU (160 KB) instead of two (round 6; C5's 50 M-instance tile sort)
-  __shared__ uint16_t wave_cnt[4][BINS];      // histogram of each wave's run, then running rank counters
+  // (counted through uint32_t atomics on pairs of counters: rows of an even number of counters, each starting on a 4-byte boundary)
+  static_assert(BINS % 2 == 0, "scatter_kernel: wave_cnt is updated two 16-bit counters at a time");
+  __shared__ alignas(4) uint16_t wave_cnt[4][BINS];   // histogram of each wave's run, then running rank counters
   __shared__ uint32_t scan_tmp[4];
   __shared__ K lds_k[BLOCK_ITEMS];            // the block's items reordered by digit (stable), so that the global
   __shared__ uint32_t lds_v[BLOCK_ITEMS];     // writes below go out in contiguous per-digit runs

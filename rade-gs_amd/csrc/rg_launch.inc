@@ -751,16 +751,14 @@ struct OrderedScratch {
   float* part = nullptr; uint32_t* keys = nullptr; uint32_t* pos = nullptr; void* sort_temp = nullptr; size_t part_bytes = 0, sort_bytes = 0, total = 0;
   static OrderedScratch carve(void* base, size_t R, bool coord) {
     OrderedScratch o;
-    char* p = static_cast<char*>(base);
-    size_t used = 0;
-    auto take = [&](size_t bytes) { char* r = p ? p + used : nullptr; used += (bytes + 255) & ~size_t(255); return r; };
+    Carver c(base);
     o.part_bytes = R * (size_t)acc_record_floats(coord) * sizeof(float);
     o.sort_bytes = sort_temp_bytes(R);
-    o.part = reinterpret_cast<float*>(take(o.part_bytes));
-    o.keys = reinterpret_cast<uint32_t*>(take(R * sizeof(uint32_t)));
-    o.pos = reinterpret_cast<uint32_t*>(take(R * sizeof(uint32_t)));
-    o.sort_temp = take(o.sort_bytes);
-    o.total = used;
+    o.part = c.take<float>(R * (size_t)acc_record_floats(coord));
+    o.keys = c.take<uint32_t>(R);
+    o.pos = c.take<uint32_t>(R);
+    o.sort_temp = c.take<char>(o.sort_bytes);
+    o.total = c.off;
     return o;
   }
 };

@@ -23,23 +23,13 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "rg_workspace.h"
+
 namespace rg {
 
-constexpr size_t kAlign = 256;
-inline size_t align_up(size_t v) { return (v + kAlign - 1) & ~(kAlign - 1); }
-
-struct Carver {
-  char* base;
-  size_t off;
-  explicit Carver(void* b) : base(static_cast<char*>(b)), off(0) {}
-  template <class T> T* take(size_t count) {
-    off = align_up(off);
-    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-    off += count * sizeof(T);
-    return p;
-  }
-  size_t total() const { return align_up(off) + kAlign; }
-};
+// The four states below are laid out with rg_workspace.h's Carver (every array starts on a 256-byte boundary of its buffer) and end in
+// kTailPad bytes of padding after the last array: radegs_debug_export and _C.debug_export("blk_chunks") count on them.
+constexpr size_t kTailPad = 256;
 
 struct GeomState {
   float* splat_a;          // [P*16]
@@ -74,7 +64,7 @@ struct GeomState {
     g.tile_sq_sum = c.take<unsigned long long>(2);
     g.temp = c.take<char>(temp_bytes);
     g.temp_bytes = temp_bytes;
-    g.total = c.total();
+    g.total = c.off + kTailPad;
     return g;
   }
 };
@@ -96,7 +86,7 @@ struct BinState {
     b.point_list_unsorted = c.take<uint32_t>(R);
     b.temp = c.take<char>(temp_bytes);
     b.temp_bytes = temp_bytes;
-    b.total = c.total();
+    b.total = c.off + kTailPad;
     return b;
   }
 };
@@ -152,7 +142,7 @@ struct ImageState {
     s.blk_order = c.take<uint32_t>(kBlocksPerTile * tiles);
     s.stream_tag = c.take<uint32_t>(4);
     s.blk_chunks = c.take<uint32_t>(stream_chunks * kChunkWords);
-    s.total = c.total();
+    s.total = c.off + kTailPad;
     return s;
   }
 };
@@ -185,7 +175,7 @@ struct PointState {
     s.final_T = c.take<float>(HW);
     s.temp = c.take<char>(temp_bytes);
     s.temp_bytes = temp_bytes;
-    s.total = c.total();
+    s.total = c.off + kTailPad;
     return s;
   }
 };

@@ -109,6 +109,7 @@ __global__ void __launch_bounds__(kListThreads) block_counts_kernel(const BlockL
 // Needs the blocks' counts only (block_counts_kernel), not the lists: since round 6 it runs in the FIRST workgroups of block_lists_kernel,
 // next to the list building, instead of as a kernel of its own behind it (7.7 us + a kernel boundary per stream forward).
 constexpr int kBalanceBlocks = 512;
+static_assert(kListThreads == 256, "balance_blocks: one compare-exchange per thread per step over 512 keys, and strides of 256");
 __device__ __forceinline__ void balance_blocks(int group, int nblocks, const uint32_t* __restrict__ blk_count, uint32_t* __restrict__ blk_order,
                                                uint64_t* keys /* LDS [kBalanceBlocks] */) {
   const int tid = threadIdx.x;

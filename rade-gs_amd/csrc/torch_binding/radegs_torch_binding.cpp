@@ -101,21 +101,41 @@ struct StateBuffer {
 
 void* current_stream(const c10::Device& d) { return static_cast<void*>(c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(d.index()).stream()); }
 
-int checked(int rc, const char* what) {
-  TORCH_CHECK(rc >= 0, what, " failed (", rc, "): ", radegs_last_error());
-  return rc;
-}
-
 // The accumulation scratch of the backward: one all-zero buffer per (device, stream), handed back all-zero by every successful
 // call (RadegsBwdArgs.acc_reuse) -- up to 256 MB; larger ones are allocated per call and filled by the library.
 constexpr size_t kAccReuseMaxBytes = size_t(256) << 20;
-// The mutex is held for the whole of a backward that uses a cached scratch: two host threads queueing backwards on ONE stream would
-// otherwise interleave their kernels over the same buffer (each call's kernels must run back to back: the second one clears what the first
-// accumulated).  The map is leaked on purpose: tensors destroyed during static destruction would outlive the HIP context.
-std::mutex g_acc_mutex;
-std::map<std::pair<int, void*>, Tensor>& acc_scratch_map() {
-  static auto* m = new std::map<std::pair<int, void*>, Tensor>();
-  return *m;
+// The cache owns its mutex and its map; nothing touches the map without the mutex.  A lease holds the mutex for the whole of a backward
+// that uses a cached scratch: two host threads queueing backwards on ONE stream would otherwise interleave their kernels over the same
+// buffer (each call's kernels must run back to back: the second one clears what the first accumulated).  The map is leaked on purpose:
+// tensors destroyed during static destruction would outlive the HIP context.
+struct AccCache {
+  using Key = std::pair<int, void*>;
+  std::mutex mutex;
+  std::map<Key, Tensor>* map = new std::map<Key, Tensor>();
+  // locks, and hands out the all-zero buffer of `key` grown to `nbytes` (at most 8 are kept); the caller keeps the lock until the native
+  // call has returned
+  std::unique_lock<std::mutex> lease(const Key& key, size_t nbytes, const c10::Device& dev, Tensor& out) {
+    std::unique_lock<std::mutex> lock(mutex);
+    auto it = map->find(key);
+    if (it == map->end() || static_cast<size_t>(it->second.numel()) < nbytes) {
+      if (map->size() >= 8) map->clear();
+      (*map)[key] = torch::zeros({static_cast<int64_t>(nbytes ? nbytes : 1)}, torch::TensorOptions().dtype(torch::kUInt8).device(dev));
+      it = map->find(key);
+    }
+    out = it->second;
+    return lock;
+  }
+  void drop(const Key& key) { map->erase(key); }   // under a lease: the call failed, the buffer's state is unknown
+  void clear() { std::lock_guard<std::mutex> lock(mutex); map->clear(); }
+};
+AccCache g_acc;
+
+// Whatever failed, the cached scratches are no longer known to be zero (RADEGS_ERR_STATE in particular is reported one call late: the
+// backward it belongs to has poisoned its scratch with NaN): the next backward starts from a fresh one, as in _C._check.
+int checked(int rc, const char* what) {
+  if (rc < 0) g_acc.clear();
+  TORCH_CHECK(rc >= 0, what, " failed (", rc, "): ", radegs_last_error());
+  return rc;
 }
 
 struct AccRequest { Tensor t; bool failed = false; };
@@ -201,22 +221,12 @@ rasterize_gaussians_backward(const Tensor& background, const Tensor& means3D, co
     const Tensor rad = radii.contiguous(), gb = geomBuffer.contiguous(), bb = binningBuffer.contiguous(), ib = imageBuffer.contiguous();
     void* stream = current_stream(dev);
     const size_t abytes = static_cast<size_t>(P) * (require_coord ? 128 : 64);
-    const std::pair<int, void*> key(dev.index(), stream);
+    const AccCache::Key key(dev.index(), stream);
     const bool reuse = abytes <= kAccReuseMaxBytes;
     AccRequest acc;
     StateBuffer acc_fresh(dev, false);
-    std::unique_lock<std::mutex> scratch_lock(g_acc_mutex, std::defer_lock);
-    if (reuse) {
-      scratch_lock.lock();
-      auto& cache = acc_scratch_map();
-      auto it = cache.find(key);
-      if (it == cache.end() || static_cast<size_t>(it->second.numel()) < abytes) {
-        if (cache.size() >= 8) cache.clear();
-        cache[key] = torch::zeros({static_cast<int64_t>(abytes ? abytes : 1)}, torch::TensorOptions().dtype(torch::kUInt8).device(dev));
-        it = cache.find(key);
-      }
-      acc.t = it->second;
-    }
+    std::unique_lock<std::mutex> scratch_lock;
+    if (reuse) scratch_lock = g_acc.lease(key, abytes, dev, acc.t);
     RadegsBwdArgs a{};
     a.struct_size = sizeof(RadegsBwdArgs);
     a.P = P; a.D = degree; a.M = M; a.R = R; a.width = W; a.height = H;
@@ -234,7 +244,7 @@ rasterize_gaussians_backward(const Tensor& background, const Tensor& means3D, co
     a.require_coord = require_coord ? 1 : 0; a.require_depth = require_depth ? 1 : 0; a.debug = debug ? 1 : 0;
     a.acc_reuse = reuse ? 1 : 0;
     const int rc = reuse ? radegs_backward(&a, acc_fixed, &acc, stream) : radegs_backward(&a, StateBuffer::grow, &acc_fresh, stream);
-    if (reuse && (rc != 0 || acc.failed)) acc_scratch_map().erase(key);   // unknown state: the next call starts from a fresh one
+    if (reuse && (rc != 0 || acc.failed)) g_acc.drop(key);   // unknown state: the next call starts from a fresh one
     if (reuse) scratch_lock.unlock();
     checked(rc, "radegs_backward");
     if (!sc.p) {   // precomputed covariance: scale / rotation gradients are identically zero

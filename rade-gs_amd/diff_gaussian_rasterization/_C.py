@@ -12,6 +12,7 @@ HIP stream only; no torch type crosses the C boundary.
 
 There is NO CPU path and no fallback: a missing library or a non-GPU tensor raises.
 """
+import contextlib
 import ctypes
 import os
 import threading
@@ -76,6 +77,9 @@ class RadegsIntegrateArgs(ctypes.Structure):
                 ("out_color", ctypes.c_void_p), ("out_alpha_integrated", ctypes.c_void_p), ("out_color_integrated", ctypes.c_void_p),
                 ("out_coordinate2d", ctypes.c_void_p), ("out_sdf", ctypes.c_void_p), ("radii", ctypes.c_void_p)]
 
+
+for _s in (RadegsFwdArgs, RadegsBwdArgs, RadegsIntegrateArgs):
+    _s._names = frozenset(name for name, _ in _s._fields_)
 
 # every symbol include/radegs.h declares
 EXPORTED_SYMBOLS = ("radegs_forward", "radegs_backward", "radegs_backward_ordered", "radegs_backward_ordered_scratch_bytes", "radegs_backward_from_sums", "radegs_mark_visible", "radegs_integrate", "radegs_sh_grad_from_views", "radegs_geometry_bytes", "radegs_image_bytes",
@@ -189,87 +193,83 @@ def _c_hook(fn_type, fn, errors):
     return fn_type(_call)
 
 
-def _bwd_args(**fields):
-    """RadegsBwdArgs from keyword fields (struct_size filled in; a field not named is 0 / NULL).  A tensor stands for its device pointer,
-    None for NULL, a hook made by _c_hook for its C address."""
-    unknown = set(fields) - {name for name, _ in RadegsBwdArgs._fields_}
+def _args(struct, **fields):
+    """An argument structure from keyword fields (struct_size filled in where there is one; a field not named is 0 / NULL).  A tensor stands
+    for its device pointer, None for NULL, a hook made by _c_hook for its C address.  The structure keeps the values alive."""
+    unknown = fields.keys() - struct._names
     if unknown:
-        raise TypeError(f"RadegsBwdArgs has no field {sorted(unknown)}")
-    a = RadegsBwdArgs(struct_size=ctypes.sizeof(RadegsBwdArgs))
-    for name, v in fields.items():
-        if isinstance(v, torch.Tensor):
-            v = _ptr(v)
-        elif isinstance(v, (_READY_FN, _GRADS_READY_FN)):
-            v = ctypes.cast(v, ctypes.c_void_p)
-        setattr(a, name, v)
+        raise TypeError(f"{struct.__name__} has no field {sorted(unknown)}")
+    values = {name: v.data_ptr() if isinstance(v, torch.Tensor) else ctypes.cast(v, ctypes.c_void_p) if isinstance(v, ctypes._CFuncPtr) else v
+              for name, v in fields.items()}
+    if "struct_size" in struct._names:
+        values["struct_size"] = ctypes.sizeof(struct)
+    a = struct(**values)
+    a.keep = fields
     return a
 
 
-def library():
-    """Load libradegs_hip.so (built in-tree by rade-gs_amd/build.py).  Fails loudly."""
+_I, _SZ, _VP, _ULL = ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p, ctypes.POINTER(ctypes.c_ulonglong)
+# the rasterizer's own entry points: {name: (restype, [argtypes])}.  Every other module keeps such a table for the symbols it calls and hands
+# it to bind(); together the tables cover EXPORTED_SYMBOLS (tests/test_signatures.py), so no function is ever called with ctypes' defaults
+_SIGNATURES = {
+    "radegs_forward": (_I, [ctypes.POINTER(RadegsFwdArgs)] + [_ALLOC_FN, _VP] * 3 + [_VP]),
+    "radegs_backward": (_I, [ctypes.POINTER(RadegsBwdArgs), _ALLOC_FN, _VP, _VP]),
+    "radegs_backward_ordered": (_I, [ctypes.POINTER(RadegsBwdArgs), _ALLOC_FN, _VP, _VP, _SZ, _VP]),
+    "radegs_backward_ordered_scratch_bytes": (_SZ, [_I, _I, _I]),
+    "radegs_backward_from_sums": (_I, [ctypes.POINTER(RadegsBwdArgs), _VP, _VP]),
+    "radegs_integrate": (_I, [ctypes.POINTER(RadegsIntegrateArgs)] + [_ALLOC_FN, _VP] * 4 + [_VP]),
+    "radegs_sh_grad_from_views": (_I, [_I] * 4 + [_VP] * 3 + [ctypes.c_float, _VP, _VP]),
+    "radegs_mark_visible": (_I, [_I] + [_VP] * 5),
+    "radegs_geometry_bytes": (_SZ, [_I, _I]),
+    "radegs_image_bytes": (_SZ, [_I, _I]),
+    "radegs_binning_bytes": (_SZ, [_I]),
+    "radegs_debug_export": (ctypes.c_longlong, [ctypes.c_char_p] + [_I] * 5 + [_VP] * 4 + [_SZ, _VP]),
+    "radegs_forget_image": (None, [_VP]),
+    "radegs_last_error": (ctypes.c_char_p, []),
+    "radegs_version": (ctypes.c_char_p, []),
+    "radegs_binning_stats": (None, [_ULL, _ULL, _I]),
+    "radegs_reload_env": (None, []),
+    "radegs_last_forward_used_streams": (_I, []),
+    "radegs_profile_enable": (None, [_I]),
+    "radegs_profile_select": (None, [_I]),
+    "radegs_profile_stride": (None, [_I]),
+    "radegs_profile_num_stages": (_I, []),
+    "radegs_profile_stage_name": (ctypes.c_char_p, [_I]),
+    "radegs_profile_collect": (_I, [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(_I), _I]),
+}
+_bound = set()   # id() of the tables (module-level dicts, never freed) already set on the library
+_BIND_LOCK = threading.Lock()
+
+
+def bind(signatures):
+    """Loads libradegs_hip.so (built in-tree by rade-gs_amd/build.py; fails loudly) on first use, sets the module's table
+    {"radegs_x": (restype, [argtypes...]), ...} on it, once, and returns the library."""
     global _lib
-    if _lib is None:
-        if not os.path.exists(_LIB_PATH):
-            raise RuntimeError(f"{_LIB_PATH} is missing: build it with `python rade-gs_amd/build.py` "
-                               "(there is no CPU or PyTorch fallback for this operator)")
-        L = ctypes.CDLL(_LIB_PATH)
-        L.radegs_forward.restype = ctypes.c_int
-        L.radegs_forward.argtypes = [ctypes.POINTER(RadegsFwdArgs), _ALLOC_FN, ctypes.c_void_p, _ALLOC_FN, ctypes.c_void_p, _ALLOC_FN,
-                                     ctypes.c_void_p, ctypes.c_void_p]
-        L.radegs_backward.restype = ctypes.c_int
-        L.radegs_backward.argtypes = [ctypes.POINTER(RadegsBwdArgs), _ALLOC_FN, ctypes.c_void_p, ctypes.c_void_p]
-        L.radegs_backward_ordered.restype = ctypes.c_int
-        L.radegs_backward_ordered.argtypes = [ctypes.POINTER(RadegsBwdArgs), _ALLOC_FN, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-                                              ctypes.c_void_p]
-        L.radegs_backward_ordered_scratch_bytes.restype = ctypes.c_size_t
-        L.radegs_backward_ordered_scratch_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-        L.radegs_backward_from_sums.restype = ctypes.c_int
-        L.radegs_backward_from_sums.argtypes = [ctypes.POINTER(RadegsBwdArgs), ctypes.c_void_p, ctypes.c_void_p]
-        L.radegs_integrate.restype = ctypes.c_int
-        L.radegs_integrate.argtypes = [ctypes.POINTER(RadegsIntegrateArgs)] + [_ALLOC_FN, ctypes.c_void_p] * 4 + [ctypes.c_void_p]
-        L.radegs_sh_grad_from_views.restype = ctypes.c_int
-        L.radegs_sh_grad_from_views.argtypes = [ctypes.c_int] * 4 + [ctypes.c_void_p] * 3 + [ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]
-        L.radegs_mark_visible.restype = ctypes.c_int
-        L.radegs_mark_visible.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        L.radegs_geometry_bytes.restype = ctypes.c_size_t
-        L.radegs_geometry_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
-        L.radegs_image_bytes.restype = ctypes.c_size_t
-        L.radegs_image_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
-        L.radegs_binning_bytes.restype = ctypes.c_size_t
-        L.radegs_binning_bytes.argtypes = [ctypes.c_int]
-        L.radegs_debug_export.restype = ctypes.c_longlong
-        L.radegs_debug_export.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        L.radegs_forget_image.restype = None
-        L.radegs_forget_image.argtypes = [ctypes.c_void_p]
-        L.radegs_last_error.restype = ctypes.c_char_p
-        L.radegs_version.restype = ctypes.c_char_p
-        L.radegs_binning_stats.restype = None
-        L.radegs_binning_stats.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_int]
-        L.radegs_reload_env.restype = None
-        L.radegs_reload_env.argtypes = []
-        L.radegs_last_forward_used_streams.restype = ctypes.c_int
-        L.radegs_last_forward_used_streams.argtypes = []
-        L.radegs_profile_enable.restype = None
-        L.radegs_profile_enable.argtypes = [ctypes.c_int]
-        L.radegs_profile_select.restype = None
-        L.radegs_profile_select.argtypes = [ctypes.c_int]
-        L.radegs_profile_stride.restype = None
-        L.radegs_profile_stride.argtypes = [ctypes.c_int]
-        L.radegs_profile_num_stages.restype = ctypes.c_int
-        L.radegs_profile_stage_name.restype = ctypes.c_char_p
-        L.radegs_profile_stage_name.argtypes = [ctypes.c_int]
-        L.radegs_profile_collect.restype = ctypes.c_int
-        L.radegs_profile_collect.argtypes = [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int), ctypes.c_int]
-        _lib = L
+    if id(signatures) not in _bound:
+        with _BIND_LOCK:
+            if _lib is None:
+                if not os.path.exists(_LIB_PATH):
+                    raise RuntimeError(f"{_LIB_PATH} is missing: build it with `python rade-gs_amd/build.py` "
+                                       "(there is no CPU or PyTorch fallback for this operator)")
+                _lib = ctypes.CDLL(_LIB_PATH)
+            for name, (restype, argtypes) in signatures.items():
+                fn = getattr(_lib, name)
+                fn.restype, fn.argtypes = restype, argtypes
+            _bound.add(id(signatures))
     return _lib
+
+
+def library():
+    """libradegs_hip.so with the rasterizer's entry points bound."""
+    return bind(_SIGNATURES)
 
 
 def _check(rc, what):
     if rc < 0:
-        # whatever failed, the cached accumulation scratches are no longer known to be zero (RADEGS_ERR_STATE in particular is reported
-        # one call late: the backward it belongs to has poisoned its scratch with NaN): the next backward starts from a fresh one
+        # whatever failed, the cached scratches are no longer known to be zero (RADEGS_ERR_STATE in particular is reported one call late: the
+        # backward it belongs to has poisoned its scratch with NaN): the next backward starts from a fresh one
         _ACC_SCRATCH.clear()
+        _ORDERED_SCRATCH.clear()
         raise RuntimeError(f"{what} failed ({rc}): {library().radegs_last_error().decode()}")
     return rc
 
@@ -370,55 +370,52 @@ class _Fixed:
         self.cb = None
 
 
-_ACC_SCRATCH = {}   # (device index, stream handle) -> all-zero uint8 tensor, kept zero by the backward itself (RadegsBwdArgs.acc_reuse)
 # held for the whole of a backward that uses a cached scratch: ctypes drops the GIL during the native call, and two host threads queueing
-# backwards on ONE stream would otherwise interleave their kernels over the same buffer
-_ACC_LOCK = threading.Lock()
+# backwards on ONE stream would otherwise interleave their kernels over the same buffer.  Re-entrant, because an exchange hook runs on the
+# calling thread inside the native call, and a call of this module that fails there clears the caches (_check).
+_SCRATCH_LOCK = threading.RLock()
 
 
-def _acc_scratch(key, nbytes, device):
-    """The zeroed accumulation scratch of this (device, stream), grown (and zeroed again) when a call needs more; at most 8 are kept."""
-    t = _ACC_SCRATCH.get(key)
-    if t is None or t.numel() < nbytes:
-        if len(_ACC_SCRATCH) >= 8:
-            _ACC_SCRATCH.clear()
-        t = torch.zeros(max(int(nbytes), 1), dtype=torch.uint8, device=device)
-        _ACC_SCRATCH[key] = t
-    return t
+class _ScratchCache:
+    """uint8 scratch buffers of the backward, one per key = (device index, stream handle), at most 8; every access is made under
+    _SCRATCH_LOCK.  zeroed=True: a buffer is all zeros when it is made and the backward hands it back so (RadegsBwdArgs.acc_reuse);
+    zeroed=False: the contents are irrelevant between calls."""
+
+    def __init__(self, zeroed):
+        self._alloc = torch.zeros if zeroed else torch.empty
+        self._buffers = {}
+
+    @contextlib.contextmanager
+    def lease(self, key, nbytes, device):
+        """Takes the lock and yields the buffer of `key`, grown to `nbytes`; the lock is held until the block ends."""
+        with _SCRATCH_LOCK:
+            t = self._buffers.get(key)
+            if t is None or t.numel() < nbytes:
+                if t is None and len(self._buffers) >= 8:
+                    self._buffers.clear()
+                del t
+                self._buffers.pop(key, None)    # let go of the smaller one before its replacement is allocated
+                t = self._buffers[key] = self._alloc(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+            yield t
+
+    def drop(self, key):
+        """Inside a lease whose call failed: the buffer is in an unknown state, the next call starts from a fresh one."""
+        self._buffers.pop(key, None)
+
+    def clear(self):
+        with _SCRATCH_LOCK:
+            self._buffers.clear()
+
+    def values(self):
+        with _SCRATCH_LOCK:
+            return list(self._buffers.values())
+
+    def __len__(self):
+        return len(self.values())
 
 
-_ORDERED_SCRATCH = {}   # (device index, stream handle) -> uint8 tensor of the ordered backward (partial records, sorted positions); only grows
-
-
-def _ordered_scratch(key, nbytes, device):
-    """The ordered backward's scratch of this (device, stream): contents irrelevant between calls, grown when a call needs more; at most 8."""
-    t = _ORDERED_SCRATCH.get(key)
-    if t is None or t.numel() < nbytes:
-        if t is None and len(_ORDERED_SCRATCH) >= 8:
-            _ORDERED_SCRATCH.clear()
-        del t
-        _ORDERED_SCRATCH.pop(key, None)    # let go of the smaller one before its replacement is allocated
-        t = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
-        _ORDERED_SCRATCH[key] = t
-    return t
-
-
-def _backward_ordered(L, a, acc, P, R, require_coord, dev, akey):
-    """radegs_backward_ordered over the prepared arguments `a` and the accumulator holder `acc` (acc_reuse = 0: a fresh accumulator per call,
-    every record of it written by the call); returns rc."""
-    global LAST_PARTIALS
-    assert a.acc_reuse == 0
-    nbytes = int(L.radegs_backward_ordered_scratch_bytes(P, int(R), int(bool(require_coord))))
-    with _ACC_LOCK:    # one scratch per (device, stream): two host threads queueing on ONE stream must not interleave over it
-        scratch = _ordered_scratch(akey, nbytes, dev) if R > 0 else None
-        with torch.cuda.device(dev):
-            rc = L.radegs_backward_ordered(ctypes.byref(a), acc.cb, None, _ptr(scratch), nbytes if scratch is not None else 0, _stream(dev))
-        acc.release()
-        if KEEP_ACC and rc == 0 and acc.error is None:
-            rec = 32 if require_coord else 16
-            part = torch.empty((0, rec), dtype=torch.float32, device=dev) if scratch is None else scratch[:int(R) * rec * 4].view(torch.float32).view(int(R), rec).clone()
-            LAST_PARTIALS = (part, int(R))
-    return rc
+_ACC_SCRATCH = _ScratchCache(zeroed=True)        # the per-Gaussian accumulators, all zeros between calls
+_ORDERED_SCRATCH = _ScratchCache(zeroed=False)   # the ordered backward's partial records and sorted positions
 
 
 def _zero_maps(channels, H, W, device):
@@ -444,6 +441,18 @@ def _zero_maps(channels, H, W, device):
 
 def _stream(device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _gaussian_fields(means3D, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, kernel_size,
+                     sh, degree, campos):
+    """The fields RadegsFwdArgs, RadegsBwdArgs and RadegsIntegrateArgs share: the Gaussians and the camera as contiguous float32 tensors
+    (None: not provided), P, D, M and the four scalars."""
+    shs = _f32(sh, "shs")
+    return dict(P=int(means3D.size(0)), D=int(degree), M=int(sh.size(1)) if shs is not None else 0, means3D=_f32(means3D, "means3D"), shs=shs,
+                colors_precomp=_f32(colors, "colors_precomp"), scales=_f32(scales, "scales"), rotations=_f32(rotations, "rotations"),
+                cov3D_precomp=_f32(cov3D_precomp, "cov3D_precomp"), viewmatrix=_f32(viewmatrix, "viewmatrix"),
+                projmatrix=_f32(projmatrix, "projmatrix"), cam_pos=_f32(campos, "campos"), scale_modifier=float(scale_modifier),
+                tan_fovx=float(tan_fovx), tan_fovy=float(tan_fovy), kernel_size=float(kernel_size))
 
 
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
@@ -478,16 +487,12 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
     geom, binning, img = _Resizable(dev), _Resizable(dev), _Resizable(dev, image=True)
     rendered = 0
     if live:
-        bg, m3 = _f32(background, "bg"), _f32(means3D, "means3D")
-        col, op = _f32(colors, "colors_precomp"), _f32(opacity, "opacities")
-        sc, rot, cov = _f32(scales, "scales"), _f32(rotations, "rotations"), _f32(cov3D_precomp, "cov3D_precomp")
-        vm, pm, cp, shs = _f32(viewmatrix, "viewmatrix"), _f32(projmatrix, "projmatrix"), _f32(campos, "campos"), _f32(sh, "shs")
-        M = int(sh.size(1)) if (sh is not None and sh.numel() != 0) else 0
-        a = RadegsFwdArgs(P, int(degree), M, W, H, _ptr(bg), _ptr(m3), _ptr(shs), _ptr(col), _ptr(op), _ptr(sc), _ptr(rot), _ptr(cov),
-                          _ptr(vm), _ptr(pm), _ptr(cp), float(scale_modifier), float(tan_fovx), float(tan_fovy), float(kernel_size),
-                          int(bool(prefiltered)), int(require_coord), int(require_depth), int(bool(debug)),
-                          _ptr(out_color), _ptr(out_coord), _ptr(out_mcoord), _ptr(out_depth), _ptr(out_mdepth), _ptr(out_alpha),
-                          _ptr(out_normal), _ptr(radii))
+        a = _args(RadegsFwdArgs, width=W, height=H, background=_f32(background, "bg"), opacities=_f32(opacity, "opacities"),
+                  prefiltered=int(bool(prefiltered)), require_coord=int(require_coord), require_depth=int(require_depth), debug=int(bool(debug)),
+                  out_color=out_color, out_coord=out_coord, out_mcoord=out_mcoord, out_depth=out_depth, out_mdepth=out_mdepth,
+                  out_alpha=out_alpha, out_normal=out_normal, radii=radii,
+                  **_gaussian_fields(means3D, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx,
+                                     tan_fovy, kernel_size, sh, degree, campos))
         with torch.cuda.device(dev):
             rc = L.radegs_forward(ctypes.byref(a), geom.cb, None, binning.cb, None, img.cb, None, _stream(dev))
         for r in (geom, binning, img):
@@ -499,111 +504,129 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
             binning.tensor, img.tensor)
 
 
-def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
-                                 projmatrix, tan_fovx, tan_fovy, kernel_size, dL_dout_color, dL_dout_coord, dL_dout_mcoord,
-                                 dL_dout_depth, dL_dout_mdepth, dL_dout_alpha, dL_dout_normal, normalmap, sh, degree, campos,
-                                 geomBuffer, R, binningBuffer, imageBuffer, alphas, require_coord, require_depth, debug):
-    _require_gpu(means3D, "means3D")
-    L = library()
-    dev = means3D.device
-    P = int(means3D.size(0))
-    H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
-    M = int(sh.size(1)) if (sh is not None and sh.numel() != 0) else 0
+def _alloc_grads(grad_alloc, P, M, dev):
+    """The eight gradients of the backward in its return order, then dL_drgb_clamped (None unless the allocator supplies it).  Each comes
+    from the device's allocator hook where that returns a tensor; dL_dsh is None where the hook answered SKIP_GRAD (see SKIP_GRAD)."""
     fo = dict(dtype=torch.float32, device=dev)
 
-    grad_alloc = _grad_allocator_for(dev)
+    def hooked(name, shape):
+        t = grad_alloc(name, shape, torch.float32, dev)
+        if t is not None:
+            assert t.shape == torch.Size(shape) and t.is_contiguous() and t.dtype == torch.float32 and t.device == dev
+        return t
 
     def mk(name, shape):
-        if P != 0 and grad_alloc is not None:
-            t = grad_alloc(name, shape, torch.float32, dev)
-            if t is not None:
-                assert t.shape == torch.Size(shape) and t.is_contiguous() and t.dtype == torch.float32 and t.device == dev
-                return t
+        t = hooked(name, shape) if P != 0 and grad_alloc is not None else None
+        if t is not None:
+            return t
         if P != 0 and _POISON:
             return torch.full(shape, float("nan"), **fo)
         return torch.empty(shape, **fo) if P != 0 else torch.zeros(shape, **fo)
 
     dL_dmeans3D, dL_dmeans2D, dL_dcolors = mk("dL_dmeans3D", (P, 3)), mk("dL_dmeans2D", (P, 3)), mk("dL_dcolors", (P, 3))
     dL_dopacity, dL_dcov3D = mk("dL_dopacity", (P, 1)), mk("dL_dcov3D", (P, 6))
-    drgb = None
-    skip_dsh = False
-    if P != 0 and M != 0 and grad_alloc is not None:
-        drgb = grad_alloc("dL_drgb_clamped", (P, 3), torch.float32, dev)
-        skip_dsh = drgb is not None and grad_alloc("dL_dsh", (P, M, 3), torch.float32, dev) is SKIP_GRAD
-        if drgb is not None:
-            assert drgb.shape == torch.Size((P, 3)) and drgb.is_contiguous() and drgb.dtype == torch.float32 and drgb.device == dev
+    drgb = hooked("dL_drgb_clamped", (P, 3)) if P != 0 and M != 0 and grad_alloc is not None else None
+    skip_dsh = drgb is not None and grad_alloc("dL_dsh", (P, M, 3), torch.float32, dev) is SKIP_GRAD
     dL_dsh = None if skip_dsh else mk("dL_dsh", (P, M, 3))
     dL_dscales, dL_drotations = mk("dL_dscales", (P, 3)), mk("dL_drotations", (P, 4))
-    if P != 0:
-        bg, m3, col = _f32(background, "bg"), _f32(means3D, "means3D"), _f32(colors, "colors_precomp")
-        sc, rot, cov = _f32(scales, "scales"), _f32(rotations, "rotations"), _f32(cov3D_precomp, "cov3D_precomp")
-        vm, pm, cp, shs = _f32(viewmatrix, "viewmatrix"), _f32(projmatrix, "projmatrix"), _f32(campos, "campos"), _f32(sh, "shs")
-        g = [_f32(t, n) for t, n in ((dL_dout_color, "dL_dcolor"), (dL_dout_coord, "dL_dcoord"), (dL_dout_mcoord, "dL_dmcoord"),
-                                     (dL_dout_depth, "dL_ddepth"), (dL_dout_mdepth, "dL_dmdepth"), (dL_dout_alpha, "dL_dalpha"),
-                                     (dL_dout_normal, "dL_dnormal"))]
-        al, nm = _f32(alphas, "alphas"), _f32(normalmap, "normalmap")
-        rad = radii.contiguous()
-        gb, bb, ib = geomBuffer.contiguous(), binningBuffer.contiguous(), imageBuffer.contiguous()
-        if not sc is None and rot is None:
-            raise RuntimeError("scales given without rotations")
-        # the accumulation scratch: ONE buffer per (device, stream), zeroed once and handed back zeroed by every successful call
-        # (RadegsBwdArgs.acc_reuse) -- unless its contents are wanted afterwards (KEEP_ACC), which takes a scratch of its own
-        abytes = P * (128 if require_coord else 64)
-        akey = (dev.index if dev.index is not None else torch.cuda.current_device(), int(torch.cuda.current_stream(dev).cuda_stream))
+    return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, drgb
+
+
+def _exchange_hooks(grad_alloc, drgb, errors):
+    """{drgb_ready, grads_ready, grad_chunks} of RadegsBwdArgs from the object the allocator is a bound method of: `drgb_ready()` is called
+    on the host as soon as the kernel that writes dL_drgb_clamped is queued, `grads_ready(first, count)` after each of `grad_chunks`
+    launches of the per-Gaussian backward, so that the owner's exchange of those rows runs under the launches that follow."""
+    owner = getattr(grad_alloc, "__self__", None)
+    hooks = {}
+    if owner is not None and drgb is not None and callable(getattr(owner, "drgb_ready", None)) and getattr(owner, "early_drgb", False):
+        hooks["drgb_ready"] = _c_hook(_READY_FN, owner.drgb_ready, errors)
+    if owner is not None and callable(getattr(owner, "grads_ready", None)) and int(getattr(owner, "grad_chunks", 0) or 0) > 1 \
+            and getattr(owner, "early_grads", False):
+        hooks["grad_chunks"] = int(owner.grad_chunks)
+        hooks["grads_ready"] = _c_hook(_GRADS_READY_FN, owner.grads_ready, errors)
+    return hooks
+
+
+def _run_backward(L, a, dev, ordered, hook_errors):
+    """radegs_backward, or radegs_backward_ordered, over the prepared arguments `a`; returns (rc, the accumulator's holder).  The accumulator
+    is ONE all-zero buffer per (device, stream), handed back all-zero by every successful call (RadegsBwdArgs.acc_reuse) -- unless its
+    contents are wanted afterwards (KEEP_ACC, _POISON, the ordered backward: every record written by the call) or it is too large: then the
+    call gets a fresh one.  The ordered backward's scratch is cached in the same way.  A failed call drops what it leased."""
+    global LAST_PARTIALS
+    coord = bool(a.require_coord)
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), int(torch.cuda.current_stream(dev).cuda_stream))
+    if ordered:
+        cache, nbytes = _ORDERED_SCRATCH, int(L.radegs_backward_ordered_scratch_bytes(a.P, a.R, int(coord)))
+        cached = a.R > 0
+    else:
         # (above ACC_REUSE_MAX_BYTES the clearing stores cost the per-Gaussian kernel more than the fill they replace: C4, 5 M Gaussians with
         # the coord map = 640 MB, same-box A/B: preprocess_bwd +0.13 ms against a 0.08-ms fill)
+        cache, nbytes = _ACC_SCRATCH, a.P * (128 if coord else 64)
+        cached = not (KEEP_ACC or _POISON or not ACC_REUSE or nbytes > ACC_REUSE_MAX_BYTES)
+    with cache.lease(key, nbytes, dev) if cached else contextlib.nullcontext() as buf:
+        a.acc_reuse = int(cached and not ordered)
+        acc = _Fixed(buf) if a.acc_reuse else _Resizable(dev)
+        with torch.cuda.device(dev):
+            if ordered:
+                rc = L.radegs_backward_ordered(ctypes.byref(a), acc.cb, None, _ptr(buf), nbytes if cached else 0, _stream(dev))
+            else:
+                rc = L.radegs_backward(ctypes.byref(a), acc.cb, None, _stream(dev))
+        acc.release()
+        ok = rc == 0 and acc.error is None and not hook_errors
+        if cached and not ok:
+            cache.drop(key)
+        if ordered and KEEP_ACC and ok:
+            rec = 32 if coord else 16
+            part = torch.empty((0, rec), dtype=torch.float32, device=dev) if buf is None else buf[:a.R * rec * 4].view(torch.float32).view(a.R, rec).clone()
+            LAST_PARTIALS = (part, a.R)
+    return rc, acc
+
+
+def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
+                                 projmatrix, tan_fovx, tan_fovy, kernel_size, dL_dout_color, dL_dout_coord, dL_dout_mcoord,
+                                 dL_dout_depth, dL_dout_mdepth, dL_dout_alpha, dL_dout_normal, normalmap, sh, degree, campos,
+                                 geomBuffer, R, binningBuffer, imageBuffer, alphas, require_coord, require_depth, debug):
+    global LAST_ACC
+    _require_gpu(means3D, "means3D")
+    L = library()
+    dev = means3D.device
+    P = int(means3D.size(0))
+    M = int(sh.size(1)) if (sh is not None and sh.numel() != 0) else 0
+    grad_alloc = _grad_allocator_for(dev)
+    *grads, drgb = _alloc_grads(grad_alloc, P, M, dev)
+    dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations = grads
+    if P != 0:
+        g = _gaussian_fields(means3D, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
+                             kernel_size, sh, degree, campos)
+        if g["scales"] is not None and g["rotations"] is None:
+            raise RuntimeError("scales given without rotations")
+        gb, bb, ib = geomBuffer.contiguous(), binningBuffer.contiguous(), imageBuffer.contiguous()
+        hook_errors = []
         ordered = DETERMINISTIC     # read once: another thread may flip the switch while this call runs
-        acc_cached = None if (ordered or KEEP_ACC or _POISON or not ACC_REUSE or abytes > ACC_REUSE_MAX_BYTES) else _acc_scratch(akey, abytes, dev)
-        acc = _Resizable(dev) if acc_cached is None else _Fixed(acc_cached)
-        ready_cb, ready_err = None, []
-        owner = getattr(grad_alloc, "__self__", None)
-        if drgb is not None and owner is not None and callable(getattr(owner, "drgb_ready", None)) and getattr(owner, "early_drgb", False):
-            ready_cb = _c_hook(_READY_FN, owner.drgb_ready, ready_err)
-        # ... and may take the per-Gaussian backward in several launches, told after each one which rows are final (include/radegs.h:
-        # grad_chunks / grads_ready): its all-reduce of those rows then runs under the launches that follow
-        chunks_cb, nchunks = None, 0
-        if owner is not None and callable(getattr(owner, "grads_ready", None)) and int(getattr(owner, "grad_chunks", 0) or 0) > 1 \
-                and getattr(owner, "early_grads", False):
-            nchunks = int(owner.grad_chunks)
-            chunks_cb = _c_hook(_GRADS_READY_FN, owner.grads_ready, ready_err)
-        a = _bwd_args(P=P, D=int(degree), M=M, R=int(R), width=W, height=H, background=bg, means3D=m3, shs=shs, colors_precomp=col, alphas=al,
-                      scales=sc, rotations=rot, cov3D_precomp=cov, viewmatrix=vm, projmatrix=pm, cam_pos=cp,
-                      scale_modifier=float(scale_modifier), tan_fovx=float(tan_fovx), tan_fovy=float(tan_fovy), kernel_size=float(kernel_size),
-                      radii=rad, normalmap=nm, geom_buffer=gb if gb.numel() else None, binning_buffer=bb if bb.numel() else None,
-                      image_buffer=ib if ib.numel() else None,
-                      dL_dpix=g[0], dL_dpix_coord=g[1], dL_dpix_mcoord=g[2], dL_dpix_depth=g[3], dL_dpix_mdepth=g[4], dL_dalphas=g[5],
-                      dL_dpix_normal=g[6],
-                      dL_dmean2D=dL_dmeans2D, dL_dcolor=dL_dcolors, dL_dopacity=dL_dopacity, dL_dmean3D=dL_dmeans3D, dL_dcov3D=dL_dcov3D,
-                      dL_dsh=dL_dsh if M else None, dL_dscale=dL_dscales, dL_drot=dL_drotations,
-                      require_coord=int(bool(require_coord)), require_depth=int(bool(require_depth)), debug=int(bool(debug)),
-                      dL_drgb_clamped=drgb, opacity_grad_intended=int(bool(OPACITY_GRAD_INTENDED)), drgb_ready=ready_cb,
-                      grad_chunks=nchunks, grads_ready=chunks_cb, keep_sums=int(bool(KEEP_ACC)), acc_reuse=int(acc_cached is not None))
-        if ordered:
-            rc = _backward_ordered(L, a, acc, P, R, require_coord, dev, akey)
-        else:
-            if acc_cached is not None:
-                _ACC_LOCK.acquire()
-            try:
-                with torch.cuda.device(dev):
-                    rc = L.radegs_backward(ctypes.byref(a), acc.cb, None, _stream(dev))
-                acc.release()
-                if acc_cached is not None and (rc != 0 or acc.error is not None or ready_err):
-                    _ACC_SCRATCH.pop(akey, None)   # the scratch is in an unknown state: the next call starts from a fresh one
-            finally:
-                if acc_cached is not None:
-                    _ACC_LOCK.release()
+        a = _args(RadegsBwdArgs, R=int(R), width=int(dL_dout_color.size(2)), height=int(dL_dout_color.size(1)),
+                  background=_f32(background, "bg"), alphas=_f32(alphas, "alphas"), radii=radii.contiguous(), normalmap=_f32(normalmap, "normalmap"),
+                  geom_buffer=gb if gb.numel() else None, binning_buffer=bb if bb.numel() else None, image_buffer=ib if ib.numel() else None,
+                  dL_dpix=_f32(dL_dout_color, "dL_dcolor"), dL_dpix_coord=_f32(dL_dout_coord, "dL_dcoord"),
+                  dL_dpix_mcoord=_f32(dL_dout_mcoord, "dL_dmcoord"), dL_dpix_depth=_f32(dL_dout_depth, "dL_ddepth"),
+                  dL_dpix_mdepth=_f32(dL_dout_mdepth, "dL_dmdepth"), dL_dalphas=_f32(dL_dout_alpha, "dL_dalpha"),
+                  dL_dpix_normal=_f32(dL_dout_normal, "dL_dnormal"),
+                  dL_dmean2D=dL_dmeans2D, dL_dcolor=dL_dcolors, dL_dopacity=dL_dopacity, dL_dmean3D=dL_dmeans3D, dL_dcov3D=dL_dcov3D,
+                  dL_dsh=dL_dsh if M else None, dL_dscale=dL_dscales, dL_drot=dL_drotations,
+                  require_coord=int(bool(require_coord)), require_depth=int(bool(require_depth)), debug=int(bool(debug)),
+                  dL_drgb_clamped=drgb, opacity_grad_intended=int(bool(OPACITY_GRAD_INTENDED)), keep_sums=int(bool(KEEP_ACC)),
+                  **g, **_exchange_hooks(grad_alloc, drgb, hook_errors))
+        rc, acc = _run_backward(L, a, dev, ordered, hook_errors)
         if acc.error is not None:
             raise acc.error
-        if ready_err:
-            raise ready_err[0]
+        if hook_errors:
+            raise hook_errors[0]
         _check(rc, "radegs_backward_ordered" if ordered else "radegs_backward")
         if KEEP_ACC:
-            global LAST_ACC
             LAST_ACC = acc.tensor.view(torch.float32)
-        if sc is None:  # precomputed covariance: scale/rotation grads are identically zero
+        if g["scales"] is None:  # precomputed covariance: scale/rotation grads are identically zero
             dL_dscales.zero_()
             dL_drotations.zero_()
-    return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
+    return tuple(grads)
 
 
 def backward_from_sums(sums, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx,
@@ -630,28 +653,22 @@ def backward_from_sums(sums, means3D, radii, colors, scales, rotations, scale_mo
         raise RuntimeError(f"sums must be ({P}, {rec})")
     out = [torch.full(s, float("nan"), **fo) for s in ((P, 3), (P, 3), (P, 1), (P, 3), (P, 6), (P, max(M, 1), 3), (P, 3), (P, 4))]
     dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations = out
-    m3, col = _f32(means3D, "means3D"), _f32(colors, "colors_precomp")
-    sc, rot, cov = _f32(scales, "scales"), _f32(rotations, "rotations"), _f32(cov3D_precomp, "cov3D_precomp")
-    vm, pm, cp, shs = _f32(viewmatrix, "viewmatrix"), _f32(projmatrix, "projmatrix"), _f32(campos, "campos"), _f32(sh, "shs")
-    rad, gb = radii.contiguous(), geomBuffer.contiguous()
     want_drgb = bool(want_drgb) or drgb_ready is not None
     drgb = torch.full((P, 3), float("nan"), **fo) if want_drgb else None
     cb_err = []
-    ready_cb, chunks_cb = _c_hook(_READY_FN, drgb_ready, cb_err), _c_hook(_GRADS_READY_FN, grads_ready, cb_err)
-    a = _bwd_args(P=P, D=int(degree), M=M, width=int(image_width), height=int(image_height), means3D=m3, shs=shs, colors_precomp=col,
-                  scales=sc, rotations=rot, cov3D_precomp=cov, viewmatrix=vm, projmatrix=pm, cam_pos=cp,
-                  scale_modifier=float(scale_modifier), tan_fovx=float(tan_fovx), tan_fovy=float(tan_fovy), kernel_size=float(kernel_size),
-                  radii=rad, geom_buffer=gb,
-                  dL_dmean2D=dL_dmeans2D, dL_dcolor=dL_dcolors, dL_dopacity=dL_dopacity, dL_dmean3D=dL_dmeans3D, dL_dcov3D=dL_dcov3D,
-                  dL_dsh=dL_dsh if M else None, dL_dscale=dL_dscales, dL_drot=dL_drotations, require_coord=int(bool(require_coord)),
-                  dL_drgb_clamped=drgb, opacity_grad_intended=int(bool(OPACITY_GRAD_INTENDED)), drgb_ready=ready_cb,
-                  grad_chunks=int(grad_chunks), grads_ready=chunks_cb, keep_sums=int(bool(keep_sums)))
+    g = _gaussian_fields(means3D, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
+                         kernel_size, sh, degree, campos)
+    a = _args(RadegsBwdArgs, width=int(image_width), height=int(image_height), radii=radii.contiguous(), geom_buffer=geomBuffer.contiguous(),
+              dL_dmean2D=dL_dmeans2D, dL_dcolor=dL_dcolors, dL_dopacity=dL_dopacity, dL_dmean3D=dL_dmeans3D, dL_dcov3D=dL_dcov3D,
+              dL_dsh=dL_dsh if M else None, dL_dscale=dL_dscales, dL_drot=dL_drotations, require_coord=int(bool(require_coord)),
+              dL_drgb_clamped=drgb, opacity_grad_intended=int(bool(OPACITY_GRAD_INTENDED)), drgb_ready=_c_hook(_READY_FN, drgb_ready, cb_err),
+              grad_chunks=int(grad_chunks), grads_ready=_c_hook(_GRADS_READY_FN, grads_ready, cb_err), keep_sums=int(bool(keep_sums)), **g)
     with torch.cuda.device(dev):
         rc = L.radegs_backward_from_sums(ctypes.byref(a), _ptr(sm), _stream(dev))
     if cb_err:
         raise cb_err[0]
     _check(rc, "radegs_backward_from_sums")
-    if sc is None:
+    if g["scales"] is None:
         dL_dscales.zero_()
         dL_drotations.zero_()
     out = (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, (dL_dsh if M else None), dL_dscales, dL_drotations)
@@ -713,15 +730,11 @@ def integrate_gaussians_to_points(background, points3D, means3D, colors, opacity
     out_coordinate2d = torch.empty((PN, 2), **fo)
     out_sdf = torch.empty((PN,), **fo)
     geom, binning, img, pts = _Resizable(dev), _Resizable(dev), _Resizable(dev), _Resizable(dev)
-    bg, m3, p3 = _f32(background, "bg"), _f32(means3D, "means3D"), _f32(points3D, "points3D")
-    col, op = _f32(colors, "colors_precomp"), _f32(opacity, "opacities")
-    sc, rot, cov = _f32(scales, "scales"), _f32(rotations, "rotations"), _f32(cov3D_precomp, "cov3D_precomp")
-    vm, pm, cp, shs = _f32(viewmatrix, "viewmatrix"), _f32(projmatrix, "projmatrix"), _f32(campos, "campos"), _f32(sh, "shs")
-    M = int(sh.size(1)) if (sh is not None and sh.numel() != 0) else 0
-    a = RadegsIntegrateArgs(P, int(degree), M, PN, W, H, _ptr(bg), _ptr(m3), _ptr(shs), _ptr(col), _ptr(op), _ptr(sc), _ptr(rot),
-                            _ptr(cov), _ptr(vm), _ptr(pm), _ptr(cp), _ptr(p3), float(scale_modifier), float(tan_fovx), float(tan_fovy),
-                            float(kernel_size), int(bool(debug)), _ptr(out_color), _ptr(out_alpha_integrated),
-                            _ptr(out_color_integrated), _ptr(out_coordinate2d), _ptr(out_sdf), _ptr(radii))
+    a = _args(RadegsIntegrateArgs, PN=PN, width=W, height=H, background=_f32(background, "bg"), opacities=_f32(opacity, "opacities"),
+              points3D=_f32(points3D, "points3D"), debug=int(bool(debug)), out_color=out_color, out_alpha_integrated=out_alpha_integrated,
+              out_color_integrated=out_color_integrated, out_coordinate2d=out_coordinate2d, out_sdf=out_sdf, radii=radii,
+              **_gaussian_fields(means3D, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
+                                 kernel_size, sh, degree, campos))
     with torch.cuda.device(dev):
         rc = L.radegs_integrate(ctypes.byref(a), geom.cb, None, binning.cb, None, img.cb, None, pts.cb, None, _stream(dev))
     for r in (geom, binning, img, pts):
@@ -742,7 +755,7 @@ def debug_export(name, dtype, numel, P, R, W, H, require_coord, geomBuffer, binn
     dst = torch.empty(numel, dtype=dtype, device=dev)
     if name == "blk_chunks":
         # the last array of the image state, copied at the size asked for: it starts where a state without stream storage ends, less
-        # the layout's 256 bytes of tail padding (csrc/rg_layout.h: Carver::total)
+        # the layout's 256 bytes of tail padding (csrc/rg_layout.h: kTailPad)
         end = int(L.radegs_image_bytes(int(W), int(H))) - 256 + dst.numel() * dst.element_size()
         have = imageBuffer.numel() * imageBuffer.element_size()
         if end > have:

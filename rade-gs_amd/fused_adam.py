@@ -17,18 +17,11 @@ class RadegsAdamTensor(ctypes.Structure):
                 ("numel", ctypes.c_ulonglong), ("lr", ctypes.c_float), ("step", ctypes.c_double)]
 
 
-_bound = False
+_SIGNATURES = {"radegs_adam_step": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(RadegsAdamTensor)] + [ctypes.c_double] * 3 + [ctypes.c_void_p])}
 
 
 def _lib():
-    global _bound
-    L = _C.library()
-    if not _bound:
-        L.radegs_adam_step.restype = ctypes.c_int
-        L.radegs_adam_step.argtypes = [ctypes.c_int, ctypes.POINTER(RadegsAdamTensor), ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                       ctypes.c_void_p]
-        _bound = True
-    return L
+    return _C.bind(_SIGNATURES)
 
 
 class Adam(torch.optim.Optimizer):

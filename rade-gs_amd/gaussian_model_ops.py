@@ -10,7 +10,6 @@ import torch
 
 from diff_gaussian_rasterization import _C
 
-_bound = False
 DENSIFY_NUM_TENSORS = 18
 
 
@@ -18,31 +17,21 @@ class RadegsDensifyTensors(ctypes.Structure):
     _fields_ = [("inp", ctypes.c_void_p * DENSIFY_NUM_TENSORS), ("out", ctypes.c_void_p * DENSIFY_NUM_TENSORS)]
 
 
+_I, _VP, _FL = ctypes.c_int, ctypes.c_void_p, ctypes.c_float
+_SIGNATURES = {
+    "radegs_filter3d_forward": (_I, [_I] + [_VP] * 6),
+    "radegs_filter3d_backward": (_I, [_I] + [_VP] * 8),
+    "radegs_compute_filter3d": (_I, [_I, _VP, _I, _VP, _FL, _VP, _VP, _VP, _VP]),
+    "radegs_densify_stats": (_I, [_I] + [_VP] * 9),
+    "radegs_densify_stats_reduced": (_I, [_I] + [_VP] * 8),
+    "radegs_densify_plan_bytes": (ctypes.c_size_t, [_I]),
+    "radegs_densify_plan": (_I, [_I] + [_VP] * 5 + [_FL, _VP, _FL, _FL, _I, _FL, _VP, ctypes.c_size_t, _VP, _VP]),
+    "radegs_densify_apply": (_I, [_I, _I, _I, ctypes.POINTER(RadegsDensifyTensors), _VP, _VP, _VP]),
+}
+
 
 def _lib():
-    global _bound
-    L = _C.library()
-    if not _bound:
-        vp = ctypes.c_void_p
-        L.radegs_filter3d_forward.restype = ctypes.c_int
-        L.radegs_filter3d_forward.argtypes = [ctypes.c_int] + [vp] * 6
-        L.radegs_filter3d_backward.restype = ctypes.c_int
-        L.radegs_filter3d_backward.argtypes = [ctypes.c_int] + [vp] * 8
-        L.radegs_compute_filter3d.restype = ctypes.c_int
-        L.radegs_compute_filter3d.argtypes = [ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_float, vp, vp, vp, vp]
-        L.radegs_densify_stats.restype = ctypes.c_int
-        L.radegs_densify_stats.argtypes = [ctypes.c_int] + [vp] * 9
-        L.radegs_densify_stats_reduced.restype = ctypes.c_int
-        L.radegs_densify_stats_reduced.argtypes = [ctypes.c_int] + [vp] * 8
-        L.radegs_densify_plan_bytes.restype = ctypes.c_size_t
-        L.radegs_densify_plan_bytes.argtypes = [ctypes.c_int]
-        L.radegs_densify_plan.restype = ctypes.c_int
-        L.radegs_densify_plan.argtypes = [ctypes.c_int] + [vp] * 5 + [ctypes.c_float, vp, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_float,
-                                                                    vp, ctypes.c_size_t, vp, vp]
-        L.radegs_densify_apply.restype = ctypes.c_int
-        L.radegs_densify_apply.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RadegsDensifyTensors), vp, vp, vp]
-        _bound = True
-    return L
+    return _C.bind(_SIGNATURES)
 
 
 def _prep(t, name, cols):

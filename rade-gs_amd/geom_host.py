@@ -11,17 +11,7 @@ ERR_TOO_LARGE = -6   # RADEGS_ERR_TOO_LARGE (include/radegs.h)
 # the C types of the signature tables
 vp, ll, i32, sz, f32, f64 = ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_size_t, ctypes.c_float, ctypes.c_double
 pf32, pf64 = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)
-_bound = set()
-
-
-def bind(signatures):
-    """sets {"radegs_x": (restype, [argtypes...]), ...} on the library, each name once, and returns the library"""
-    L = _C.library()
-    for name in signatures.keys() - _bound:
-        fn = getattr(L, name)
-        fn.restype, fn.argtypes = signatures[name]
-        _bound.add(name)
-    return L
+bind = _C.bind   # sets a module's table {"radegs_x": (restype, [argtypes...]), ...} on the library, once, and returns the library
 
 
 def check(rc, what):

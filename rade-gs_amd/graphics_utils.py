@@ -19,27 +19,19 @@ class RadegsNormalArgs(ctypes.Structure):
                 ("fovy", ctypes.c_double), ("map1", ctypes.c_void_p), ("map2", ctypes.c_void_p)]
 
 
-_bound = False
+_I, _VP, _AP = ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(RadegsNormalArgs)
+_SIGNATURES = {
+    "radegs_normals_forward": (_I, [_AP, _VP, _VP]),
+    "radegs_normals_backward": (_I, [_AP, _VP, _VP, _VP, _VP]),
+    "radegs_normal_loss_scratch_bytes": (ctypes.c_size_t, [_I, _I]),
+    "radegs_normal_loss_forward": (_I, [_AP, _VP, ctypes.c_float, _VP, _VP, _VP]),
+    "radegs_normal_loss_backward": (_I, [_AP, _VP, ctypes.c_float, _VP, _VP, _VP, _VP, _VP]),
+    "radegs_normals_last_error": (ctypes.c_char_p, []),
+}
 
 
 def _lib():
-    global _bound
-    L = _C.library()
-    if not _bound:
-        vp, ap = ctypes.c_void_p, ctypes.POINTER(RadegsNormalArgs)
-        L.radegs_normals_forward.restype = ctypes.c_int
-        L.radegs_normals_forward.argtypes = [ap, vp, vp]
-        L.radegs_normals_backward.restype = ctypes.c_int
-        L.radegs_normals_backward.argtypes = [ap, vp, vp, vp, vp]
-        L.radegs_normal_loss_scratch_bytes.restype = ctypes.c_size_t
-        L.radegs_normal_loss_scratch_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
-        L.radegs_normal_loss_forward.restype = ctypes.c_int
-        L.radegs_normal_loss_forward.argtypes = [ap, vp, ctypes.c_float, vp, vp, vp]
-        L.radegs_normal_loss_backward.restype = ctypes.c_int
-        L.radegs_normal_loss_backward.argtypes = [ap, vp, ctypes.c_float, vp, vp, vp, vp, vp]
-        L.radegs_normals_last_error.restype = ctypes.c_char_p
-        _bound = True
-    return L
+    return _C.bind(_SIGNATURES)
 
 
 def _check(rc, what):

@@ -20,32 +20,21 @@ import torch
 
 from diff_gaussian_rasterization import _C
 
-_bound = False
+_I, _VP, _SZ = ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t
+_SIGNATURES = {
+    "radegs_photometric_scratch_bytes": (_SZ, [_I, _I, _I]),
+    "radegs_photometric_forward": (_I, [_I, _I, _I, _VP, _VP, ctypes.c_float, _VP, _VP, _VP, _VP]),
+    "radegs_photometric_backward": (_I, [_I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "radegs_appearance_downsample_forward": (_I, [_I, _I, _VP, _VP, _VP]),
+    "radegs_appearance_downsample_backward": (_I, [_I, _I, _VP, _VP, _VP]),
+    "radegs_appearance_head_scratch_bytes": (_SZ, [_I, _I, _I]),
+    "radegs_appearance_head_forward": (_I, [_I] * 4 + [_VP] * 8 + [_SZ, _VP, _VP, _VP]),
+    "radegs_appearance_head_backward": (_I, [_I] * 4 + [_VP] * 9 + [_SZ] + [_VP] * 7),
+}
 
 
 def _lib():
-    global _bound
-    L = _C.library()
-    if not _bound:
-        vp, ci = ctypes.c_void_p, ctypes.c_int
-        L.radegs_photometric_scratch_bytes.restype = ctypes.c_size_t
-        L.radegs_photometric_scratch_bytes.argtypes = [ci, ci, ci]
-        L.radegs_photometric_forward.restype = ci
-        L.radegs_photometric_forward.argtypes = [ci, ci, ci, vp, vp, ctypes.c_float, vp, vp, vp, vp]
-        L.radegs_photometric_backward.restype = ci
-        L.radegs_photometric_backward.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, vp]
-        L.radegs_appearance_downsample_forward.restype = ci
-        L.radegs_appearance_downsample_forward.argtypes = [ci, ci, vp, vp, vp]
-        L.radegs_appearance_downsample_backward.restype = ci
-        L.radegs_appearance_downsample_backward.argtypes = [ci, ci, vp, vp, vp]
-        L.radegs_appearance_head_scratch_bytes.restype = ctypes.c_size_t
-        L.radegs_appearance_head_scratch_bytes.argtypes = [ci, ci, ci]
-        L.radegs_appearance_head_forward.restype = ci
-        L.radegs_appearance_head_forward.argtypes = [ci] * 4 + [vp] * 8 + [ctypes.c_size_t, vp, vp, vp]
-        L.radegs_appearance_head_backward.restype = ci
-        L.radegs_appearance_head_backward.argtypes = [ci] * 4 + [vp] * 9 + [ctypes.c_size_t] + [vp] * 7
-        _bound = True
-    return L
+    return _C.bind(_SIGNATURES)
 
 
 def _prep(img, gt):

@@ -7,19 +7,12 @@ import torch
 
 from diff_gaussian_rasterization import _C as _radegs
 
-_bound = False
+_SIGNATURES = {"radegs_knn_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int]),
+               "radegs_knn_mean_dist2": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 4)}
 
 
 def _lib():
-    global _bound
-    L = _radegs.library()
-    if not _bound:
-        L.radegs_knn_scratch_bytes.restype = ctypes.c_size_t
-        L.radegs_knn_scratch_bytes.argtypes = [ctypes.c_int]
-        L.radegs_knn_mean_dist2.restype = ctypes.c_int
-        L.radegs_knn_mean_dist2.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        _bound = True
-    return L
+    return _radegs.bind(_SIGNATURES)
 
 
 def distCUDA2(points):

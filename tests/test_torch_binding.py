@@ -137,6 +137,55 @@ def test_compiled_module_equals_the_ctypes_binding(coord, depth, precomp):
 
 
 @pytest.mark.gpu
+def test_compiled_module_drops_its_scratch_when_the_next_call_reports_the_error(monkeypatch):
+    """The rule both bindings share: ANY negative return code empties the cache of accumulation scratches.  A stream backward
+    on an overwritten image state poisons its scratch with NaN and returns 0; the error arrives with the next call, here a forward
+    (tests/test_gpu_parity.py::test_stream_backward_on_an_overwritten_image_state_reports_an_error_instead_of_trapping, the same scene).
+    The per-Gaussian kernel of the poisoned backward clears the rows of the Gaussians of ITS view only, so a scratch that survived the error
+    would hand NaN to the next view's backward for every Gaussian that view sees and the first did not."""
+    import diff_gaussian_rasterization._C as C
+    from synth_scene import jittered_view, to_device
+    T = _binding()
+    monkeypatch.setenv("RADEGS_STREAMS", "1")
+    C.reload_env()
+    dev = torch.device("cuda:0")
+    first = make_scene(4000, 176, 120, sh_degree=1, mu_px=2.0, seed=97, kernel_size=0.0, require_coord=False, require_depth=True)
+    second = jittered_view(first, 1, angle_deg=10.0, shift=0.2)   # chosen with the CPU oracle: 69 Gaussians it sees and the first does not
+    g = {k: v.to(dev) for k, v in upstream_grads(first, 97).items()}
+    e = torch.Tensor([])
+
+    def forward(mod, s):
+        return mod.rasterize_gaussians(s.bg, s.means3D, e, s.opacities, s.scales, s.rotations, 1.0, e, s.viewmatrix, s.projmatrix, s.tanfovx,
+                                       s.tanfovy, s.kernel_size, s.H, s.W, s.shs, s.sh_degree, s.campos, False, s.require_coord, s.require_depth, False)
+
+    def backward(mod, s, fw):
+        R, color, coord, mcoord, alpha, normal, depth, mdepth, radii, geom, binning, img = fw
+        return mod.rasterize_gaussians_backward(s.bg, s.means3D, radii, e, s.scales, s.rotations, 1.0, e, s.viewmatrix, s.projmatrix, s.tanfovx,
+                                                s.tanfovy, s.kernel_size, g["color"], g["coord"], g["mcoord"], g["depth"], g["mdepth"], g["alpha"],
+                                                g["normal"], normal, s.shs, s.sh_degree, s.campos, geom, R, binning, img, alpha, s.require_coord,
+                                                s.require_depth, False)
+    s1, s2 = to_device(first, dev), to_device(second, dev)
+    fw = forward(T, s1)
+    assert C.last_forward_used_streams() is True
+    seen_first = fw[8] > 0
+    fw[11].zero_()                       # the image state, tag included, is gone
+    backward(T, s1, fw)                  # poisons the cached scratch; no exception yet
+    torch.cuda.synchronize(dev)
+    with pytest.raises(RuntimeError, match="does not hold the entry streams"):
+        forward(T, s1)                   # the next call reports it: the cache must be empty afterwards
+    fw2 = forward(T, s2)
+    newly_seen = (fw2[8] > 0) & ~seen_first
+    assert bool(newly_seen.any()), "the second pose sees no Gaussian the first did not"
+    got = backward(T, s2, fw2)
+    ref = backward(C, s2, forward(C, s2))
+    torch.cuda.synchronize(dev)
+    for name, a, b in zip(("dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dscales", "dL_drotations"), got, ref):
+        assert bool(torch.isfinite(a).all()), (name, "non-finite elements:", int((~torch.isfinite(a)).sum()))
+        scale = float(b.abs().max()) + 1e-30
+        assert float((a - b).abs().max()) <= 1e-3 * scale, (name, float((a - b).abs().max()), scale)
+
+
+@pytest.mark.gpu
 def test_compiled_module_runs_on_the_current_stream():
     """The module queues on torch's CURRENT stream of the inputs' device (c10::hip::getCurrentHIPStreamMasqueradingAsCUDA), as upstream's
     kernels do: a forward + backward issued inside `torch.cuda.stream(side)` is ordered with the side stream's other work and equals the
