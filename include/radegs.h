@@ -757,6 +757,52 @@ int radegs_tntcull_render_finish(long long V, long long F, const double* vertice
 int radegs_tntcull_count_views(long long N, const float* points /* [N,3] */, int B, int H, int W, const float* depths /* [B,H,W] */,
                                const float* w2c /* [B,12] */, float fx, float fy, float cx, float cy, float eps, int* counts /* [N] */, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Mesh clean-up: the steps that treat the mesh as a graph, which upstream hands to Open3D
+ * (utils/mesh_utils.py:23-44 post_process_mesh, mesh_extract.py:104 compute_vertex_normals) and to trimesh
+ * (eval_tnt/cull_mesh.py:186-202 get_connected_mesh).  Conventions as above: device pointers, 0 or a negative
+ * RADEGS_ERR_*, work enqueued on `stream`, nothing read back, arguments refused before the first HIP call.
+ * faces int64 [F,3], vertices float64 [V,3]; V < 2^31 and F <= 2^30, beyond that RADEGS_ERR_TOO_LARGE; F == 0 launches
+ * nothing.  Workspaces are 16-byte aligned.  A face with an index outside [0, V) is never used to address memory: it
+ * joins nothing, has area 0, adds to no normal and does not survive a compaction.
+ *
+ * radegs_meshclean_cluster: triangle_clusters[f] in [0, C) and *n_clusters = C.  The 3 F records (min, max) of the
+ *   edges corner k -> corner k + 1 are sorted; a record with equal ends joins nothing; manifold = 0: all triangles of
+ *   the records with one key are joined (Open3D's cluster_connected_triangles), manifold = 1: only where exactly two
+ *   records have the key (trimesh's face_adjacency; records are counted, so a triangle (a, b, a) brings two).  Clusters
+ *   are numbered by ascending smallest triangle index.  The labels do not depend on the order of the atomics.
+ * radegs_meshclean_stats: cluster_n_triangles [C]; cluster_area [C] (may be NULL) = the sum of
+ *   0.5 * sqrt((nx nx + ny ny) + nz nz), n = (b - a) x (c - a) = (uy vz - uz vy, uz vx - ux vz, ux vy - uy vx), one
+ *   rounding per operation, over the cluster's triangles in ascending index: consecutive groups of 256 (the last
+ *   padded with 0.0) through the 256-wide halving tree, then the group sums added to 0.0 in ascending order;
+ *   total_area [1] (may be NULL) = the two-stage fixed-order sum over all triangles in their own order.  C is the value
+ *   radegs_meshclean_cluster left in *n_clusters, read by the host in between to size these outputs.
+ * radegs_meshclean_compact_plan / _apply: a face is selected unless remove[f] != 0 (remove may be NULL) or
+ *   cluster_keep[triangle_clusters[f]] == 0 (cluster_keep may be NULL); drop_unreferenced: only the corners of the
+ *   selected faces stay as vertices; drop_degenerate: a selected face with two equal indices goes (after the vertices
+ *   were marked).  counts2 = {vertices kept, faces kept}, which the host reads to size kept_vertices [nv] (the old index
+ *   of every new vertex) and out_faces [nf,3] (renumbered); both keep the original relative order.
+ * radegs_meshclean_vertex_normals: normals [V,3] = per vertex the sum of the n above over its corners in ascending
+ *   (triangle, corner) order, starting from 0.0; normalized: divided by len = sqrt((sx sx + sy sy) + sz sz), or
+ *   (0, 0, 1) unless len is positive and finite.
+ * --------------------------------------------------------------------------------------------------------------- */
+size_t radegs_meshclean_cluster_bytes(long long F);
+int radegs_meshclean_cluster(long long V, long long F, const long long* faces, int manifold, void* workspace, size_t workspace_bytes,
+                             long long* triangle_clusters /* [F] */, long long* n_clusters /* [1] */, void* stream);
+size_t radegs_meshclean_stats_bytes(long long F, long long C);
+int radegs_meshclean_stats(long long V, long long F, long long C, const double* vertices, const long long* faces, const long long* triangle_clusters,
+                           void* workspace, size_t workspace_bytes, long long* cluster_n_triangles /* [C] */, double* cluster_area /* [C] */,
+                           double* total_area /* [1] */, void* stream);
+size_t radegs_meshclean_compact_bytes(long long V, long long F);
+int radegs_meshclean_compact_plan(long long V, long long F, long long C, const long long* faces, const unsigned char* remove /* [F] */,
+                                  const long long* triangle_clusters /* [F] */, const unsigned char* cluster_keep /* [C] */, int drop_degenerate,
+                                  int drop_unreferenced, void* workspace, size_t workspace_bytes, long long* counts2, void* stream);
+int radegs_meshclean_compact_apply(long long V, long long F, const long long* faces, const void* workspace, long long nv_out, long long nf_out,
+                                   long long* kept_vertices /* [nv_out] */, long long* out_faces /* [nf_out,3] */, void* stream);
+size_t radegs_meshclean_normals_bytes(long long F);
+int radegs_meshclean_vertex_normals(long long V, long long F, const double* vertices, const long long* faces, int normalized, void* workspace,
+                                    size_t workspace_bytes, double* normals /* [V,3] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,11 +46,12 @@ UNITS = {
     "radegs_adam": ["radegs_adam.hip", os.path.join("..", "..", "include", "radegs.h")],
     "radegs_densify": ["radegs_densify.hip", "rg_prims.h", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
     "radegs_knn": ["radegs_knn.hip", "rg_prims.h", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
-    "radegs_tetmesh": ["radegs_tetmesh.hip", "rg_prims.h", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
+    "radegs_tetmesh": ["radegs_tetmesh.hip", "rg_filter.h", "rg_prims.h", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
     "radegs_mesheval": ["radegs_mesheval.hip", "rg_prims.h", "rg_reduce.h", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
     "radegs_tsdf": ["radegs_tsdf.hip", "rg_mc_tables.h", "rg_prims.h", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
     "radegs_tnteval": ["radegs_tnteval.hip", "rg_prims.h", "rg_reduce.h", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
     "radegs_tntcull": ["radegs_tntcull.hip", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
+    "radegs_meshclean": ["radegs_meshclean.hip", "rg_filter.h", "rg_prims.h", "rg_reduce.h", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
     "radegs_appearance": ["radegs_appearance.hip", "rg_reduce.h", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
 }
 # Units outside the rasterizer's decision chain have no bit-exactness contract with the oracle: let them contract to fma.

@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include "../../include/radegs.h"
+#include "rg_filter.h"
 #include "rg_prims.h"
 #include "rg_workspace.h"
 
@@ -333,35 +334,40 @@ __global__ void __launch_bounds__(256) filter_apply_kernel(long long NV, long lo
   }
 }
 
-struct FilterView {
-  uint32_t *flags, *incl;
-  void* temp;
-  size_t temp_bytes, bytes;
-};
-static FilterView filter_carve(long long NV, long long NF, void* base) {
+using rg::FilterView;
+
+// The part of the two filter plans after the vertex flags w.flags[0, NV) are on their way: the face flags, the scan, the counts.
+static int filter_plan_faces(long long NV, long long NF, const long long* faces, const FilterView& w, long long* counts2, hipStream_t s) {
+  if (NF) hipLaunchKernelGGL(keep_face_kernel, dim3(blocks_of((size_t)NF)), dim3(256), 0, s, NV, NF, faces, w.flags);
+  return rg::filter_scan_counts(NV, NF, w, counts2, s);
+}
+
+}  // namespace rgt
+
+// rg_filter.h: the half of the filter radegs_meshclean.hip shares
+namespace rg {
+
+FilterView filter_carve(long long NV, long long NF, void* base) {
   const size_t n = (size_t)(NV + NF);
-  rg::Carver c(base);
+  Carver c(base);
   FilterView v;
-  v.temp_bytes = rg::scan_temp_bytes(n);
+  v.temp_bytes = scan_temp_bytes(n);
   v.flags = c.take<uint32_t>(n);
   v.incl = c.take<uint32_t>(n);
   v.temp = c.take<char>(v.temp_bytes);
   v.bytes = c.off;
   return v;
 }
-static bool filter_sizes_ok(long long NV, long long NF) {
+bool filter_sizes_ok(long long NV, long long NF) {
   return NV >= 0 && NF >= 0 && (unsigned long long)NV < kMaxItems && (unsigned long long)NF < kMaxItems && (unsigned long long)(NV + NF) < kMaxItems;
 }
-
-// The part of the two filter plans after the vertex flags w.flags[0, NV) are on their way: the face flags, the scan, the counts.
-static int filter_plan_faces(long long NV, long long NF, const long long* faces, const FilterView& w, long long* counts2, hipStream_t s) {
-  if (NF) hipLaunchKernelGGL(keep_face_kernel, dim3(blocks_of((size_t)NF)), dim3(256), 0, s, NV, NF, faces, w.flags);
-  if (rg::inclusive_scan_gather_u32(w.temp, w.temp_bytes, w.flags, nullptr, w.incl, (size_t)(NV + NF), s) != hipSuccess) return RADEGS_ERR_HIP;
-  hipLaunchKernelGGL(filter_counts_kernel, dim3(1), dim3(1), 0, s, NV, NF, w.incl, counts2);
-  return rg::launch_status();
+int filter_scan_counts(long long NV, long long NF, const FilterView& w, long long* counts2, hipStream_t s) {
+  if (inclusive_scan_gather_u32(w.temp, w.temp_bytes, w.flags, nullptr, w.incl, (size_t)(NV + NF), s) != hipSuccess) return RADEGS_ERR_HIP;
+  hipLaunchKernelGGL(rgt::filter_counts_kernel, dim3(1), dim3(1), 0, s, NV, NF, w.incl, counts2);
+  return launch_status();
 }
 
-}  // namespace rgt
+}  // namespace rg
 
 extern "C" {
 
@@ -459,20 +465,20 @@ int radegs_tetmesh_bisect(long long N, float* left_pts, float* right_pts, float*
 }
 
 size_t radegs_tetmesh_filter_plan_bytes(long long NV, long long NF) {
-  if (!rgt::filter_sizes_ok(NV, NF) || NV + NF == 0) return 0;
-  return rgt::filter_carve(NV, NF, nullptr).bytes;
+  if (!rg::filter_sizes_ok(NV, NF) || NV + NF == 0) return 0;
+  return rg::filter_carve(NV, NF, nullptr).bytes;
 }
 
 int radegs_tetmesh_filter_plan(long long NV, long long NF, const float* end_points, const float* end_scales, const long long* faces, void* workspace,
                                size_t workspace_bytes, long long* counts2, void* stream_v) {
   if (NV < 0 || NF < 0 || !counts2) return RADEGS_ERR_INVALID_ARG;
-  if (!rgt::filter_sizes_ok(NV, NF)) return RADEGS_ERR_TOO_LARGE;
+  if (!rg::filter_sizes_ok(NV, NF)) return RADEGS_ERR_TOO_LARGE;
   hipStream_t s = static_cast<hipStream_t>(stream_v);
   if (NV == 0) return hipMemsetAsync(counts2, 0, 2 * sizeof(long long), s) == hipSuccess ? 0 : RADEGS_ERR_HIP;   // no vertex: no face survives
   if (!end_points || !end_scales || (NF && !faces) || !workspace || workspace_bytes < radegs_tetmesh_filter_plan_bytes(NV, NF) ||
       !rg::aligned16(workspace))
     return RADEGS_ERR_INVALID_ARG;
-  const rgt::FilterView w = rgt::filter_carve(NV, NF, workspace);
+  const rg::FilterView w = rg::filter_carve(NV, NF, workspace);
   hipLaunchKernelGGL(rgt::keep_vertex_kernel, dim3(rg::blocks_of((size_t)NV)), dim3(256), 0, s, NV, end_points, end_scales, w.flags);
   return rgt::filter_plan_faces(NV, NF, faces, w, counts2, s);
 }
@@ -480,13 +486,13 @@ int radegs_tetmesh_filter_plan(long long NV, long long NF, const float* end_poin
 int radegs_tetmesh_filter_plan_flags(long long NV, long long NF, const unsigned* vertex_flags, const long long* faces, void* workspace,
                                      size_t workspace_bytes, long long* counts2, void* stream_v) {
   if (NV < 0 || NF < 0 || !counts2) return RADEGS_ERR_INVALID_ARG;
-  if (!rgt::filter_sizes_ok(NV, NF)) return RADEGS_ERR_TOO_LARGE;
+  if (!rg::filter_sizes_ok(NV, NF)) return RADEGS_ERR_TOO_LARGE;
   hipStream_t s = static_cast<hipStream_t>(stream_v);
   if (NV == 0) return hipMemsetAsync(counts2, 0, 2 * sizeof(long long), s) == hipSuccess ? 0 : RADEGS_ERR_HIP;
   if (!vertex_flags || (NF && !faces) || !workspace || workspace_bytes < radegs_tetmesh_filter_plan_bytes(NV, NF) ||
       !rg::aligned16(workspace))
     return RADEGS_ERR_INVALID_ARG;
-  const rgt::FilterView w = rgt::filter_carve(NV, NF, workspace);
+  const rg::FilterView w = rg::filter_carve(NV, NF, workspace);
   if (hipMemcpyAsync(w.flags, vertex_flags, (size_t)NV * sizeof(uint32_t), hipMemcpyDeviceToDevice, s) != hipSuccess) return RADEGS_ERR_HIP;
   return rgt::filter_plan_faces(NV, NF, faces, w, counts2, s);
 }
@@ -494,10 +500,10 @@ int radegs_tetmesh_filter_plan_flags(long long NV, long long NF, const unsigned*
 int radegs_tetmesh_filter_apply(long long NV, long long NF, const float* points, const long long* faces, const void* workspace, long long nv_out,
                                 long long nf_out, float* out_vertices, long long* out_faces, void* stream) {
   if (NV < 0 || NF < 0 || nv_out < 0 || nf_out < 0 || nv_out > NV || nf_out > NF) return RADEGS_ERR_INVALID_ARG;
-  if (!rgt::filter_sizes_ok(NV, NF)) return RADEGS_ERR_TOO_LARGE;
+  if (!rg::filter_sizes_ok(NV, NF)) return RADEGS_ERR_TOO_LARGE;
   if (NV == 0 || nv_out == 0) return 0;
   if (!points || (NF && !faces) || !workspace || !out_vertices || (nf_out && !out_faces)) return RADEGS_ERR_INVALID_ARG;
-  const rgt::FilterView w = rgt::filter_carve(NV, NF, const_cast<void*>(workspace));
+  const rg::FilterView w = rg::filter_carve(NV, NF, const_cast<void*>(workspace));
   hipLaunchKernelGGL(rgt::filter_apply_kernel, dim3(rg::blocks_of((size_t)(NV + (nf_out ? NF : 0)))), dim3(256), 0, static_cast<hipStream_t>(stream), NV,
                      nf_out ? NF : 0, nv_out, nf_out, points, faces, w.flags, w.incl, out_vertices, out_faces);
   return rg::launch_status();

@@ -113,7 +113,11 @@ EXPORTED_SYMBOLS = ("radegs_forward", "radegs_backward", "radegs_backward_ordere
                     "radegs_tnteval_voxel_plan", "radegs_tnteval_voxel_emit", "radegs_tnteval_sums_bytes", "radegs_tnteval_pair_sums",
                     "radegs_tnteval_histogram",
                     # Tanks-and-Temples mesh culling (bound in tnt_cull.py)
-                    "radegs_tntcull_render_bytes", "radegs_tntcull_render_begin", "radegs_tntcull_render_finish", "radegs_tntcull_count_views")
+                    "radegs_tntcull_render_bytes", "radegs_tntcull_render_begin", "radegs_tntcull_render_finish", "radegs_tntcull_count_views",
+                    # mesh clean-up (bound in mesh_clean.py)
+                    "radegs_meshclean_cluster_bytes", "radegs_meshclean_cluster", "radegs_meshclean_stats_bytes", "radegs_meshclean_stats",
+                    "radegs_meshclean_compact_bytes", "radegs_meshclean_compact_plan", "radegs_meshclean_compact_apply",
+                    "radegs_meshclean_normals_bytes", "radegs_meshclean_vertex_normals")
 
 _lib = None
 # test hook: when True, the per-Gaussian accumulation scratch of the last backward is kept in LAST_ACC

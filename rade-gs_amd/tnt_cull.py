@@ -2,13 +2,15 @@
 tnt_eval.evaluate -- one depth map of the mesh per camera (upstream: pyrender / EGL), the per-vertex count of the cameras that see a vertex
 (Mesher.point_masks at forecast_radius 0), and the faces whose three vertices at least `min_views` cameras see.  GPU only.  The rasterizer
 is float64 and pinned to a written rule set (include/radegs.h); the vertex test is float32, as upstream's.  Reading the
-trajectory, trimesh's load / merge_vertices, the forecast branch and get_connected_mesh stay with the caller."""
+trajectory, trimesh's load / merge_vertices and the forecast branch stay with the caller; Mesher.get_connected_mesh, the
+step after cull_mesh (cull_mesh.py:283), is mesh_clean's and is passed on here under the name the reference's class has it."""
 import math
 
 import numpy as np
 import torch
 
 import geom_host as gh
+import mesh_clean
 from diff_gaussian_rasterization import _C
 from geom_host import f32, f64, i32, ll, sz, vp
 
@@ -25,7 +27,9 @@ _SIGNATURES = {
     "radegs_tetmesh_filter_plan_bytes": (sz, [ll, ll]),
     "radegs_tetmesh_filter_plan_flags": (i32, [ll, ll, vp, vp, vp, sz, vp, vp]),
     "radegs_tetmesh_filter_apply": (i32, [ll, ll, vp, vp, vp, ll, ll, vp, vp, vp]),
+    **mesh_clean.SIGNATURES,      # get_connected_mesh below runs on them
 }
+get_connected_mesh = mesh_clean.get_connected_mesh      # cull_mesh.py:186-202
 
 
 def _lib():

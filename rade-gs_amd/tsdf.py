@@ -317,9 +317,10 @@ def fuse_views(views, render_fn, voxel_size=0.002, depth_max=8.0, alpha_thres=0.
     return grid.extract_triangle_mesh(weight_threshold)
 
 
-def write_ply(path, vertices, faces, colors=None):
-    """binary little-endian PLY of a triangle mesh: float32 x y z per vertex, then uchar red green blue when `colors` ([V,3] in [0, 1]) is
-    given; `uchar 3, int32 x 3` per face"""
+def write_ply(path, vertices, faces, colors=None, normals=None):
+    """binary little-endian PLY of a triangle mesh: float32 x y z per vertex, then float32 nx ny nz when `normals` ([V,3], e.g.
+    mesh_clean.compute_vertex_normals) is given, then uchar red green blue when `colors` ([V,3] in [0, 1]) is given; `uchar 3, int32 x 3` per
+    face.  Without `normals` the file is what it was before the keyword existed, byte for byte."""
     def host(a):
         return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
     v = np.ascontiguousarray(host(vertices), dtype="<f4").reshape(-1, 3)
@@ -328,6 +329,12 @@ def write_ply(path, vertices, faces, colors=None):
         raise RuntimeError("write_ply: a face index is outside the vertices")
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
     header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n" % v.shape[0]
+    if normals is not None:
+        n = np.ascontiguousarray(host(normals), dtype="<f4").reshape(-1, 3)
+        if n.shape[0] != v.shape[0]:
+            raise RuntimeError("write_ply: `normals` must have one row per vertex")
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        header += "property float nx\nproperty float ny\nproperty float nz\n"
     if colors is not None:
         c = host(colors).reshape(-1, 3)
         if c.shape[0] != v.shape[0]:
@@ -337,6 +344,8 @@ def write_ply(path, vertices, faces, colors=None):
     header += "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % f.shape[0]
     vrec = np.empty(v.shape[0], dtype=fields)
     vrec["x"], vrec["y"], vrec["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if normals is not None:
+        vrec["nx"], vrec["ny"], vrec["nz"] = n[:, 0], n[:, 1], n[:, 2]
     if colors is not None:
         c8 = np.rint(np.clip(c.astype(np.float64), 0.0, 1.0) * 255.0).astype(np.uint8)
         vrec["red"], vrec["green"], vrec["blue"] = c8[:, 0], c8[:, 1], c8[:, 2]
