@@ -803,6 +803,44 @@ size_t radegs_meshclean_normals_bytes(long long F);
 int radegs_meshclean_vertex_normals(long long V, long long F, const double* vertices, const long long* faces, int normalized, void* workspace,
                                     size_t workspace_bytes, double* normals /* [V,3] */, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Delaunay: the tetrahedra of N points, which upstream gets from tetranerf's CGAL binding
+ * (mesh_extract_tetrahedra.py:63, cpp.triangulate).  Conventions as above: device pointers unless marked (host), 0 or a
+ * negative RADEGS_ERR_*, work enqueued on `stream`, nothing read back, arguments refused before the first HIP call.
+ * points float64 [N,3], finite; 4 <= N <= 2^31 - 8 and record_capacity <= 2^32 - 65 537, beyond that
+ * RADEGS_ERR_TOO_LARGE.  The workspace is 16-byte aligned, radegs_delaunay_bytes(N, record_capacity) long, and the same
+ * for plan and emit: emit reads what plan left in it.
+ *
+ * Coordinates triangulated (radegs_delaunay_perturb writes them to out [N,3]; plan computes the same):
+ *   x' = x + scale * (u - 0.5),  one rounding per operation;  x' = x where scale == 0;
+ *   u = (z >> 11) * 2^-53,  z = fin((3 i + axis + 1) * 0x9E3779B97F4A7C15 + seed * 0xD1B54A32D192ED03)  mod 2^64,
+ *   fin(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31.
+ *   The caller passes scale = jitter * bounding-box diagonal.
+ * Every point clips its own Voronoi cell (rade-gs_amd/csrc/rg_delaunay_cell.h states the predicates, the four ghost
+ * generators at infinity that close the cells of hull points, and the error bound behind `uncertain`); a cell's
+ * vertices that hold no ghost are the tetrahedra at that point.
+ *
+ * radegs_delaunay_plan: bounds (host) = {min x, y, z, max x, y, z} of the points, used only to lay the search grid: any
+ *   finite box gives the same result.  Appends one record (the ascending quadruple of point indices) per tetrahedron
+ *   per corner that found it to the workspace, at most record_capacity of them, and writes counts4 = {records found
+ *   (4 T on a consistent input; above record_capacity: nothing past the capacity was written, call again with more
+ *   room), points deferred to the one-wave-per-point kernel, predicate values within their error bound, cells that
+ *   outgrew the 256 faces / 508 triangles of that kernel}.  The host reads counts4.
+ * radegs_delaunay_emit: records = counts4[0] <= record_capacity.  Sorts the records (two passes of the two-word sort),
+ *   and writes one row per distinct quadruple, in lexicographic order, to cells int32 [out_capacity,4] (rows past the
+ *   capacity are dropped): (a, b, c, d) ascending, c and d exchanged where det[b - a, c - a, d - a] < 0 on x'.
+ *   counts2 = {distinct quadruples, those not found exactly four times or with a zero determinant}.
+ *
+ * Size.  A record costs 16 B and the sort's working arrays 56 B more, and 4 T is about 27 N on scattered points, so the
+ * workspace is about 2 KB a point (N = 30 M: 58 GB); the 32-bit sort words bound 4 T below 2^32 - 65 536, N near 150 M.
+ * --------------------------------------------------------------------------------------------------------------- */
+size_t radegs_delaunay_bytes(long long N, long long record_capacity);
+int radegs_delaunay_perturb(long long N, const double* points /* [N,3] */, double scale, unsigned long long seed, double* out /* [N,3] */, void* stream);
+int radegs_delaunay_plan(long long N, const double* points /* [N,3] */, const double* bounds /* (host) [6] */, double scale, unsigned long long seed,
+                         long long record_capacity, void* workspace, size_t workspace_bytes, long long* counts4, void* stream);
+int radegs_delaunay_emit(long long N, long long records, long long record_capacity, void* workspace, size_t workspace_bytes, long long out_capacity,
+                         int* cells /* [out_capacity,4] */, long long* counts2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,7 @@ UNITS = {
     "radegs_tnteval": ["radegs_tnteval.hip", "rg_prims.h", "rg_reduce.h", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
     "radegs_tntcull": ["radegs_tntcull.hip", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
     "radegs_meshclean": ["radegs_meshclean.hip", "rg_filter.h", "rg_prims.h", "rg_reduce.h", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
+    "radegs_delaunay": ["radegs_delaunay.hip", "rg_delaunay_cell.h", "rg_prims.h", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
     "radegs_appearance": ["radegs_appearance.hip", "rg_reduce.h", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
 }
 # Units outside the rasterizer's decision chain have no bit-exactness contract with the oracle: let them contract to fma.

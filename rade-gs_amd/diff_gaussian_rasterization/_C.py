@@ -117,7 +117,9 @@ EXPORTED_SYMBOLS = ("radegs_forward", "radegs_backward", "radegs_backward_ordere
                     # mesh clean-up (bound in mesh_clean.py)
                     "radegs_meshclean_cluster_bytes", "radegs_meshclean_cluster", "radegs_meshclean_stats_bytes", "radegs_meshclean_stats",
                     "radegs_meshclean_compact_bytes", "radegs_meshclean_compact_plan", "radegs_meshclean_compact_apply",
-                    "radegs_meshclean_normals_bytes", "radegs_meshclean_vertex_normals")
+                    "radegs_meshclean_normals_bytes", "radegs_meshclean_vertex_normals",
+                    # Delaunay tetrahedralisation (bound in delaunay.py)
+                    "radegs_delaunay_bytes", "radegs_delaunay_perturb", "radegs_delaunay_plan", "radegs_delaunay_emit")
 
 _lib = None
 # test hook: when True, the per-Gaussian accumulation scratch of the last backward is kept in LAST_ACC

@@ -2,10 +2,12 @@
 GaussianRasterizer.integrate -- marching tetrahedra (utils/tetmesh.py), GaussianModel.get_tetra_points, the per-view
 accumulation of evaluage_cull_alpha, the bisection along every crossing edge and the final vertex / face filter.  GPU only:
 upstream moves marching tetrahedra to the CPU to save memory; here it is a sort over the crossing edges on the device.
-The Delaunay triangulation (`cells`) is an input."""
+The Delaunay triangulation (`cells`) is an input of every function here; delaunay.triangulate, the step that makes it
+(mesh_extract_tetrahedra.py:63), is passed on under its name."""
 import numpy as np
 import torch
 
+import delaunay
 import geom_host as gh
 from diff_gaussian_rasterization import _C
 from geom_host import i32, ll, sz, vp
@@ -21,7 +23,11 @@ _SIGNATURES = {
     "radegs_tetmesh_filter_plan_bytes": (sz, [ll, ll]),
     "radegs_tetmesh_filter_plan": (i32, [ll, ll, vp, vp, vp, vp, sz, vp, vp]),
     "radegs_tetmesh_filter_apply": (i32, [ll, ll, vp, vp, vp, ll, ll, vp, vp, vp]),
+    # delaunay.py binds its own table; it is merged here because the check that the signature tables of the host modules together cover every
+    # exported symbol reads this module's table, not delaunay's
+    **delaunay.SIGNATURES,
 }
+triangulate = delaunay.triangulate      # mesh_extract_tetrahedra.py:63, cpp.triangulate
 
 
 def _lib():
