@@ -841,6 +841,40 @@ int radegs_delaunay_plan(long long N, const double* points /* [N,3] */, const do
 int radegs_delaunay_emit(long long N, long long records, long long record_capacity, void* workspace, size_t workspace_bytes, long long out_capacity,
                          int* cells /* [out_capacity,4] */, long long* counts2, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Image evaluation: what render.py -> metric.py need and upstream takes from torchvision and
+ * lpipsPyTorch: the 8-bit round trip of a saved image, PSNR's squared-difference sum, and the LPIPS-VGG trunk and
+ * taps.  Conventions as above: device pointers unless marked (host), 0 or a negative RADEGS_ERR_*, work enqueued on
+ * `stream`, nothing read back, arguments refused before the first HIP call.  All float32 unless stated; activations
+ * are channels-last [N,H,W,C]; H, W <= 32768 and N H W < 2^31 - 64.
+ *
+ * radegs_imageeval_conv3x3: y = max(conv3x3(x, w) + bias, 0), stride 1, zero padding 1.  Cin a multiple of 16, Cout a
+ *   multiple of 64.  Every output element is ONE fmaf chain that starts at the bias, in the K order of
+ *   rade-gs_amd/csrc/rg_conv_chain.h (chunks of 16 channels, then the nine taps row by row, then the chunk's channels);
+ *   the f32-input MFMA computes it.  packed_weight holds w[co][ci][ky][kx] as [Cout/64][Cin/16][ky*3+kx][ci%16][co%64],
+ *   16-byte aligned like x.
+ * radegs_imageeval_conv3x3_first: the same chain for Cin = 3 (one chunk) on a planar image [N,3,H,W], with
+ *   (image - mean3[c]) / std3[c] applied as a pixel is loaded; a pixel outside the image is 0 after that step.
+ *   mean3, std3 (host).  packed_weight is [ky*3+kx][ci][Cout].
+ * radegs_imageeval_tap: feat [2,H,W,C] holds the feature maps of the two images, C in {64,128,256,512}.
+ *   out[0] (float64) = 1/(H W) sum over pixels of sum_c lin[c] (fx_c/(|fx| + 1e-10) - fy_c/(|fy| + 1e-10))^2, |.| the
+ *   channel norm; float32 per pixel, float64 in a fixed order across pixels, so two calls return the same bits.
+ *   pooled (may be NULL; needs H, W >= 2) [2,H/2,W/2,C] = the 2x2 max pool, the last row / column of an odd size
+ *   dropped.  Workspace: 16-byte aligned, radegs_imageeval_tap_bytes(H, W).
+ * radegs_imageeval_quantize: image planar [3,H,W]; u8 [H,W,3] (may be NULL) = trunc(clamp(x * 255 + 0.5, 0, 255)) with
+ *   one rounding per operation, NaN -> 0; out [3,H,W] (may be NULL) = u8 / 255.
+ * radegs_imageeval_ssd: out[0] (float64) = sum_i float32((a_i - b_i)^2), n >= 1 elements, fixed order.
+ * --------------------------------------------------------------------------------------------------------------- */
+int radegs_imageeval_conv3x3(int N, int H, int W, int Cin, int Cout, const float* x, const float* packed_weight, const float* bias, float* y, void* stream);
+int radegs_imageeval_conv3x3_first(int N, int H, int W, int Cout, const float* image, const float* mean3 /* (host) */, const float* std3 /* (host) */,
+                                   const float* packed_weight, const float* bias, float* y, void* stream);
+size_t radegs_imageeval_tap_bytes(int H, int W);
+int radegs_imageeval_tap(int H, int W, int C, const float* feat, const float* lin /* [C] */, float* pooled, void* workspace, size_t workspace_bytes,
+                         double* out, void* stream);
+int radegs_imageeval_quantize(int H, int W, const float* image, unsigned char* u8, float* out, void* stream);
+size_t radegs_imageeval_ssd_bytes(void);
+int radegs_imageeval_ssd(long long n, const float* a, const float* b, void* workspace, size_t workspace_bytes, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,10 @@ SORT_CHECK_LIB = os.path.join(OUT_DIR, "libradegs_sort_check.so")
 # product, a shared object of its own -- never linked into the product, not package data
 BLEND_CHECK_SRC = os.path.join(CSRC, "radegs_blend_check.hip")
 BLEND_CHECK_LIB = os.path.join(OUT_DIR, "libradegs_blend_check.so")
+# test-only: the host fmaf-chain restatement of the image-evaluation convolution (tests/imageeval_restatement.py), g++ over the header the
+# kernel states its K order in; -ffp-contract=off so that fmaf() stays the only fused step -- never linked into the product, not package data
+CONV_CHAIN_CHECK_SRC = os.path.join(CSRC, "radegs_conv_chain_check.cpp")
+CONV_CHAIN_CHECK_LIB = os.path.join(OUT_DIR, "libradegs_conv_chain_check.so")
 ARCH = "gfx950"   # the only target: kernels use gfx950's 160 KB LDS (radegs_sort.hip's 32-item scatter needs 70 KB per workgroup), its DPP /
                   # bank-mask forms and wave64 tilings -- changing this does not give a working gfx90a / gfx942 library
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-munsafe-fp-atomics",
@@ -54,6 +58,7 @@ UNITS = {
     "radegs_meshclean": ["radegs_meshclean.hip", "rg_filter.h", "rg_prims.h", "rg_reduce.h", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
     "radegs_delaunay": ["radegs_delaunay.hip", "rg_delaunay_cell.h", "rg_prims.h", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
     "radegs_appearance": ["radegs_appearance.hip", "rg_reduce.h", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
+    "radegs_imageeval": ["radegs_imageeval.hip", "rg_conv_chain.h", "rg_reduce.h", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
 }
 # Units outside the rasterizer's decision chain have no bit-exactness contract with the oracle: let them contract to fma.
 # radegs_filter3d calls expf: under `fast` the compiler also contracts INSIDE expf's expansion (x*log2e - round(x*log2e) becomes one fma and
@@ -112,6 +117,11 @@ def build(force=False, verbose=True):
         subprocess.check_call(cmd)
     if force or _stale(BLEND_CHECK_LIB, [blend_obj]):
         cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", BLEND_CHECK_LIB, blend_obj]
+        if verbose:
+            print("[radegs build]", " ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+    if force or _stale(CONV_CHAIN_CHECK_LIB, [CONV_CHAIN_CHECK_SRC, os.path.join(CSRC, "rg_conv_chain.h"), os.path.abspath(__file__)]):
+        cmd = [os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I", CSRC, CONV_CHAIN_CHECK_SRC, "-o", CONV_CHAIN_CHECK_LIB]
         if verbose:
             print("[radegs build]", " ".join(cmd), flush=True)
         subprocess.check_call(cmd)

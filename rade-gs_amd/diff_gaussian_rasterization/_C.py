@@ -119,7 +119,10 @@ EXPORTED_SYMBOLS = ("radegs_forward", "radegs_backward", "radegs_backward_ordere
                     "radegs_meshclean_compact_bytes", "radegs_meshclean_compact_plan", "radegs_meshclean_compact_apply",
                     "radegs_meshclean_normals_bytes", "radegs_meshclean_vertex_normals",
                     # Delaunay tetrahedralisation (bound in delaunay.py)
-                    "radegs_delaunay_bytes", "radegs_delaunay_perturb", "radegs_delaunay_plan", "radegs_delaunay_emit")
+                    "radegs_delaunay_bytes", "radegs_delaunay_perturb", "radegs_delaunay_plan", "radegs_delaunay_emit",
+                    # image evaluation (bound in image_eval.py)
+                    "radegs_imageeval_conv3x3", "radegs_imageeval_conv3x3_first", "radegs_imageeval_tap_bytes", "radegs_imageeval_tap",
+                    "radegs_imageeval_quantize", "radegs_imageeval_ssd_bytes", "radegs_imageeval_ssd")
 
 _lib = None
 # test hook: when True, the per-Gaussian accumulation scratch of the last backward is kept in LAST_ACC

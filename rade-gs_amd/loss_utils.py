@@ -18,6 +18,7 @@ import ctypes
 
 import torch
 
+import image_eval
 from diff_gaussian_rasterization import _C
 
 _I, _VP, _SZ = ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t
@@ -30,6 +31,7 @@ _SIGNATURES = {
     "radegs_appearance_head_scratch_bytes": (_SZ, [_I, _I, _I]),
     "radegs_appearance_head_forward": (_I, [_I] * 4 + [_VP] * 8 + [_SZ, _VP, _VP, _VP]),
     "radegs_appearance_head_backward": (_I, [_I] * 4 + [_VP] * 9 + [_SZ] + [_VP] * 7),
+    **image_eval.SIGNATURES,      # the evaluation metrics next to the training losses; image_eval.ssim runs on the ssim below
 }
 
 
