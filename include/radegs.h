@@ -875,6 +875,57 @@ int radegs_imageeval_quantize(int H, int W, const float* image, unsigned char* u
 size_t radegs_imageeval_ssd_bytes(void);
 int radegs_imageeval_ssd(long long n, const float* a, const float* b, void* workspace, size_t workspace_bytes, double* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Model state: the Gaussian model on its way to and from a file, which upstream does through
+ * plyfile and a dozen eager kernels each: GaussianModel.save_ply / load_ply (scene/gaussian_model.py:379-397, 515-559),
+ * reset_opacity (495-513) and create_from_pcd after the kNN step (301-328).  Conventions as above: device pointers, 0
+ * or a negative RADEGS_ERR_*, work enqueued on `stream`, nothing read back, arguments refused before the first HIP
+ * call.  All tensors float32 and contiguous; row counts are long long (20 M records of 252 B pass 4 GB).  Every kernel
+ * is one pass without atomics: two calls return the same bits.  Divisions and square roots are IEEE (the unit is built
+ * without fast-math, clang's default for HIP keeps float division correctly rounded) and no product is contracted.
+ *
+ * radegs_modelio_pack: rows [row_begin, row_end) of xyz [P,3], f_dc [P,1,3], f_rest [P,K,3] (K <=
+ *   RADEGS_MODELIO_MAX_REST; may be NULL for K = 0), opacity [P,1], scaling [P,3], rotation [P,4] and filter_3D [P,1]
+ *   (may be NULL) become records of C = 17 + 3 K (+ 1 with the filter) floats in out [row_end - row_begin, C] (16-byte
+ *   aligned), in the file's order: x y z, nx ny nz (zeros), f_dc_0..2, f_rest_0..3K-1 with f_rest_{c K + k} =
+ *   f_rest[k][c] (upstream's transpose(1,2).flatten(1)), opacity, scale_0..2, rot_0..3, filter_3D.  Bits are copied.
+ * radegs_modelio_unpack: records holds P records of S bytes (1 <= S <= RADEGS_MODELIO_MAX_RECORD), little-endian, at
+ *   a 4-byte aligned address, and is readable up to the next multiple of 4 past P S.  columns [D] (device memory, D <=
+ *   RADEGS_MODELIO_MAX_COLUMNS, 16-byte aligned): for every row r the value of type src_type at byte src_offset of the
+ *   record is written as float32 to dst[r * dst_stride + dst_elem].  F4 with scale = 0 is copied bit for bit; every
+ *   other value goes through double: divided by 255.0 where scale != 0 (so U1 gives float(double(u) / 255.0), upstream's
+ *   float64 quotient followed by .float()), then rounded to nearest even once (F8 as torch.tensor(float64,
+ *   dtype=torch.float)).  A descriptor with an unknown type or that leaves the record reads and writes nothing.
+ * radegs_modelio_reset_opacity: per row, float32, expf / logf / sqrtf, one rounding per operation, in upstream's order:
+ *   q_k = exp(s_k)^2, coef = sqrt(((q0 q1) q2) / (((q0 + f^2)(q1 + f^2))(q2 + f^2))), cur = (1 / (1 + exp(-o))) coef,
+ *   x = min(cur, 0.01) / coef (a NaN passes through), opacity_out = log(x / (1 - x)).  zero_a, zero_b [P] (may be NULL;
+ *   the opacity's two Adam moments) are filled with zeros.
+ * radegs_modelio_init: f_dc = (colors - 0.5f) / 0.28209479177387814f (RGB2SH, IEEE float division), f_rest [P,K,3] =
+ *   0, scaling = log(sqrt(max(dist2, 1e-7f))) in all three columns, rotation (16-byte aligned) = (1, 0, 0, 0), opacity =
+ *   opacity_value, which the caller computes once: the float32 log(0.1f / (1 - 0.1f)).  dist2 [P] is
+ *   radegs_knn_mean_dist2's output.
+ * --------------------------------------------------------------------------------------------------------------- */
+#define RADEGS_MODELIO_MAX_REST 79        /* K: the 64-row LDS image of the output tile stays within 64 KB */
+#define RADEGS_MODELIO_MAX_RECORD 768     /* S */
+#define RADEGS_MODELIO_MAX_COLUMNS 256    /* D */
+enum { RADEGS_MODELIO_I1 = 0, RADEGS_MODELIO_U1, RADEGS_MODELIO_I2, RADEGS_MODELIO_U2, RADEGS_MODELIO_I4, RADEGS_MODELIO_U4, RADEGS_MODELIO_F4,
+       RADEGS_MODELIO_F8 };
+typedef struct RadegsModelioColumn {
+  float* dst;             /* the destination tensor's first element */
+  long long dst_stride;   /* floats between two of its rows */
+  int dst_elem;           /* float within the row */
+  int src_offset;         /* byte within the record */
+  int src_type;           /* RADEGS_MODELIO_* */
+  int scale;              /* 0: the value; 1: the value / 255 */
+} RadegsModelioColumn;
+int radegs_modelio_pack(long long P, long long row_begin, long long row_end, int K, const float* xyz, const float* f_dc, const float* f_rest,
+                        const float* opacity, const float* scaling, const float* rotation, const float* filter_3D, float* out, void* stream);
+int radegs_modelio_unpack(long long P, int S, const void* records, int D, const RadegsModelioColumn* columns, void* stream);
+int radegs_modelio_reset_opacity(long long P, const float* opacity_raw, const float* scaling_raw, const float* filter_3D, float* opacity_out /* [P] */,
+                                 float* zero_a, float* zero_b, void* stream);
+int radegs_modelio_init(long long P, int K, const float* colors /* [P,3] */, const float* dist2 /* [P] */, float opacity_value, float* f_dc, float* f_rest,
+                        float* opacity, float* scaling, float* rotation, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

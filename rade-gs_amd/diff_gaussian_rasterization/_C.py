@@ -122,7 +122,9 @@ EXPORTED_SYMBOLS = ("radegs_forward", "radegs_backward", "radegs_backward_ordere
                     "radegs_delaunay_bytes", "radegs_delaunay_perturb", "radegs_delaunay_plan", "radegs_delaunay_emit",
                     # image evaluation (bound in image_eval.py)
                     "radegs_imageeval_conv3x3", "radegs_imageeval_conv3x3_first", "radegs_imageeval_tap_bytes", "radegs_imageeval_tap",
-                    "radegs_imageeval_quantize", "radegs_imageeval_ssd_bytes", "radegs_imageeval_ssd")
+                    "radegs_imageeval_quantize", "radegs_imageeval_ssd_bytes", "radegs_imageeval_ssd",
+                    # model state (bound in model_io.py)
+                    "radegs_modelio_pack", "radegs_modelio_unpack", "radegs_modelio_reset_opacity", "radegs_modelio_init")
 
 _lib = None
 # test hook: when True, the per-Gaussian accumulation scratch of the last backward is kept in LAST_ACC

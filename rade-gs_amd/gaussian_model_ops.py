@@ -8,6 +8,7 @@ import ctypes
 
 import torch
 
+import model_io as _model_io
 from diff_gaussian_rasterization import _C
 
 DENSIFY_NUM_TENSORS = 18
@@ -27,6 +28,7 @@ _SIGNATURES = {
     "radegs_densify_plan_bytes": (ctypes.c_size_t, [_I]),
     "radegs_densify_plan": (_I, [_I] + [_VP] * 5 + [_FL, _VP, _FL, _FL, _I, _FL, _VP, ctypes.c_size_t, _VP, _VP]),
     "radegs_densify_apply": (_I, [_I, _I, _I, ctypes.POINTER(RadegsDensifyTensors), _VP, _VP, _VP]),
+    **_model_io.SIGNATURES,      # patch_gaussian_model_io installs the methods that run on them
 }
 
 
@@ -300,7 +302,9 @@ def patch_gaussian_model(cls, appearance_network=False):
 
     appearance_network=True also wraps `training_setup`: after upstream's own has built the optimizer,
     `self.appearance_network` is replaced by appearance_network.AppearanceNetwork.adopt(...) of it -- the same Parameter objects, so the
-    optimizer group keeps pointing at live parameters."""
+    optimizer group keeps pointing at live parameters.
+
+    The model's state I/O is installed by patch_gaussian_model_io below; this function leaves those four methods alone."""
     def _add_densification_stats(self, viewspace_point_tensor, update_filter):
         return add_densification_stats(self, viewspace_point_tensor, update_filter)
 
@@ -319,4 +323,25 @@ def patch_gaussian_model(cls, appearance_network=False):
             return out
 
         cls.training_setup = _training_setup
+    return cls
+
+
+def patch_gaussian_model_io(cls):
+    """Installs model_io's save_model_ply, load_model_ply, create_from_pcd and reset_model_opacity on the reference's
+    GaussianModel class as `save_ply(path)`, `load_ply(path)`, `create_from_pcd(pcd, spatial_lr_scale)` and `reset_opacity()`: no plyfile,
+    one kernel each instead of a dozen.  A function of its own, not a keyword of patch_gaussian_model: that function's signature is what its
+    callers and tests know, and it touches none of these four methods.  Returns `cls`; the two compose in either order."""
+    def _save_ply(self, path):
+        return _model_io.save_model_ply(self, path)
+
+    def _load_ply(self, path):
+        return _model_io.load_model_ply(self, path)
+
+    def _create_from_pcd(self, pcd, spatial_lr_scale):
+        return _model_io.create_from_pcd(self, pcd, spatial_lr_scale)
+
+    def _reset_opacity(self):
+        return _model_io.reset_model_opacity(self)
+
+    cls.save_ply, cls.load_ply, cls.create_from_pcd, cls.reset_opacity = _save_ply, _load_ply, _create_from_pcd, _reset_opacity
     return cls
