@@ -252,7 +252,10 @@ typedef struct RadegsIntegrateArgs {
  * covariance eigenvalue <= 1e-8) the inverse ray-space covariance is ZERO: upstream's shadowed variable
  * (forward.cu:223) stores an uninitialised matrix there; (2) contributor ids are 32-bit (upstream truncates to uint16, wrong only for tile lists longer than
  * 65535 entries); (3) the exponent of the point opacity is clamped at +80 (a non-PSD ill-conditioned matrix would
- * otherwise overflow expf). */
+ * otherwise overflow expf); (4) the reference's cap is KEPT although nothing here needs it: a pixel stops at its 2048th used entry
+ * (MAX_NUM_CONTRIBUTORS * 4, forward.cu:1121-1125: the size of the reference's per-thread contributor array; this library only counts).
+ * A query point whose projection is not a number (a NaN coordinate, or 0 * inf in the view transform) is NOT projected: it keeps the
+ * initial values and is counted in no pixel, as in the reference, whose reject test it fails to pass. */
 int radegs_integrate(const RadegsIntegrateArgs* args, radegs_alloc_fn geom_alloc, void* geom_user, radegs_alloc_fn binning_alloc,
                      void* binning_user, radegs_alloc_fn image_alloc, void* image_user, radegs_alloc_fn point_alloc, void* point_user,
                      void* stream);
@@ -277,6 +280,17 @@ size_t radegs_binning_bytes(int R);
  * Returns bytes copied or a negative error. */
 long long radegs_debug_export(const char* name, int P, int R, int width, int height, int require_coord, const void* geom_buffer,
                               const void* binning_buffer, const void* image_buffer, void* dst, size_t dst_bytes, void* stream);
+
+/* Size of the point state radegs_integrate asks its `point_alloc` for: pure host arithmetic, like the three sizes above. */
+size_t radegs_point_bytes(int P, int PN, int width, int height);
+/* The same hook for the point state of radegs_integrate (the buffer its `point_alloc` returned, for the same P, PN, width, height).
+ * Names: "inte_rec" f32[P,8] ({inverse ray-space covariance, upper triangle, 6 | well-conditioned flag | 0}; rows of Gaussians that were
+ * culled are not written), "p2d" f32[PN,2] and "pdepth" f32[PN] (written for projected points only), "ppix" u32[PN] (pixel index, or
+ * 0xFFFFFFFF: not projected), "pt_sorted" u32[PN] (point ids grouped by pixel; as many entries as points were projected), "pix_count"
+ * u32[H*W] (all zero once the scatter has run), "pix_incl" u32[H*W] (inclusive scan of the per-pixel point counts) and "final_T"
+ * f32[H*W].  Same conventions and error returns as radegs_debug_export. */
+long long radegs_debug_export_points(const char* name, int P, int PN, int width, int height, const void* point_buffer, void* dst,
+                                     size_t dst_bytes, void* stream);
 
 /* Speculative binning (see radegs_forward): forwards that ran on a predicted capacity / those whose prediction was too small and
  * were redone with exact sizes, since the last reset. */

@@ -39,7 +39,8 @@ __global__ void __launch_bounds__(256) points_preprocess_kernel(const PointsPreA
   if (pv.z <= 0.2f) return;
   const float ix = (float)((double)(a.focal_x * pv.x / (pv.z + 0.0000001f)) + a.W / 2.);
   const float iy = (float)((double)(a.focal_y * pv.y / (pv.z + 0.0000001f)) + a.H / 2.);
-  if (ix < 0 || ix >= a.W || iy < 0 || iy >= a.H) return;
+  // written as acceptance: a NaN projection (a NaN coordinate, 0 * inf in the view transform) passes no compare and must not be binned
+  if (!(ix >= 0 && ix < a.W && iy >= 0 && iy < a.H)) return;
   a.pdepth[i] = sqrtf(pv.x * pv.x + pv.y * pv.y + pv.z * pv.z);
   a.p2d[i] = make_float2(ix, iy);
   const uint32_t pix = (uint32_t)f2i_sat(floorf(iy)) * (uint32_t)a.W + (uint32_t)f2i_sat(floorf(ix));

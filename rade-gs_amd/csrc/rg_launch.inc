@@ -1185,4 +1185,35 @@ long long radegs_debug_export(const char* name, int P, int R, int width, int hei
   return (long long)bytes;
 }
 
+size_t radegs_point_bytes(int P, int PN, int width, int height) {
+  const size_t HW = (size_t)width * height;
+  return PointState::carve(nullptr, (size_t)P, (size_t)PN, HW, scan_temp_bytes(HW)).total;
+}
+
+long long radegs_debug_export_points(const char* name, int P, int PN, int width, int height, const void* point_buffer, void* dst,
+                                     size_t dst_bytes, void* stream_v) {
+  if (!name || !dst) return fail(RADEGS_ERR_INVALID_ARG, "null argument");
+  if (P < 0 || PN < 0 || width <= 0 || height <= 0) return fail(RADEGS_ERR_INVALID_ARG, "bad sizes");
+  hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  const size_t N = (size_t)width * height;
+  PointState ps = PointState::carve(const_cast<void*>(point_buffer), (size_t)P, (size_t)PN, N, scan_temp_bytes(N));
+  const void* src = nullptr;
+  size_t bytes = 0;
+  const std::string n(name);
+  if (n == "inte_rec") { src = ps.inte_rec; bytes = (size_t)P * 32; }
+  else if (n == "p2d") { src = ps.p2d; bytes = (size_t)PN * 8; }
+  else if (n == "pdepth") { src = ps.pdepth; bytes = (size_t)PN * 4; }
+  else if (n == "ppix") { src = ps.ppix; bytes = (size_t)PN * 4; }
+  else if (n == "pt_sorted") { src = ps.pt_sorted; bytes = (size_t)PN * 4; }
+  else if (n == "pix_count") { src = ps.pix_count; bytes = N * 4; }
+  else if (n == "pix_incl") { src = ps.pix_incl; bytes = N * 4; }
+  else if (n == "final_T") { src = ps.final_T; bytes = N * 4; }
+  else return fail(RADEGS_ERR_INVALID_ARG, "unknown array name");
+  if (bytes > dst_bytes) return fail(RADEGS_ERR_INVALID_ARG, "destination too small");
+  if (bytes == 0) return 0;
+  if (!point_buffer) return fail(RADEGS_ERR_INVALID_ARG, "state buffer missing");
+  RG_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, stream));
+  return (long long)bytes;
+}
+
 }  // extern "C"

@@ -83,7 +83,7 @@ for _s in (RadegsFwdArgs, RadegsBwdArgs, RadegsIntegrateArgs):
 
 # every symbol include/radegs.h declares
 EXPORTED_SYMBOLS = ("radegs_forward", "radegs_backward", "radegs_backward_ordered", "radegs_backward_ordered_scratch_bytes", "radegs_backward_from_sums", "radegs_mark_visible", "radegs_integrate", "radegs_sh_grad_from_views", "radegs_geometry_bytes", "radegs_image_bytes",
-                    "radegs_binning_bytes", "radegs_debug_export", "radegs_forget_image", "radegs_last_error", "radegs_version", "radegs_profile_enable",
+                    "radegs_binning_bytes", "radegs_debug_export", "radegs_point_bytes", "radegs_debug_export_points", "radegs_forget_image", "radegs_last_error", "radegs_version", "radegs_profile_enable",
                     "radegs_profile_select", "radegs_profile_stride", "radegs_binning_stats", "radegs_reload_env", "radegs_last_forward_used_streams", "radegs_profile_num_stages", "radegs_profile_stage_name", "radegs_profile_collect",
                     # fused pre/post steps (bound in graphics_utils.py / gaussian_model_ops.py)
                     "radegs_normals_forward", "radegs_normals_backward", "radegs_normal_loss_scratch_bytes",
@@ -235,6 +235,8 @@ _SIGNATURES = {
     "radegs_image_bytes": (_SZ, [_I, _I]),
     "radegs_binning_bytes": (_SZ, [_I]),
     "radegs_debug_export": (ctypes.c_longlong, [ctypes.c_char_p] + [_I] * 5 + [_VP] * 4 + [_SZ, _VP]),
+    "radegs_point_bytes": (_SZ, [_I] * 4),
+    "radegs_debug_export_points": (ctypes.c_longlong, [ctypes.c_char_p] + [_I] * 4 + [_VP] * 2 + [_SZ, _VP]),
     "radegs_forget_image": (None, [_VP]),
     "radegs_last_error": (ctypes.c_char_p, []),
     "radegs_version": (ctypes.c_char_p, []),
@@ -777,6 +779,31 @@ def debug_export(name, dtype, numel, P, R, W, H, require_coord, geomBuffer, binn
                                   ctypes.c_void_p(binningBuffer.data_ptr()) if binningBuffer.numel() else None,
                                   ctypes.c_void_p(imageBuffer.data_ptr()) if imageBuffer.numel() else None,
                                   ctypes.c_void_p(dst.data_ptr()), dst.numel() * dst.element_size(), _stream(dev))
+    if n < 0:
+        raise RuntimeError(L.radegs_last_error().decode())
+    return dst
+
+
+def point_bytes(P, PN, W, H):
+    """Size of the point state an integrate call of these sizes allocates (radegs_point_bytes)."""
+    return int(library().radegs_point_bytes(int(P), int(PN), int(W), int(H)))
+
+
+def debug_export_points(name, dtype, numel, P, PN, W, H, pointBuffer=None):
+    """Test hook: copy a private array of the point state (see radegs_debug_export_points in include/radegs.h).  pointBuffer None: the
+    state the last integrate_gaussians_to_points left in LAST_POINT_STATE (kept under KEEP_ACC)."""
+    L = library()
+    buf = LAST_POINT_STATE if pointBuffer is None else pointBuffer
+    if buf is None:
+        raise RuntimeError("debug_export_points: no point state (set KEEP_ACC before integrate_gaussians_to_points)")
+    have, need = buf.numel() * buf.element_size(), point_bytes(P, PN, W, H)
+    if have < need:
+        raise RuntimeError(f"debug_export_points: a point state of {have} bytes, (P, PN, W, H) = {(P, PN, W, H)} needs {need}")
+    dev = buf.device
+    dst = torch.empty(numel, dtype=dtype, device=dev)
+    with torch.cuda.device(dev):
+        n = L.radegs_debug_export_points(name.encode(), int(P), int(PN), int(W), int(H), ctypes.c_void_p(buf.data_ptr()),
+                                         ctypes.c_void_p(dst.data_ptr()), dst.numel() * dst.element_size(), _stream(dev))
     if n < 0:
         raise RuntimeError(L.radegs_last_error().decode())
     return dst

@@ -230,3 +230,28 @@ def test_failed_allocation_request_does_not_outlive_a_successful_retry():
     p = r.cb(None, 4096)
     assert p and r.error is None and r.tensor.numel() == 4096
     r.release()
+
+
+def test_point_state_hooks_check_their_arguments_on_the_host():
+    """radegs_point_bytes is host arithmetic, and radegs_debug_export_points refuses a missing or unknown name, bad sizes, a destination that
+    is too small and a missing buffer before any HIP call (the conventions of radegs_debug_export)."""
+    C, L = _c_lib()
+    L.radegs_point_bytes.restype = ctypes.c_size_t
+    L.radegs_point_bytes.argtypes = [ctypes.c_int] * 4
+    ex = L.radegs_debug_export_points
+    ex.restype = ctypes.c_longlong
+    ex.argtypes = [ctypes.c_char_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 2 + [ctypes.c_size_t, ctypes.c_void_p]
+    b = [L.radegs_point_bytes(*k) for k in ((0, 0, 64, 48), (1000, 0, 64, 48), (1000, 5000, 64, 48), (1000, 5000, 640, 480))]
+    assert 0 < b[0] < b[1] < b[2] < b[3]
+    assert b[1] - b[0] >= 1000 * 32 and b[2] - b[1] >= 5000 * 20 and b[3] >= 640 * 480 * 12
+    INVALID, fake = -1, 0x1000
+
+    def call(name, P=4, PN=8, W=16, H=16, buf=fake, dst=fake, n=1 << 20):
+        return ex(name, P, PN, W, H, buf, dst, n, None), L.radegs_last_error().decode()
+    assert call(None)[0] == INVALID and call(b"ppix", dst=None)[0] == INVALID
+    for kw, text in ((dict(name=b"no_such_array"), "unknown array name"), (dict(name=b"ppix", PN=-1), "bad sizes"),
+                     (dict(name=b"final_T", W=0), "bad sizes"), (dict(name=b"inte_rec", n=4 * 32 - 1), "destination too small"),
+                     (dict(name=b"pix_incl", n=16 * 16 * 4 - 1), "destination too small"), (dict(name=b"p2d", buf=None), "state buffer missing")):
+        rc, msg = call(**kw)
+        assert rc == INVALID and text in msg, (kw, rc, msg)
+    assert call(b"inte_rec", P=0)[0] == 0 and call(b"pt_sorted", PN=0, buf=None)[0] == 0      # an empty array: nothing to copy
