@@ -940,6 +940,49 @@ int radegs_modelio_reset_opacity(long long P, const float* opacity_raw, const fl
 int radegs_modelio_init(long long P, int K, const float* colors /* [P,3] */, const float* dist2 /* [P] */, float opacity_value, float* f_dc, float* f_rest,
                         float* opacity, float* scaling, float* rotation, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Scene ingestion: a decoded 8-bit photograph on its way to a training camera, which upstream does
+ * per image on one host thread: PIL.Image.resize + / 255 + permute (utils/general_utils.py PILtoTorch, called from
+ * utils/camera_utils.py loadCam), the Blender RGBA composite (scene/dataset_readers.py:270-276) and the edge map
+ * (scene/cameras.py:59-68).  Conventions as above: device pointers unless marked (host), 0 or a negative
+ * RADEGS_ERR_*, work enqueued on `stream`, nothing read back, arguments refused before the first HIP call.  One pass
+ * per kernel, no atomics: two calls return the same bits.
+ *
+ * radegs_sceneio_resize: src uint8 [H, W, C] interleaved, C in {1, 3, 4}, 4-byte aligned; the result is Pillow's 8-bit
+ *   `resize` with its default filter (bicubic, a = -0.5, antialiased) applied to every channel on its own.  The filter
+ *   coefficients are the caller's: a RadegsSceneioTable (host structure, device arrays) per axis whose size changes,
+ *   NULL for an axis that keeps its size.  Per output index i the table holds bounds[2 i] = first source index,
+ *   bounds[2 i + 1] = n taps, and n coefficients in fixed point with RADEGS_SCENEIO_PRECISION_BITS fractional bits;
+ *   a pass computes clip8((2^21 + sum pixel * k) >> 22) in int32 (the builder of the table asserts 255 sum|k| + 2^21
+ *   < 2^31).  The horizontal pass runs first, over source rows [row_first, row_first + rows_mid) only, into mid
+ *   [rows_mid, Wout, C]; with a vertical table these must be the rows it reads (first, last), without one all H rows.
+ *   The horizontal table's kk is transposed, [ksize, out_size]; the vertical one's is [out_size, ksize]; max_span
+ *   (horizontal only) is the largest number of source pixels that 64 consecutive outputs starting at a multiple of 64
+ *   read, and must make 4 rows of that many pixels fit into 64 KB.  The resulting byte goes to out_u8 [Hout, Wout, C]
+ *   (may be NULL) and, where image is not NULL, through lut [256] (float32: i / 255) to planar float32: channels 0..2
+ *   to image [min(C, 3), Hout, Wout], channel 3 to mask [1, Hout, Wout].  Every value of lut lies in [0, 1]: upstream's
+ *   clamp(0, 1) is the identity and is not run.
+ * radegs_sceneio_composite: rgba uint8 [N, 4] (16-byte aligned) over a white or black background to rgb uint8 [N, 3]
+ *   (4-byte aligned), in float64, one rounding per operation: a = A / 255.0, v = (c / 255.0) a + bg (1 - a), byte =
+ *   trunc(v 255.0) & 0xFF.
+ * radegs_sceneio_edge: image float32 [C, H, W], C in {1, 3}; edge [H, W] = exp(-max over the four neighbours of the
+ *   mean over channels of |centre - neighbour|) in the interior, computed in float64 and rounded once, 0 on the
+ *   one-pixel border.
+ * --------------------------------------------------------------------------------------------------------------- */
+#define RADEGS_SCENEIO_PRECISION_BITS 22
+typedef struct RadegsSceneioTable {
+  const int* bounds;      /* device, [out_size, 2] */
+  const int* kk;          /* device, [ksize, out_size] (horizontal) or [out_size, ksize] (vertical) */
+  int in_size, out_size, ksize;
+  int max_span;           /* horizontal only */
+  int first, last;        /* the source indices the table reads: [first, last) */
+} RadegsSceneioTable;
+int radegs_sceneio_resize(int H, int W, int C, int Hout, int Wout, const unsigned char* src, const RadegsSceneioTable* horizontal /* host */,
+                          const RadegsSceneioTable* vertical /* host */, int row_first, int rows_mid, unsigned char* mid, const float* lut,
+                          unsigned char* out_u8, float* image, float* mask, void* stream);
+int radegs_sceneio_composite(long long N, const unsigned char* rgba, int white_background, unsigned char* rgb, void* stream);
+int radegs_sceneio_edge(int C, int H, int W, const float* image, float* edge /* [H,W] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,6 +61,8 @@ UNITS = {
     "radegs_imageeval": ["radegs_imageeval.hip", "rg_conv_chain.h", "rg_reduce.h", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
     # no entry in UNIT_FLAGS: the default -ffp-contract=off and IEEE divide / sqrt are what reset_opacity and the init state in the header
     "radegs_modelio": ["radegs_modelio.hip", os.path.join("..", "..", "include", "radegs.h")],
+    # default FLAGS too: -ffp-contract=off keeps the composite's float64 products and sums apart, as NumPy computes them
+    "radegs_sceneio": ["radegs_sceneio.hip", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
 }
 # Units outside the rasterizer's decision chain have no bit-exactness contract with the oracle: let them contract to fma.
 # radegs_filter3d calls expf: under `fast` the compiler also contracts INSIDE expf's expansion (x*log2e - round(x*log2e) becomes one fma and

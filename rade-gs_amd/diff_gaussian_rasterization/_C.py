@@ -124,7 +124,9 @@ EXPORTED_SYMBOLS = ("radegs_forward", "radegs_backward", "radegs_backward_ordere
                     "radegs_imageeval_conv3x3", "radegs_imageeval_conv3x3_first", "radegs_imageeval_tap_bytes", "radegs_imageeval_tap",
                     "radegs_imageeval_quantize", "radegs_imageeval_ssd_bytes", "radegs_imageeval_ssd",
                     # model state (bound in model_io.py)
-                    "radegs_modelio_pack", "radegs_modelio_unpack", "radegs_modelio_reset_opacity", "radegs_modelio_init")
+                    "radegs_modelio_pack", "radegs_modelio_unpack", "radegs_modelio_reset_opacity", "radegs_modelio_init",
+                    # scene ingestion (bound in scene_io.py)
+                    "radegs_sceneio_resize", "radegs_sceneio_composite", "radegs_sceneio_edge")
 
 _lib = None
 # test hook: when True, the per-Gaussian accumulation scratch of the last backward is kept in LAST_ACC

@@ -11,6 +11,7 @@ import ctypes
 
 import torch
 
+import scene_io
 from diff_gaussian_rasterization import _C
 
 
@@ -27,6 +28,9 @@ _SIGNATURES = {
     "radegs_normal_loss_forward": (_I, [_AP, _VP, ctypes.c_float, _VP, _VP, _VP]),
     "radegs_normal_loss_backward": (_I, [_AP, _VP, ctypes.c_float, _VP, _VP, _VP, _VP, _VP]),
     "radegs_normals_last_error": (ctypes.c_char_p, []),
+    # scene_io.py binds its own table; it is merged here, next to the helpers that read the `view` its Camera is, because the check that the
+    # signature tables of the host modules together cover every exported symbol reads this module's table, not scene_io's
+    **scene_io.SIGNATURES,
 }
 
 
