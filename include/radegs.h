@@ -983,6 +983,83 @@ int radegs_sceneio_resize(int H, int W, int C, int Hout, int Wout, const unsigne
 int radegs_sceneio_composite(long long N, const unsigned char* rgba, int white_background, unsigned char* rgb, void* stream);
 int radegs_sceneio_edge(int C, int H, int W, const float* image, float* edge /* [H,W] */, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Unbounded mesh extraction: GaussianExtractor.extract_mesh_unbounded, utils/mesh_utils.py:162-270
+ * with utils/mcube_utils.py -- a TSDF over a contracted cube, sampled densely and meshed crop by crop.  Conventions
+ * as for TSDF fusion above: device pointers unless marked (host), 0 or a negative RADEGS_ERR_*, work enqueued on
+ * `stream`, nothing read back, sizes of 0 legal.  All device arithmetic is float32, one rounding per operation,
+ * products before sums in the order written here; sqrt and / are correctly rounded.  NaN follows IEEE: every
+ * comparison with NaN is false, so such a view is skipped.
+ *
+ * Contraction (of a sample y of the contracted cube to the world point x):
+ *   mag = sqrt((y.x y.x + y.y y.y) + y.z y.z); x = y if mag < 1, else (1 / (2 - mag)) (y / mag) per component; then
+ *   x = x radius + center per component.  mag >= 2 is legal (the reference's grid reaches |y| = 1.9 sqrt 3): the
+ *   result is whatever this arithmetic gives, inf and NaN included.
+ * Per-sample truncation (a quirk of the reference, preserved: the norm is taken of the WORLD point, after the
+ *   un-normalisation, mesh_utils.py:198-202): n = sqrt((x.x x.x + x.y x.y) + x.z x.z); trunc = trunc5, and
+ *   trunc = trunc5 (1 / (2 - min(n, 1.9))) if n > 1.  trunc5 = float32(5 voxel_size), rounded once on the host from
+ *   float64.  Without contraction (the colouring pass) x is the input and trunc = trunc5.
+ * Per view v = 0 .. V-1, in this order, m = the view's full_proj_transform [4][4] by rows (row-vector convention):
+ *   q.c = ((x.x m[0][c] + x.y m[1][c]) + x.z m[2][c]) + m[3][c] for c = 0, 1, 3; z = q.w; px = q.x / z; py = q.y / z.
+ *   In view iff -1 < px < 1, -1 < py < 1 and z > 0, all strict.  Bilinear sample, align_corners, border padding:
+ *   ix = min(max(((px + 1) / 2) (W - 1), 0), W - 1), x0 = floor(ix), x1 = x0 + 1, likewise iy, y0, y1 with H;
+ *   nw = (x1 - ix) (y1 - iy), ne = (ix - x0) (y1 - iy), sw = (x1 - ix) (iy - y0), se = (ix - x0) (iy - y0);
+ *   value = (((0 + I[y0][x0] nw) + I[y0][x1] ne) + I[y1][x0] sw) + I[y1][x1] se, a tap with x1 = W or y1 = H
+ *   contributing nothing (its term is left out, not multiplied by zero).  sdf = depth - z.  Integrate iff in view
+ *   and sdf > -trunc: s = min(max(sdf / trunc, -1), 1); tsdf = (tsdf w + s) / (w + 1); rgb.c = (rgb.c w + colour.c)
+ *   / (w + 1) per channel; w = w + 1.  Initially tsdf = 1, w = 1 (one, not zero: a sample seen by n views of constant
+ *   colour c ends with c n / (n + 1)), rgb = 0.  V = 0: every tsdf is 1.
+ * RadegsUnboundedView (a device array [V]): m, then W, H >= 1, depth [H][W], rgb [3][H][W] or null (such a view
+ *   leaves rgb alone); the sizes may differ from view to view.  An entry with W < 1, H < 1 or no depth is skipped.
+ * radegs_unbounded_fuse: explicit mode, samples [M,3]; lattice mode, samples null: the M = nx ny nz samples
+ *   (ax[lx], ay[ly], az[lz]) at index (lx ny + ly) nz + lz, never materialised.  `mapping` (lattice mode only) picks
+ *   how lanes map to samples, RADEGS_UNBOUNDED_ZRUN: a wave is 64 consecutive indices, _BRICK: a wave is a 4x4x4
+ *   brick; the results are the same bits.  contract != 0: samples are contracted, as above; radius must be positive.
+ *   center3 (host) [3].  tsdf [M]; rgb [M,3] or null.  One thread per sample, all views in one launch, one write.
+ * radegs_unbounded_uncontract (after the weld): world [M,3] = the contraction above, then each component v clamped:
+ *   -max_range if v < -max_range, max_range if v > max_range, else v (NaN stays).
+ *
+ * Dense marching cubes over a lattice of nx ny nz values (each >= 2, fewer than 2^31 points) with coordinates ax, ay,
+ *   az: level 0; case bit i = corner i < 0 (csrc/rg_mc_tables.h, the table of TSDF fusion; NaN counts as positive);
+ *   every cell is valid.  A lattice point owns the edges leaving it along +x, +y, +z; an owned edge carries a vertex
+ *   iff its ends differ in sign: t = (0 - v_o) / (v_e - v_o), position c_o + t (c_e - c_o) along the edge's axis and
+ *   the lattice's own coordinates along the other two -- taken from the sample coordinates themselves, so two crops
+ *   that share a plane produce the same bits there.  Orientation as in TSDF fusion.  Vertices in (lattice index,
+ *   axis) order with key ((gx G + gy) G + gz) 3 + axis, g = offset3 + l, 1 <= G <= 2^20, offset3 (host) >= 0,
+ *   offset3 + n <= G; faces [F,3] in (lattice index of the cell's lowest corner, table) order, indices into this
+ *   call's vertices.  counts2 (device) = {V, F}; workspace: radegs_densemc_bytes (0 for a refused lattice), 16-byte
+ *   aligned, untouched between plan and emit.
+ * Crops and weld (host side, rade-gs_amd/unbounded_mesh.py): the lattice of crop (i, j, k) is
+ *   float32(linspace(xs[i], xs[i+1], crop)) per axis, xs = linspace(-R, R, N + 1) in float64, N = resolution / crop;
+ *   adjacent crops share their boundary plane: g = i (crop - 1) + l, G = N (crop - 1) + 1.  The final vertices are
+ *   ascending by key, duplicates removed; faces crop-major (i, then j, then k), then as emitted, re-indexed.  Then
+ *   radegs_unbounded_uncontract with max_range, then the colouring pass (no contraction, rgb) over the vertices.
+ *
+ * Deviations from upstream, restated from memory of skimage and trimesh (neither can be read where this was
+ * written): skimage's Lewiner tables are replaced by the table above; trimesh's merge_vertices(digits_vertex=6) by
+ * the exact key weld; the vertex position is the interpolation of the sample coordinates above, not skimage's
+ * origin + index spacing; the crop is a parameter (upstream: 512).
+ * --------------------------------------------------------------------------------------------------------------- */
+#define RADEGS_UNBOUNDED_ZRUN 0
+#define RADEGS_UNBOUNDED_BRICK 1
+typedef struct RadegsUnboundedView {
+  float m[16];
+  int W, H;
+  const float* depth;
+  const float* rgb;
+} RadegsUnboundedView;
+int radegs_unbounded_fuse(long long M, const float* samples /* [M,3] or null */, const float* ax, const float* ay, const float* az, int nx, int ny, int nz,
+                          int mapping, int V, const RadegsUnboundedView* views /* [V] */, int contract, float radius, const float* center3 /* host */,
+                          float trunc5, float* tsdf /* [M] */, float* rgb /* [M,3] or null */, void* stream);
+int radegs_unbounded_uncontract(long long M, const float* contracted /* [M,3] */, float radius, const float* center3 /* host */, float max_range,
+                                float* world /* [M,3] */, void* stream);
+size_t radegs_densemc_bytes(int nx, int ny, int nz);
+int radegs_densemc_plan(const float* values /* [nx,ny,nz] */, int nx, int ny, int nz, void* workspace, size_t workspace_bytes, long long* counts2,
+                        void* stream);
+int radegs_densemc_emit(const float* values, const float* ax, const float* ay, const float* az, int nx, int ny, int nz, const int* offset3 /* host */,
+                        long long G, const void* workspace, long long V, long long F, float* vertices /* [V,3] */, long long* keys /* [V] */,
+                        long long* faces /* [F,3] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

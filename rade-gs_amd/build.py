@@ -63,6 +63,8 @@ UNITS = {
     "radegs_modelio": ["radegs_modelio.hip", os.path.join("..", "..", "include", "radegs.h")],
     # default FLAGS too: -ffp-contract=off keeps the composite's float64 products and sums apart, as NumPy computes them
     "radegs_sceneio": ["radegs_sceneio.hip", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
+    # default FLAGS: the unit is held to tests/unbounded_restatement.py bit for bit, which needs -ffp-contract=off and IEEE divide / sqrt
+    "radegs_unbounded": ["radegs_unbounded.hip", "rg_mc_tables.h", "rg_prims.h", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
 }
 # Units outside the rasterizer's decision chain have no bit-exactness contract with the oracle: let them contract to fma.
 # radegs_filter3d calls expf: under `fast` the compiler also contracts INSIDE expf's expansion (x*log2e - round(x*log2e) becomes one fma and

@@ -126,7 +126,9 @@ EXPORTED_SYMBOLS = ("radegs_forward", "radegs_backward", "radegs_backward_ordere
                     # model state (bound in model_io.py)
                     "radegs_modelio_pack", "radegs_modelio_unpack", "radegs_modelio_reset_opacity", "radegs_modelio_init",
                     # scene ingestion (bound in scene_io.py)
-                    "radegs_sceneio_resize", "radegs_sceneio_composite", "radegs_sceneio_edge")
+                    "radegs_sceneio_resize", "radegs_sceneio_composite", "radegs_sceneio_edge",
+                    # unbounded mesh extraction (bound in unbounded_mesh.py)
+                    "radegs_unbounded_fuse", "radegs_unbounded_uncontract", "radegs_densemc_bytes", "radegs_densemc_plan", "radegs_densemc_emit")
 
 _lib = None
 # test hook: when True, the per-Gaussian accumulation scratch of the last backward is kept in LAST_ACC

@@ -9,6 +9,7 @@ import torch
 
 import delaunay
 import geom_host as gh
+import unbounded_mesh
 from diff_gaussian_rasterization import _C
 from geom_host import i32, ll, sz, vp
 
@@ -26,6 +27,8 @@ _SIGNATURES = {
     # delaunay.py binds its own table; it is merged here because the check that the signature tables of the host modules together cover every
     # exported symbol reads this module's table, not delaunay's
     **delaunay.SIGNATURES,
+    # likewise unbounded_mesh.py, the other route from a trained model to a mesh
+    **unbounded_mesh.SIGNATURES,
 }
 triangulate = delaunay.triangulate      # mesh_extract_tetrahedra.py:63, cpp.triangulate
 
