@@ -1060,6 +1060,56 @@ int radegs_densemc_emit(const float* values, const float* ax, const float* ay, c
                         long long G, const void* workspace, long long V, long long F, float* vertices /* [V,3] */, long long* keys /* [V] */,
                         long long* faces /* [F,3] */, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Evaluation from files: the step from the files of a geometry evaluation to the tensors of the
+ * units above -- what upstream hands to o3d.io.read_point_cloud, trimesh.load and
+ * o3d.pipelines.registration.registration_ransac_based_on_correspondence (eval_tnt/registration.py:66-110).
+ * Conventions as above: device pointers unless marked (host), 0 or a negative RADEGS_ERR_*, work enqueued on
+ * `stream`, nothing read back, arguments refused before the first HIP call, sizes of 0 legal.  fp64, one rounding per
+ * operation in the order written here, products before sums, IEEE divide and sqrt.
+ *
+ * Records: `buffer` (4-byte aligned, readable up to the next multiple of 4 past the last record) holds, from byte
+ *   byte_offset (any alignment), little-endian records of S bytes, 1 <= S <= RADEGS_MODELIO_MAX_RECORD.  Types are
+ *   RADEGS_MODELIO_*.
+ * radegs_evalio_unpack_points: out [N,3] double; column k is the value of type types3[k] at byte offsets3[k] of the
+ *   record (both host, refused when the value leaves the record).  Integers and F4 are widened exactly, F8 is copied
+ *   bit for bit.
+ * radegs_evalio_unpack_faces: a record holds a list length of count_type (I1 .. U4) at count_offset and three indices
+ *   of index_type (I4 or U4) from index_offset; whatever else it holds is skipped.  faces [F,3] gets the indices as
+ *   read; *bad (device, zeroed by the call) counts the records whose length is not 3 or that hold an index outside
+ *   [0, V).  A caller that finds *bad != 0 must not use faces: the records did not have the fixed stride assumed.
+ *
+ * radegs_evalio_ransac: source, target [N,3], pair i = (source[i], target[i]), N < 2^31; hypotheses h = 0 .. K-1.
+ *   Generator: u(seed, h, k) = the high 32 bits of mix(seed 0x9E3779B97F4A7C15 + h 0xD1B54A32D192ED03 +
+ *   k 0x8CB92BA72F3D8DD7 + 0x2545F4914F6CDD1D) in 64-bit wrapping arithmetic, mix(z): z ^= z >> 30;
+ *   z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31.  Draw k = 0 .. ransac_n - 1 of
+ *   hypothesis h takes the r-th index of [0, N) not taken by an earlier draw, r = (u(seed, h, k) (N - k)) >> 32: the
+ *   sample is a function of (seed, h) alone.
+ *   Similarity of a sample (Eigen's umeyama with scaling, what tnt_eval.umeyama computes from radegs_tnteval_pair_sums'
+ *   numbers): sums of s and t in draw order, means ms, mt = sum / n; Sigma = (sum (t - mt)(s - ms)^T) / n and var =
+ *   (sum (ds0 ds0 + ds1 ds1) + ds2 ds2) / n in draw order; Sigma = U D V^T by RADEGS_EVALIO_RANSAC_SWEEPS sweeps of
+ *   one-sided Jacobi rotations over the column pairs (0,1), (0,2), (1,2), singular values descending; S = diag(1, 1,
+ *   sign(det U det V)); c = ((D0 + D1) + S2 D2) / var; R = U S V^T; T = [c R | mt - (c R) ms].  The rotation agrees with
+ *   any other SVD to rounding only while D1 / D0 is well away from 0.  var = 0 (a sample without extent) or a T that
+ *   is not finite: the hypothesis counts 0 inliers.
+ *   Evaluation: for i ascending, p = T (s_i, 1) with rows ((m0 x + m1 y) + m2 z) + m3, d2 = (dx dx + dy dy) + dz dz of
+ *   p - t_i; where sqrt(d2) < max_dist: counts[h] += 1, sumsq[h] += d2.
+ *   Choice: the largest count; among those the smallest sqrt(sumsq / count); among those the smallest h.  Keys are
+ *   compared, nothing is accumulated atomically: two calls give the same bits whatever the launch geometry.
+ *   out15 = rows 0-2 of T of the chosen hypothesis, its count, its sumsq, h; with every count 0: the identity, 0, 0, -1.
+ *   The kernel stages the pairs through LDS RADEGS_EVALIO_RANSAC_CHUNK at a time.
+ * --------------------------------------------------------------------------------------------------------------- */
+#define RADEGS_EVALIO_RANSAC_CHUNK 256    /* pairs per LDS stage: 12 KB */
+#define RADEGS_EVALIO_RANSAC_SWEEPS 8
+#define RADEGS_EVALIO_RANSAC_MIN_N 3
+#define RADEGS_EVALIO_RANSAC_MAX_N 8
+int radegs_evalio_unpack_points(long long N, int S, const void* buffer, long long byte_offset, const int* offsets3 /* host */, const int* types3 /* host */,
+                                double* out /* [N,3] */, void* stream);
+int radegs_evalio_unpack_faces(long long F, int S, const void* buffer, long long byte_offset, int count_offset, int count_type, int index_offset,
+                               int index_type, long long V, long long* faces /* [F,3] */, unsigned int* bad, void* stream);
+int radegs_evalio_ransac(long long N, const double* source, const double* target, double max_dist, int ransac_n, long long K, unsigned long long seed,
+                         int* counts /* [K] */, double* sumsq /* [K] */, double* out15, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

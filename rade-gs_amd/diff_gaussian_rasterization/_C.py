@@ -128,7 +128,9 @@ EXPORTED_SYMBOLS = ("radegs_forward", "radegs_backward", "radegs_backward_ordere
                     # scene ingestion (bound in scene_io.py)
                     "radegs_sceneio_resize", "radegs_sceneio_composite", "radegs_sceneio_edge",
                     # unbounded mesh extraction (bound in unbounded_mesh.py)
-                    "radegs_unbounded_fuse", "radegs_unbounded_uncontract", "radegs_densemc_bytes", "radegs_densemc_plan", "radegs_densemc_emit")
+                    "radegs_unbounded_fuse", "radegs_unbounded_uncontract", "radegs_densemc_bytes", "radegs_densemc_plan", "radegs_densemc_emit",
+                    # evaluation from files (bound in eval_io.py)
+                    "radegs_evalio_unpack_points", "radegs_evalio_unpack_faces", "radegs_evalio_ransac")
 
 _lib = None
 # test hook: when True, the per-Gaussian accumulation scratch of the last backward is kept in LAST_ACC

@@ -331,3 +331,48 @@ def cull_mesh(vertices, faces, cameras, masks=None, dilation=6):
     if v_in.dtype == torch.float64:            # the kept rows of the caller's own precision
         out_v = v_in[flags.bool()]
     return out_v, out_f
+
+
+# ---------------------------------------------------------------------- from paths to the numbers ----------------------------------------------------------------------
+def _camera_centre(cam):
+    """evaluate_dtu_mesh.py:153-155: c2w[:3, 3] of (world_view_transform.T).inverse(), float32 as torch computes it on the host"""
+    w2c = cam[0] if isinstance(cam, (tuple, list)) else cam.world_view_transform.T
+    return torch.as_tensor(w2c).detach().to("cpu", torch.float32).inverse()[:3, 3].numpy()
+
+
+@torch.no_grad()
+def evaluate_dtu_mesh(mesh_path, cameras, dataset_dir, scan, out_dir=None, perm=None, generator=None, device="cuda"):
+    """evaluate_dtu_mesh.py:141-194 with dtu_eval/eval.py from paths alone: the training cameras' centres are aligned to those of
+    dataset_dir/Calibration/cal18/pos_XXX.txt (scale, then best_fit_transform), the mesh is read, culled (cull_mesh), scaled and moved, and
+    scored against dataset_dir/Points/stl/stl{scan:03}_total.ply with the ObsMask and Plane files (dtu_chamfer).  `cameras` as cull_mesh
+    takes them.  With `out_dir`: recon_culled.ply, recon_aligned.ply and results.json are written there.  Returns dtu_chamfer's dict with
+    `scale`, `R`, `t` and the aligned `vertices` / `faces` added."""
+    import json
+    import os
+
+    import eval_io
+    import tetmesh
+    points = np.array([_camera_centre(cam) for cam in cameras])
+    if points.shape[0] < 3:
+        raise RuntimeError("evaluate_dtu_mesh needs at least three cameras for the alignment")
+    gt_points = eval_io.dtu_camera_centres(os.path.join(dataset_dir, "Calibration", "cal18"), n=min(64, points.shape[0]))
+    scale_gt, scale, r, t = eval_io.dtu_alignment(points[:64], gt_points)
+    obs_mask, BB, Res, plane = eval_io.load_dtu_masks(dataset_dir, scan)
+    v, f = eval_io.read_ply_mesh(mesh_path, device)
+    v, f = cull_mesh(v, f, cameras)
+    dev = v.device
+    if out_dir is not None:
+        os.makedirs(out_dir, exist_ok=True)
+        tetmesh.write_ply(os.path.join(out_dir, "recon_culled.ply"), v, f)
+    v = v * float(scale_gt) / float(scale)                                                  # :180-181
+    v = v @ torch.from_numpy(np.asarray(r.T, dtype=np.float64)).to(dev) + torch.from_numpy(np.asarray(t, dtype=np.float64)).to(dev)
+    v = v.contiguous()
+    if out_dir is not None:
+        tetmesh.write_ply(os.path.join(out_dir, "recon_aligned.ply"), v, f)
+    stl = eval_io.read_ply_points(os.path.join(dataset_dir, "Points", "stl", f"stl{int(scan):03}_total.ply"), device)
+    res = dtu_chamfer(v, f, stl, obs_mask, BB, Res, plane, perm=perm, generator=generator)
+    if out_dir is not None:
+        with open(os.path.join(out_dir, "results.json"), "w") as fp:
+            json.dump({"mean_d2s": res["mean_d2s"], "mean_s2d": res["mean_s2d"], "overall": res["overall"]}, fp, indent=True)
+    res.update(scale=float(scale_gt) / float(scale), R=r, t=t, vertices=v, faces=f)
+    return res

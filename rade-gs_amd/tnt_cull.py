@@ -243,3 +243,18 @@ def cull_mesh(vertices, faces, c2w, H=1080, W=1920, fx=1163.8678928442187, fy=11
     if v_in.dtype == torch.float64:            # the kept rows of the caller's own precision
         out_v = v_in[flags.bool()]
     return out_v, out_f
+
+
+@torch.no_grad()
+def cull_mesh_file(mesh_path, traj_path, out_path=None, device="cuda", **kw):
+    """Mesher.__call__ from paths alone (cull_mesh.py:292-317, 403-416): eval_io.read_ply_mesh, eval_io.merge_vertices (trimesh's
+    load(process=True) and merge_vertices()), eval_io.get_traj, cull_mesh with `kw`, tetmesh.write_ply to `out_path` (default: the mesh
+    path with `.ply` replaced by `_cull.ply`).  Returns (vertices, faces int64, out_path)."""
+    import eval_io
+    import tetmesh
+    v, f = eval_io.read_ply_mesh(mesh_path, device)
+    v, f = eval_io.merge_vertices(v, f)
+    kv, kf = cull_mesh(v, f, eval_io.get_traj(traj_path), **kw)
+    out_path = mesh_path.replace(".ply", "_cull.ply") if out_path is None else out_path
+    tetmesh.write_ply(out_path, kv, kf)
+    return kv, kf, out_path

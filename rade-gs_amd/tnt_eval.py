@@ -1,15 +1,19 @@
 """HIP-backed Tanks-and-Temples mesh evaluation: what the reference does with the marching-tetrahedra mesh --
 eval_tnt/run.py:94-108 and 152-187 with registration.py (crop, voxel / uniform thinning, three rounds of point-to-point ICP with scaling)
 and evaluation.py (nearest-neighbour distances both ways, the cumulative histograms, precision / recall / F-score).  GPU only; geometry is
-float64.  Nearest neighbours are mesh_eval.PointGrid.  Reading the .ply / .log / _trans.txt files, trajectory_alignment (which produces
-`init_transform`), estimate_normals, the coloured clouds, the plots and eval_tnt/cull_mesh.py stay with the caller."""
+float64.  Nearest neighbours are mesh_eval.PointGrid.  The files (.ply / .log / _trans.txt) are read by eval_io; trajectory_alignment, which
+produces `init_transform`, is ransac_correspondence below, a deterministic RANSAC in HIP, and run_evaluation goes from paths
+to the scores.  estimate_normals, the coloured clouds and the plots stay with the caller; eval_tnt/cull_mesh.py is
+tnt_cull."""
 import ctypes
 import json
 import math
+import os
 
 import numpy as np
 import torch
 
+import eval_io
 import geom_host as gh
 from diff_gaussian_rasterization import _C
 from geom_host import f64, i32, ll, pf64, sz, vp
@@ -29,6 +33,7 @@ _SIGNATURES = {
     "radegs_tnteval_sums_bytes": (sz, []),
     "radegs_tnteval_pair_sums": (i32, [ll, vp, ll, vp, vp, vp, sz, vp, vp]),
     "radegs_tnteval_histogram": (i32, [ll, vp, i32, vp, f64, vp, vp, vp]),
+    **eval_io.SIGNATURES,         # ransac_correspondence below runs on radegs_evalio_ransac; the readers are eval_io's
 }
 
 
@@ -372,3 +377,134 @@ def evaluate_histo(source, target, trans, volume, voxel_size, threshold, plot_st
     out = dict(zip(names, precision_recall(dist1, dist2, threshold, plot_stretch)))
     out.update(s=s, t=t, dist1=dist1, idx1=idx1, dist2=dist2, idx2=idx2)
     return out
+
+
+# ------------------------------------------------------------------- the coarse alignment -------------------------------------------------------------------
+def _integer(value, name, lo, hi):
+    if isinstance(value, bool) or not isinstance(value, int) or not lo <= value <= hi:
+        raise RuntimeError(f"`{name}` must be an integer in [{lo}, {hi}]")
+    return value
+
+
+@torch.no_grad()
+def ransac_correspondence(source, target, max_dist=0.2, ransac_n=6, max_iteration=100000, seed=0, with_scaling=True, return_all=False):
+    """Open3D's registration_ransac_based_on_correspondence with TransformationEstimationPointToPoint(True) over the correspondence set (i, i):
+    `source`, `target` float64 [N,3] on the GPU, already paired.  Hypothesis h = 0 .. max_iteration - 1 draws `ransac_n` distinct pairs from
+    the counter-based generator of include/radegs.h (a function of seed, h and the draw alone), fits Eigen's umeyama to them, moves all N
+    pairs and counts d < max_dist; the best is the largest count, then the smallest sqrt(sumsq / count), then the smallest h.  ALL hypotheses
+    are evaluated (Open3D stops early by a confidence estimate, and its draws are unseeded): two runs give the same bits.  Returns a dict:
+    transformation (numpy 4x4), fitness (count / N), inlier_rmse, hypothesis (-1 when no hypothesis has an inlier: the identity, fitness 0),
+    count; with `return_all` also counts int32 [max_iteration] and sumsq float64 [max_iteration] on the GPU."""
+    max_dist = gh.positive(max_dist, "max_dist")
+    ransac_n = _integer(ransac_n, "ransac_n", eval_io.RANSAC_MIN_N, eval_io.RANSAC_MAX_N)
+    K = _integer(max_iteration, "max_iteration", 1, 2 ** 31 - 1)
+    seed = _integer(seed, "seed", 0, 2 ** 64 - 1)
+    if with_scaling is not True:
+        raise RuntimeError("`with_scaling` must be True: the trajectory alignment estimates a similarity (TransformationEstimationPointToPoint(True))")
+    src, tgt = gh.points(source, "source"), gh.points(target, "target")
+    if src.device != tgt.device or src.shape != tgt.shape:
+        raise RuntimeError("`source` and `target` must be paired: the same shape on the same device")
+    N, dev = src.shape[0], src.device
+    if N < ransac_n:
+        raise RuntimeError(f"{N} pairs are fewer than `ransac_n` = {ransac_n}")
+    if N >= 2 ** 31:
+        gh.check(gh.ERR_TOO_LARGE, "ransac_correspondence")
+    gh.finite(src, "source")
+    gh.finite(tgt, "target")
+    counts = torch.empty(K, dtype=torch.int32, device=dev)
+    sumsq = torch.empty(K, dtype=torch.float64, device=dev)
+    out = torch.empty(15, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        gh.check(_lib().radegs_evalio_ransac(N, _C._ptr(src), _C._ptr(tgt), max_dist, ransac_n, K, seed, _C._ptr(counts), _C._ptr(sumsq), _C._ptr(out),
+                                             _C._stream(dev)), "radegs_evalio_ransac")
+    o = out.cpu().numpy()                              # the one host read
+    T = np.eye(4)
+    T[:3] = o[:12].reshape(3, 4)
+    count = int(o[12])
+    res = dict(transformation=T, fitness=count / N, inlier_rmse=math.sqrt(o[13] / count) if count else 0.0, hypothesis=int(o[14]), count=count)
+    if return_all:
+        res.update(counts=counts, sumsq=sumsq)
+    return res
+
+
+def _device(device):
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"tnt_eval runs on the GPU only, got device `{device}`")
+    return torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
+
+
+def _centres(traj):
+    """convert_trajectory_to_pointcloud: the camera centres pose[:3, 3] of [B,4,4] poses (or of a list of CameraPose-like objects / 4x4s)"""
+    if not isinstance(traj, np.ndarray):
+        traj = np.array([np.asarray(getattr(p, "pose", p), dtype=np.float64) for p in traj], dtype=np.float64).reshape(-1, 4, 4)
+    if traj.ndim != 3 or traj.shape[1:] != (4, 4):
+        raise RuntimeError(f"a trajectory must be a stack of 4x4 poses, got shape {traj.shape}")
+    return np.ascontiguousarray(traj[:, :3, 3], dtype=np.float64)
+
+
+@torch.no_grad()
+def trajectory_alignment(map_file, traj_to_register, gt_traj_col, gt_trans, seed=0, device="cuda"):
+    """registration.py:66-110: the similarity that takes the camera centres of `traj_to_register` onto those of `gt_traj_col` moved by
+    `gt_trans` (4x4 or None), pose i paired with pose i.  Trajectories are [B,4,4] arrays (eval_io.read_trajectory's) or lists of poses.
+    With more than 1600 poses and a `map_file`, the sparse trajectory of eval_io.gen_sparse_trajectory is registered.  Returns numpy 4x4."""
+    ref = _centres(gt_traj_col)
+    m = _matrix(gt_trans, "gt_trans")
+    est_traj = traj_to_register if isinstance(traj_to_register, np.ndarray) else np.array(
+        [np.asarray(getattr(p, "pose", p), dtype=np.float64) for p in traj_to_register], dtype=np.float64).reshape(-1, 4, 4)
+    if len(est_traj) > 1600 and map_file is not None:
+        est_traj = eval_io.gen_sparse_trajectory(eval_io.read_mapping(map_file)[2], est_traj)
+    est = _centres(est_traj)
+    if est.shape != ref.shape:
+        raise RuntimeError(f"{est.shape[0]} poses to register against {ref.shape[0]} reference poses: pose i is paired with pose i")
+    dev = _device(device)
+    ref_d = transform_points(torch.from_numpy(ref).to(dev), m)
+    return ransac_correspondence(torch.from_numpy(est).to(dev), ref_d, 0.2, 6, 100000, seed=seed)["transformation"]
+
+
+# ------------------------------------------------------------------------- from paths to the scores -------------------------------------------------------------------------
+SCENES_TAU = {"Barn": 0.01, "Caterpillar": 0.005, "Church": 0.025, "Courthouse": 0.025, "Ignatius": 0.003, "Meetingroom": 0.01,
+              "Truck": 0.005}          # eval_tnt/config.py scenes_tau_dict, restated
+
+
+@torch.no_grad()
+def run_evaluation(dataset_dir, traj_path, ply_path, out_dir=None, seed=0, device="cuda"):
+    """eval_tnt/run.py:58-196 from paths alone: the scene is the directory's name and sets dTau; reads {scene}_COLMAP_SfM.log, {scene}_trans.txt,
+    {scene}.ply, {scene}.json, the trajectory to register (.npy or .log; upstream's .json branch is refused) and the mesh; runs
+    trajectory_alignment (without the mapping file, as upstream, which sets it to None) and evaluate; prints upstream's report.  With
+    `out_dir`, writes {scene}.recall.txt, {scene}.precision.txt and {scene}.prf_tau_plotstr.txt as EvaluateHisto's np.savetxt calls do.
+    Returns evaluate's dict with `scene`, `tau` and `init_transform` added."""
+    scene = os.path.basename(os.path.normpath(dataset_dir))
+    if scene not in SCENES_TAU:
+        raise RuntimeError(f"invalid dataset_dir `{dataset_dir}`: `{scene}` is none of {sorted(SCENES_TAU)}")
+    if traj_path.endswith(".json"):
+        raise RuntimeError(f"{traj_path}: the .json branch of run.py (auto_orient_and_center_poses) is not supported; pass a .npy stack or a .log file")
+    tau = SCENES_TAU[scene]
+    dev = _device(device)
+    print("")
+    print("===========================")
+    print("Evaluating %s" % scene)
+    print("===========================")
+    vertices, faces = eval_io.read_ply_mesh(ply_path, dev)
+    gt = eval_io.read_ply_points(os.path.join(dataset_dir, scene + ".ply"), dev)
+    gt_trans = eval_io.load_transform(os.path.join(dataset_dir, scene + "_trans.txt"))
+    traj = np.load(traj_path) if traj_path.endswith(".npy") else eval_io.read_trajectory(traj_path)[0]
+    gt_traj = eval_io.read_trajectory(os.path.join(dataset_dir, scene + "_COLMAP_SfM.log"))[0]
+    init = trajectory_alignment(None, np.asarray(traj, dtype=np.float64), gt_traj, gt_trans, seed=seed, device=dev)
+    volume = CropVolume.from_json(os.path.join(dataset_dir, scene + ".json"))
+    res = evaluate(vertices, faces, gt, init, volume, tau)
+    res.update(scene=scene, tau=tau, init_transform=init)
+    print("==============================")
+    print("evaluation result : %s" % scene)
+    print("==============================")
+    print("distance tau : %.3f" % tau)
+    print("precision : %.4f" % res["precision"])
+    print("recall : %.4f" % res["recall"])
+    print("f-score : %.4f" % res["fscore"])
+    print("==============================")
+    if out_dir is not None:
+        os.makedirs(out_dir, exist_ok=True)
+        np.savetxt(os.path.join(out_dir, scene + ".recall.txt"), res["cum_target"])
+        np.savetxt(os.path.join(out_dir, scene + ".precision.txt"), res["cum_source"])
+        np.savetxt(os.path.join(out_dir, scene + ".prf_tau_plotstr.txt"), np.array([res["precision"], res["recall"], res["fscore"], tau, 5]))
+    return res
