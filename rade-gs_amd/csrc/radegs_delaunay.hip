@@ -15,6 +15,8 @@
 //          slow_kernel           one WAVE per deferred point (every hull point is one: its cell keeps ghost triangles and must see all N);
 //                                64 candidates at a time against the triangles, a ballot picks those that cut, lane 0 applies them in turn.
 //                                A block of 64 whose bounding box lies outside every triangle's sphere or half-space is skipped whole.
+//          Both kernels answer the cell's second_look: an in-sphere value within its error bound is evaluated once more about the sphere
+//          point nearest the candidate, from the absolute coordinates (rg_delaunay_cell.h, in_sphere_recentred), before it counts.
 //          A finished cell appends its all-real triangles as ascending quadruples (i, a, b, c) to the record arrays at an atomic cursor: the
 //          order of the records is arbitrary, what the sort makes of them is not.
 //   emit   two rg::radix_sort_order_2xu32 (LSD over the four words), heads of runs, rg::inclusive_scan_gather_u32, one oriented row per run.
@@ -67,9 +69,9 @@ inline Grid make_grid(long long N, const double* bounds) {
   const int side = grid_side(N);
   double ext[3], m = 0.0;
   for (int k = 0; k < 3; k++) g.lo[k] = bounds[k], ext[k] = bounds[3 + k] - bounds[k], m = ext[k] > m ? ext[k] : m;
-  g.h = m > 0.0 ? m / side : 1.0;
-  for (int k = 0; k < 3; k++) {
-    const double c = floor(ext[k] / g.h) + 1.0;
+  g.h = m > 0.0 ? m / side : 0.0;      // a box of no extent is one cell of no size: it says nothing about distances, so the fast kernel's
+  for (int k = 0; k < 3; k++) {        // stop test (reach = r h = 0) never holds and every point is the slow kernel's, whatever the units
+    const double c = g.h > 0.0 ? floor(ext[k] / g.h) + 1.0 : 1.0;
     g.dim[k] = c >= (double)side ? side : (c >= 1.0 ? (int)c : 1);
   }
   return g;
@@ -116,7 +118,7 @@ __global__ void __launch_bounds__(256) perturb_kernel(uint32_t N, const double* 
 }
 
 __device__ __forceinline__ int cell_coord(double x, double lo, double h, int dim) {
-  const double t = floor((x - lo) / h);
+  const double t = h > 0.0 ? floor((x - lo) / h) : 0.0;
   return t >= (double)(dim - 1) ? dim - 1 : (t >= 1.0 ? (int)t : 0);     // a point outside the bounds lands in the border cell
 }
 
@@ -186,10 +188,16 @@ __device__ __forceinline__ void write_records(const C& cell, uint32_t j, uint32_
 }
 
 // ---------------------------------------------------------------------------- fast cells ----------------------------------------------------------------------------
+__device__ __forceinline__ V3 point_at(const double* __restrict__ Ps, uint32_t k) { return V3{Ps[3 * (size_t)k], Ps[3 * (size_t)k + 1], Ps[3 * (size_t)k + 2]}; }
+
 struct FastData : NoTriangleData {
   const double* Ps;
   V3 xi;
   __device__ __forceinline__ V3 rel(int, uint32_t g) const { return V3{Ps[3 * (size_t)g] - xi.x, Ps[3 * (size_t)g + 1] - xi.y, Ps[3 * (size_t)g + 2] - xi.z}; }
+  // rare, and kept out of line so that the clip's hot loop keeps its registers
+  __device__ __noinline__ int second_look(uint32_t ia, uint32_t ib, uint32_t ic, uint32_t iq, V3 a, V3 b, V3 c, V3 q) const {
+    return in_sphere_recentred(xi, point_at(Ps, ia), point_at(Ps, ib), point_at(Ps, ic), point_at(Ps, iq), a, b, c, q);
+  }
 };
 typedef Cell<kFastFaces, kFastTris, 64> FastCell;
 
@@ -262,7 +270,12 @@ struct SlowData {
   //   kHalfSpace  a ghost: m.q > 0 for the inward normal m in the first three words
   //   INFINITY    nothing is known (the determinant behind either is too close to its error bound): every candidate takes the predicate
   double* sph;
+  const double* Ps;   // the absolute coordinates, for the second look only
+  V3 xi;
   __device__ __forceinline__ V3 rel(int f, uint32_t) const { return relc[f]; }
+  __device__ __noinline__ int second_look(uint32_t ia, uint32_t ib, uint32_t ic, uint32_t iq, V3 a, V3 b, V3 c, V3 q) const {
+    return in_sphere_recentred(xi, point_at(Ps, ia), point_at(Ps, ib), point_at(Ps, ic), point_at(Ps, iq), a, b, c, q);
+  }
   __device__ __forceinline__ void put_face(int f, V3 q) { relc[f] = q; }
   __device__ __forceinline__ void move_tri(int from, int to) {
 #pragma unroll
@@ -303,11 +316,11 @@ __device__ __forceinline__ bool may_hold_box(const double* __restrict__ sph, int
 
 // Does the candidate at q cut the cell?  The uncertain values it meets are added to `uncertain` only where the answer is no: a candidate
 // that cuts is clipped again by lane 0, which counts them there.
-__device__ __forceinline__ bool cuts_any(const SlowCell& cell, const SlowData& data, V3 q, unsigned& uncertain) {
+__device__ __forceinline__ bool cuts_any(const SlowCell& cell, const SlowData& data, uint32_t k, V3 q, unsigned& uncertain) {
   unsigned met = 0;
   for (int t = 0; t < cell.nt; t++) {
     if (!may_hold_point(data.sph, t, q)) continue;
-    if (cell.tri_inside(t, q, data, met)) return true;
+    if (cell.tri_inside(t, k, q, data, met)) return true;
   }
   uncertain += met;
   return false;
@@ -328,8 +341,8 @@ __global__ void __launch_bounds__(64) slow_kernel(uint32_t N, const double* __re
   for (uint32_t d = blockIdx.x; d < ndef; d += gridDim.x) {          // uniform over the workgroup, which is one wave
     const uint32_t j = min(deferred[d], N - 1u);
     SlowData data;
-    data.relc = s_rel, data.sph = s_sph;
     const V3 xi = V3{Ps[3 * (size_t)j], Ps[3 * (size_t)j + 1], Ps[3 * (size_t)j + 2]};
+    data.relc = s_rel, data.sph = s_sph, data.Ps = Ps, data.xi = xi;
     SlowCell cell;
     __syncthreads();                                                  // the last point's readers are through
     if (lane == 0) {
@@ -360,7 +373,7 @@ __global__ void __launch_bounds__(64) slow_kernel(uint32_t N, const double* __re
       bool c = false;
       if (k < N && k != j) {
         const V3 q = V3{Ps[3 * (size_t)k], Ps[3 * (size_t)k + 1], Ps[3 * (size_t)k + 2]} - xi;
-        if (dot(q, q) <= r2lim) c = cuts_any(cell, data, q, uncertain);
+        if (dot(q, q) <= r2lim) c = cuts_any(cell, data, k, q, uncertain);
       }
       u64 mask = __ballot(c);
       if (mask == 0ull) continue;                                     // uniform

@@ -24,7 +24,8 @@
 //   s: |a|^2 = a_x a_x + .. is 2 differences, a product and two additions, 5 roundings; times an 8-rounding determinant, 1 more; the sum of
 //   the four terms, 3 more: 17 in all, and as many again at second order for the permanent: kSphere = 20 e.
 // A value whose magnitude is within its bound is UNCERTAIN: it is counted, and the decision taken is "not inside".  On an input with no
-// uncertain value every decision is the exact one, whatever the order of clipping.
+// uncertain value every decision is the exact one, whatever the order of clipping.  An in-sphere value gets a second look about the
+// nearest origin first (in_sphere_recentred), where the kernel can supply absolute coordinates: a decision taken there is exact as well.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -80,18 +81,38 @@ RG_HD double hash_unit(uint64_t seed, uint64_t counter) {
 RG_HD bool opposite_signs(double s, double o) { return (s < 0.0 && o > 0.0) || (s > 0.0 && o < 0.0); }
 RG_HD bool same_signs(double s, double o) { return (s < 0.0 && o < 0.0) || (s > 0.0 && o > 0.0); }
 
-// no ghost
-RG_HD bool in_sphere(V3 a, V3 b, V3 c, V3 q, unsigned& uncertain) {
+// no ghost: 1 inside, 0 not inside, -1 where s or o is within its bound
+RG_HD int in_sphere_sign(V3 a, V3 b, V3 c, V3 q) {
   double pbcq, pacq, pabq, pabc;
   const double dbcq = det3(b, c, q, pbcq), dacq = det3(a, c, q, pacq), dabq = det3(a, b, q, pabq), o = det3(a, b, c, pabc);
   const double la = dot(a, a), lb = dot(b, b), lc = dot(c, c), lq = dot(q, q);
   const double s = ((lb * dacq - la * dbcq) - lc * dabq) + lq * o;
   const double ps = ((lb * pacq + la * pbcq) + lc * pabq) + lq * pabc;
-  if (fabs(s) <= kSphere * ps || fabs(o) <= kDet3 * pabc) {
-    uncertain++;
-    return false;
-  }
-  return opposite_signs(s, o);
+  if (fabs(s) <= kSphere * ps || fabs(o) <= kDet3 * pabc) return -1;
+  return opposite_signs(s, o) ? 1 : 0;
+}
+RG_HD bool in_sphere(V3 a, V3 b, V3 c, V3 q, unsigned& uncertain) {
+  const int r = in_sphere_sign(a, b, c, q);
+  if (r < 0) uncertain++;
+  return r > 0;
+}
+
+// The second look at an uncertain in-sphere value: the same predicate about another origin.  "q inside the sphere through four points" does
+// not care which of the four the coordinates are relative to (exchanging two of them changes the sign of s and of o), but the bound does:
+// every monomial of s holds one coordinate of q - origin, so with the origin at the sphere point NEAREST q the permanent, and the bound
+// with it, shrinks by |q - nearest| / |q - x_i|.  That is the case of a candidate next to a member of the triangle -- a point listed twice
+// and parted only by the jitter, two corners of neighbouring boxes a hair apart: q is then nearly ON the sphere, s is of the order of
+// o |q - c| R, and about x_i it drowns in 20 e times a permanent of order |q|^2 |a| |b| |c|.  The differences must be taken from the
+// ABSOLUTE coordinates, one rounding each as the bound assumes: a - c formed from the relative a and c would carry x_i's roundings, which
+// are of the size of the value sought.  xi, xa, xb, xc, xq absolute; a, b, c, q relative to xi (only to find the nearest).  -1: the origin
+// was the nearest already, or the value is within its bound there too.
+RG_HD int in_sphere_recentred(V3 xi, V3 xa, V3 xb, V3 xc, V3 xq, V3 a, V3 b, V3 c, V3 q) {
+  const V3 qa = q - a, qb = q - b, qc = q - c;
+  const double d0 = dot(q, q), da = dot(qa, qa), db = dot(qb, qb), dc = dot(qc, qc);
+  if (d0 <= da && d0 <= db && d0 <= dc) return -1;
+  if (da <= db && da <= dc) return in_sphere_sign(xi - xa, xb - xa, xc - xa, xq - xa);
+  if (db <= dc) return in_sphere_sign(xa - xb, xi - xb, xc - xb, xq - xb);
+  return in_sphere_sign(xa - xc, xb - xc, xi - xc, xq - xc);
 }
 
 // one to three ghosts: the half-space through x_i with normal n = u x v on the side of d
@@ -156,7 +177,10 @@ RG_HD double circumsphere(V3 a, V3 b, V3 c, V3& centre) {
 //   V3   rel(int f, uint32_t id)                      relative coordinates of real face f (generator id)
 //   void put_face(int f, V3 q)                        face f was taken by the candidate at q
 //   void move_tri(int from, int to), void new_tri(int t, ..)   per-triangle data follows the triangle list
+//   int  second_look(ia, ib, ic, iq, a, b, c, q)      an uncertain in-sphere value of generators ia, ib, ic against iq once more, from
+//                                                     absolute coordinates (in_sphere_recentred); -1 where the kernel has none
 struct NoTriangleData {
+  RG_HD int second_look(uint32_t, uint32_t, uint32_t, uint32_t, V3, V3, V3, V3) const { return -1; }
   RG_HD void put_face(int, V3) {}
   RG_HD void move_tri(int, int) {}
   RG_HD void new_tri(int, V3, bool, V3, bool, V3, bool) {}
@@ -195,11 +219,16 @@ struct Cell {
     return ghost ? ghost_dir(g - N) : data.rel(f, g);
   }
 
+  // is the candidate `pid` at q inside triangle t?  An in-sphere value within its bound gets the kernel's second look before it counts.
   template <class Data>
-  RG_HD bool tri_inside(int t, V3 q, const Data& data, unsigned& uncertain) const {
+  RG_HD bool tri_inside(int t, uint32_t pid, V3 q, const Data& data, unsigned& uncertain) const {
     bool g0, g1, g2;
     const V3 p0 = member(corner(t, 0), data, g0), p1 = member(corner(t, 1), data, g1), p2 = member(corner(t, 2), data, g2);
-    return inside(p0, g0, p1, g1, p2, g2, q, uncertain);
+    if (g0 || g1 || g2) return inside(p0, g0, p1, g1, p2, g2, q, uncertain);
+    int r = in_sphere_sign(p0, p1, p2, q);
+    if (r < 0) r = data.second_look(id(corner(t, 0)), id(corner(t, 1)), id(corner(t, 2)), pid, p0, p1, p2, q);
+    if (r < 0) uncertain++;
+    return r > 0;
   }
 
   // an edge met twice is interior to the hole: the two meetings cancel
@@ -234,7 +263,7 @@ struct Cell {
     ne = 0;
     int t = 0;
     while (t < nt) {
-      if (!tri_inside(t, q, data, uncertain)) {
+      if (!tri_inside(t, pid, q, data, uncertain)) {
         t++;
         continue;
       }

@@ -137,7 +137,7 @@ def triangulate(points, jitter=1e-9, seed=0, return_info=False):
     the ascending index quadruple with the last two exchanged where needed to make it positively oriented (float64 det[b-a, c-a, d-a] > 0
     on perturbed(points, jitter, seed)); rows are unique and in lexicographic order of their ascending quadruple; two calls give the same
     bits.  With `return_info` also a dict: `tets`; `inconsistent`, the distinct tetrahedra not found by exactly four cells; `uncertain`, the
-    predicate values within the forward error bound of their evaluation; `deferred`, the points the one-wave-per-point kernel finished;
+    predicate values within the forward error bound of their evaluation (an in-sphere value: of its second, about the nearest origin, too); `deferred`, the points the one-wave-per-point kernel finished;
     `overflow`, the cells too large even for that one; `retries`.  An inconsistent result is tried again with seed + 1 and ten times the
     jitter, at most twice, and then raises; with jitter = 0 nothing is tried again.  jitter = 0 is the caller's statement that the points
     are in general position: any uncertain predicate refutes it -- a tie was met and decided by the order of clipping, so whether the cells
