@@ -375,6 +375,26 @@ int radegs_filter3d_backward(int P, const float* scaling_raw, const float* opaci
 int radegs_compute_filter3d(int P, const float* xyz, int ncam, const float* cameras16, float focal_length, float* scratch_distance,
                             unsigned* scratch_max, float* filter_3D, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Model activations: the whole pre-step of render() -- raw parameters in, the rasterizer's four
+ * per-Gaussian inputs out -- and its backward, one launch each, nothing read back, work enqueued on `stream`.
+ *   shs[P,K+1,3]   = cat(f_dc[P,1,3], f_rest[P,K,3]) along dim 1         (the bytes torch.cat writes)
+ *   rotations[P,4] = x / fmaxf(sqrtf(((x0^2 + x1^2) + x2^2) + x3^2), 1e-12f)   one rounding per operation, nothing fused
+ *   scales, opacity: the bits radegs_filter3d_forward gives on the same inputs
+ * backward: each cotangent may be NULL (= zero cotangent; the gradients it alone feeds are written as exact zeros).
+ *   g_f_dc / g_f_rest = the two slices of g_shs;  g_scaling_raw / g_opacity_raw: the bits of radegs_filter3d_backward;
+ *   g_rotation_raw = (g - y (g.y)) / n for n >= 1e-12f, with g.y = ((g0 y0 + g1 y1) + g2 y2) + g3 y3, else g / 1e-12f.
+ * 0 <= K <= RADEGS_MODELIO_MAX_REST; f_rest / g_f_rest are NULL iff K == 0.  P == 0 is legal and launches nothing.
+ * f_dc, f_rest, rotation_raw, shs, rotations, g_shs, g_rotations, g_f_dc, g_f_rest and g_rotation_raw are 16-byte
+ * aligned.  Anything else returns RADEGS_ERR_INVALID_ARG before a launch.
+ * --------------------------------------------------------------------------------------------------------------- */
+int radegs_model_activate_forward(int P, int K, const float* f_dc, const float* f_rest, const float* rotation_raw, const float* scaling_raw,
+                                  const float* opacity_raw, const float* filter_3D, float* shs, float* rotations, float* scales, float* opacity,
+                                  void* stream);
+int radegs_model_activate_backward(int P, int K, const float* rotation_raw, const float* scaling_raw, const float* opacity_raw, const float* filter_3D,
+                                   const float* g_shs, const float* g_rotations, const float* g_scales, const float* g_opacity, float* g_f_dc,
+                                   float* g_f_rest, float* g_rotation_raw, float* g_scaling_raw, float* g_opacity_raw, void* stream);
+
 
 /* ---------------------------------------------------------------------------------------------------------------
  * The photometric loss that closes every training iteration:

@@ -46,6 +46,7 @@ UNITS = {
                        "rg_layout.h", "rg_prims.h", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
     "radegs_normals": ["radegs_normals.hip", "rg_reduce.h", os.path.join("..", "..", "include", "radegs.h")],
     "radegs_filter3d": ["radegs_filter3d.hip", os.path.join("..", "..", "include", "radegs.h")],
+    "radegs_activate": ["radegs_activate.hip", "rg_activate.h", os.path.join("..", "..", "include", "radegs.h")],
     "radegs_photometric": ["radegs_photometric.hip", "rg_reduce.h", os.path.join("..", "..", "include", "radegs.h")],
     "radegs_adam": ["radegs_adam.hip", os.path.join("..", "..", "include", "radegs.h")],
     "radegs_densify": ["radegs_densify.hip", "rg_prims.h", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
@@ -74,7 +75,8 @@ UNITS = {
 # `on` contracts within the source's own expressions only (this also changes which products of compute_3D_filter's kernels fuse: same
 # formulas, last-bit differences).  radegs_photometric calls exp on the host only; radegs_appearance still calls expf under `fast`: known,
 # not covered by a test of this kind yet.
-UNIT_FLAGS = {"radegs_normals": ["-ffp-contract=fast"], "radegs_filter3d": ["-ffp-contract=on"],
+# radegs_activate restates radegs_filter3d's scale / opacity expressions (csrc/rg_activate.h) and is held to its bits: the same flag.
+UNIT_FLAGS = {"radegs_normals": ["-ffp-contract=fast"], "radegs_filter3d": ["-ffp-contract=on"], "radegs_activate": ["-ffp-contract=on"],
               "radegs_photometric": ["-ffp-contract=fast"], "radegs_appearance": ["-ffp-contract=fast"]}
 
 

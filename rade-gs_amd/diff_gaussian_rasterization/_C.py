@@ -89,6 +89,7 @@ EXPORTED_SYMBOLS = ("radegs_forward", "radegs_backward", "radegs_backward_ordere
                     "radegs_normals_forward", "radegs_normals_backward", "radegs_normal_loss_scratch_bytes",
                     "radegs_normal_loss_forward", "radegs_normal_loss_backward", "radegs_normals_last_error",
                     "radegs_filter3d_forward", "radegs_filter3d_backward", "radegs_compute_filter3d",
+                    "radegs_model_activate_forward", "radegs_model_activate_backward",
                     "radegs_photometric_scratch_bytes",
                     "radegs_photometric_forward", "radegs_photometric_backward", "radegs_adam_step", "radegs_knn_scratch_bytes",
                     "radegs_knn_mean_dist2", "radegs_densify_stats", "radegs_densify_stats_reduced", "radegs_densify_plan_bytes",

@@ -23,6 +23,8 @@ _SIGNATURES = {
     "radegs_filter3d_forward": (_I, [_I] + [_VP] * 6),
     "radegs_filter3d_backward": (_I, [_I] + [_VP] * 8),
     "radegs_compute_filter3d": (_I, [_I, _VP, _I, _VP, _FL, _VP, _VP, _VP, _VP]),
+    "radegs_model_activate_forward": (_I, [_I, _I] + [_VP] * 11),
+    "radegs_model_activate_backward": (_I, [_I, _I] + [_VP] * 14),
     "radegs_densify_stats": (_I, [_I] + [_VP] * 9),
     "radegs_densify_stats_reduced": (_I, [_I] + [_VP] * 8),
     "radegs_densify_plan_bytes": (ctypes.c_size_t, [_I]),
@@ -79,6 +81,114 @@ def scaling_n_opacity_with_3D_filter(scaling_raw, opacity_raw, filter_3D):
     """(scales[P,3], opacity[P,1]) = GaussianModel.get_scaling_n_opacity_with_3D_filter evaluated on the raw parameters
     `_scaling` (log-space), `_opacity` (logit) and the `filter_3D` buffer.  Differentiable w.r.t. the two parameters."""
     return _ScalingOpacity3DFilter.apply(scaling_raw, opacity_raw, filter_3D)
+
+
+def _prep3(t, name, cols):
+    """`t` as the activation kernels address it: float32 (P, K, 3) with K == `cols` (any K when None), contiguous and 16-byte aligned"""
+    _C._require_gpu(t, name)
+    if t.dtype != torch.float32 or t.dim() != 3 or t.size(2) != 3 or (cols is not None and t.size(1) != cols):
+        raise RuntimeError(f"`{name}` must be float32 of shape (P,{'K' if cols is None else cols},3)")
+    return _aligned(t.contiguous())
+
+
+def _aligned(t):
+    """a contiguous tensor whose first byte lies on a 16-byte boundary (a view into the middle of a buffer is copied)"""
+    return t.clone() if t.numel() and t.data_ptr() % 16 else t
+
+
+class _ModelActivations(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, f_dc, f_rest, rotation_raw, scaling_raw, opacity_raw, filter_3D):
+        out = model_activations_forward(f_dc, f_rest, rotation_raw, scaling_raw, opacity_raw, filter_3D)
+        ctx.save_for_backward(rotation_raw, scaling_raw, opacity_raw, filter_3D)
+        ctx.K = f_rest.size(1)
+        ctx.set_materialize_grads(False)     # an output that nothing downstream uses arrives as None, not as a tensor of zeros
+        return out
+
+    @staticmethod
+    def backward(ctx, g_shs, g_rotations, g_scales, g_opacity):
+        rot, sc, op, f3 = ctx.saved_tensors
+        if g_shs is None and g_rotations is None and g_scales is None and g_opacity is None:
+            return None, None, None, None, None, None
+        return model_activations_backward(ctx.K, rot, sc, op, f3, g_shs, g_rotations, g_scales, g_opacity) + (None,)
+
+
+def _param(t, name, tail):
+    """a raw parameter as the activation kernels address it: on the GPU, float32, (P,) + tail, contiguous; nothing is copied on the way in"""
+    _C._require_gpu(t, name)
+    if t.dtype != torch.float32 or t.dim() != len(tail) + 1 or any(x is not None and x != y for x, y in zip(tail, t.shape[1:])):
+        raise RuntimeError(f"`{name}` must be float32 of shape (P,{','.join('K' if x is None else str(x) for x in tail)})")
+    if not t.is_contiguous():
+        raise RuntimeError(f"`{name}` must be a contiguous {t.dtype} GPU tensor with {t.size(0)} rows")
+    return t
+
+
+def _outputs(out, shapes, dev):
+    if out is None:
+        return tuple(torch.empty(s, dtype=torch.float32, device=dev) for s in shapes)
+    out = tuple(out)
+    if len(out) != len(shapes):
+        raise RuntimeError(f"`out` must hold {len(shapes)} tensors")
+    for t, s in zip(out, shapes):
+        _C._require_gpu(t, "out")
+        if t.dtype != torch.float32 or tuple(t.shape) != s or not t.is_contiguous() or t.device != dev:
+            raise RuntimeError(f"`out` must hold contiguous float32 tensors of shapes {shapes} on the inputs' device")
+    return out
+
+
+def model_activations_forward(f_dc, f_rest, rotation_raw, scaling_raw, opacity_raw, filter_3D, out=None):
+    """radegs_model_activate_forward without autograd: (shs, rotations, scales, opacity).  `out`: four tensors to write into instead of
+    new ones (contiguous, of those shapes; the first two 16-byte aligned)."""
+    dc, rest = _param(f_dc, "_features_dc", (1, 3)), _param(f_rest, "_features_rest", (None, 3))
+    rot, sc = _param(rotation_raw, "_rotation", (4,)), _param(scaling_raw, "_scaling", (3,))
+    op, f3 = _param(opacity_raw, "_opacity", (1,)), _param(filter_3D, "filter_3D", (1,))
+    P, K, dev = dc.size(0), rest.size(1), dc.device
+    if any(t.size(0) != P for t in (rest, rot, sc, op, f3)):
+        raise RuntimeError("_features_dc, _features_rest, _rotation, _scaling, _opacity and filter_3D must have the same number of rows")
+    if any(t.device != dev for t in (rest, rot, sc, op, f3)):
+        raise RuntimeError("_features_dc, _features_rest, _rotation, _scaling, _opacity and filter_3D must be on the same device")
+    dc, rest, rot = _aligned(dc.detach()), _aligned(rest.detach()), _aligned(rot.detach())
+    shs, rotations, scales, opacity = _outputs(out, ((P, K + 1, 3), (P, 4), (P, 3), (P, 1)), dev)
+    with torch.cuda.device(dev):
+        rc = _lib().radegs_model_activate_forward(P, K, _C._ptr(dc), _C._ptr(rest) if K else None, _C._ptr(rot), _C._ptr(sc), _C._ptr(op), _C._ptr(f3),
+                                                  _C._ptr(shs), _C._ptr(rotations), _C._ptr(scales), _C._ptr(opacity), _C._stream(dev))
+    if rc != 0:
+        raise RuntimeError(f"radegs_model_activate_forward failed ({rc})")
+    return shs, rotations, scales, opacity
+
+
+def model_activations_backward(K, rotation_raw, scaling_raw, opacity_raw, filter_3D, g_shs, g_rotations, g_scales, g_opacity, out=None):
+    """radegs_model_activate_backward: the gradients (g_f_dc [P,1,3], g_f_rest [P,K,3], g_rotation_raw, g_scaling_raw, g_opacity_raw) of the
+    cotangents of model_activations' four outputs, each of which may be None (= zero).  `out`: five tensors to write into instead of new
+    ones (contiguous, of those shapes; the first three 16-byte aligned)."""
+    rot = _aligned(_param(rotation_raw, "_rotation", (4,)).detach())
+    sc, op, f3 = _param(scaling_raw, "_scaling", (3,)), _param(opacity_raw, "_opacity", (1,)), _param(filter_3D, "filter_3D", (1,))
+    P, dev = rot.size(0), rot.device
+    if sc.size(0) != P or op.size(0) != P or f3.size(0) != P:
+        raise RuntimeError("_rotation, _scaling, _opacity and filter_3D must have the same number of rows")
+    gsh = None if g_shs is None else _prep3(g_shs, "grad of shs", K + 1)
+    gr = None if g_rotations is None else _aligned(_prep(g_rotations, "grad of rotations", 4))
+    gs = None if g_scales is None else _prep(g_scales, "grad of scales", 3)
+    go = None if g_opacity is None else _prep(g_opacity, "grad of opacity", 1)
+    for g, n in ((gsh, "shs"), (gr, "rotations"), (gs, "scales"), (go, "opacity")):
+        if g is not None and g.size(0) != P:
+            raise RuntimeError(f"grad of {n} must have {P} rows")
+    out = _outputs(out, ((P, 1, 3), (P, K, 3), (P, 4), (P, 3), (P, 1)), dev)
+    g_dc, g_rest, g_rot, g_sc, g_op = out
+    with torch.cuda.device(dev):
+        rc = _lib().radegs_model_activate_backward(P, K, _C._ptr(rot), _C._ptr(sc), _C._ptr(op), _C._ptr(f3), _C._ptr(gsh), _C._ptr(gr), _C._ptr(gs),
+                                                   _C._ptr(go), _C._ptr(g_dc), _C._ptr(g_rest) if K else None, _C._ptr(g_rot), _C._ptr(g_sc), _C._ptr(g_op),
+                                                   _C._stream(dev))
+    if rc != 0:
+        raise RuntimeError(f"radegs_model_activate_backward failed ({rc})")
+    return out
+
+
+def model_activations(f_dc, f_rest, rotation_raw, scaling_raw, opacity_raw, filter_3D):
+    """(shs[P,K+1,3], rotations[P,4], scales[P,3], opacity[P,1]) = (GaussianModel.get_features, get_rotation,
+    *get_scaling_n_opacity_with_3D_filter) from the raw parameters: everything render() does between the model and the rasterizer, one
+    launch forward and one backward (csrc/radegs_activate.hip).  Differentiable w.r.t. the five parameters; `filter_3D` carries none."""
+    return _ModelActivations.apply(f_dc, f_rest, rotation_raw, scaling_raw, opacity_raw, filter_3D)
 
 
 @torch.no_grad()

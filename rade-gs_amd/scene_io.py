@@ -623,6 +623,14 @@ class Scene:
         return self.test_cameras[scale]
 
 
+def __getattr__(name):
+    """`GaussianModel`, imported on first use: `from scene import Scene, GaussianModel` works after install() as it does upstream"""
+    if name == "GaussianModel":
+        from gaussian_model import GaussianModel
+        return GaussianModel
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 def install():
     """Registers this module as `scene`, so that upstream's `from scene import Scene` resolves to it (as lpipsPyTorch/ and tetranerf/ shadow
     upstream's names).  Opt-in: nothing calls it."""
