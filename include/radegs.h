@@ -1130,6 +1130,41 @@ int radegs_evalio_unpack_faces(long long F, int S, const void* buffer, long long
 int radegs_evalio_ransac(long long N, const double* source, const double* target, double max_dist, int ransac_n, long long K, unsigned long long seed,
                          int* counts /* [K] */, double* sumsq /* [K] */, double* out15, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Camera pose refinement (csrc/radegs_pose.hip; the arithmetic is csrc/rg_pose.h, statement for statement, restated in
+ * NumPy by tests/pose_restatement.py).  Conventions as above: device pointers, 0 or a negative RADEGS_ERR_*, work
+ * enqueued on `stream`, nothing read back, arguments refused before the first HIP call.  fp64, one rounding per
+ * operation in the order rg_pose.h writes, IEEE divide and sqrt.
+ *
+ * radegs_pose_gradient: the gradient of the loss with respect to the camera pose, from the gradients radegs_backward
+ *   returned for means3D [P,3], rotations [P,4] (w, x, y, z) and shs [P,M,3] of the same view (campos [3] and
+ *   viewmatrix [16] are that view's).  out12 = g_xi[6] then g_tau[6], each (translation, rotation):
+ *     xi, world frame:   w2c(xi) = w2c [[Exp(theta), rho], [0, 1]]
+ *     tau, camera frame: Exp(tau) w2c = w2c Exp(xi)
+ *   g_xi = the sum over the Gaussians of rg_pose.h's row in the order of rg_reduce.h's two-stage sum: a function of P
+ *   alone, so two calls give the same bits.  The SH row of a Gaussian is read only where sh_degree > 0 and the three
+ *   DC entries of its dL_dsh row are not all zero.  0 <= sh_degree <= 3, (sh_degree + 1)^2 <= M <= 16.  P = 0 gives
+ *   zeros.  workspace: radegs_pose_gradient_bytes(P) bytes, 8-byte aligned, contents irrelevant before and after.
+ *   The gradient is linear in what the backward returned: with opacity_grad_intended = 0 it inherits the reference's
+ *   argument slip (kernel_size > 0 makes that visible).
+ *
+ * radegs_pose_step: one Adam step on one camera's tau and the retraction master <- Exp(tau) master.
+ *   master [4,4] double, the world-to-camera matrix, row-major and NOT transposed; grad6 = g_tau (double, device);
+ *   exp_avg, exp_avg_sq [6] float; step >= 1 counts this camera's steps, this one included; bias corrections on the
+ *   host in double as radegs_adam_step forms them, lr_translation for tau[0..2], lr_rotation for tau[3..5]; the
+ *   update in fp32 as radegs_adam_step's, from a parameter of 0.  Exp: Rodrigues, series coefficients below
+ *   |theta| = 1e-8, then one Newton step towards the nearest rotation (rg_pose.h::retract).  proj [16] float is the
+ *   camera's projection matrix, stored transposed.  Written in place with vector stores: world_view_transform [16]
+ *   (master transposed, rounded), full_proj_transform [16] (view proj in double, rounded once), camera_center [3].
+ * --------------------------------------------------------------------------------------------------------------- */
+size_t radegs_pose_gradient_bytes(long long P);
+int radegs_pose_gradient(long long P, int M, int sh_degree, const float* means3D, const float* rotations, const float* shs, const float* campos,
+                         const float* viewmatrix, const float* dL_dmeans3D, const float* dL_drotations, const float* dL_dsh, void* workspace,
+                         size_t workspace_bytes, double* out12, void* stream);
+int radegs_pose_step(double* master, const double* grad6, float* exp_avg, float* exp_avg_sq, double step, double lr_translation,
+                     double lr_rotation, double beta1, double beta2, double eps, const float* proj, float* world_view_transform,
+                     float* full_proj_transform, float* camera_center, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

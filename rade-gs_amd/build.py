@@ -68,6 +68,8 @@ UNITS = {
     "radegs_unbounded": ["radegs_unbounded.hip", "rg_mc_tables.h", "rg_prims.h", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
     # default FLAGS: the RANSAC's per-pair decisions are held to tests/evalio_restatement.py, one rounding per operation, IEEE divide / sqrt
     "radegs_evalio": ["radegs_evalio.hip", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
+    # default FLAGS: the pose gradient is held to tests/pose_restatement.py bit for bit, one rounding per fp64 operation, IEEE divide / sqrt
+    "radegs_pose": ["radegs_pose.hip", "rg_pose.h", "rg_reduce.h", os.path.join("..", "..", "include", "radegs.h")],
 }
 # Units outside the rasterizer's decision chain have no bit-exactness contract with the oracle: let them contract to fma.
 # radegs_filter3d calls expf: under `fast` the compiler also contracts INSIDE expf's expansion (x*log2e - round(x*log2e) becomes one fma and

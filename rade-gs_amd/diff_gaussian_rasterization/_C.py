@@ -131,7 +131,9 @@ EXPORTED_SYMBOLS = ("radegs_forward", "radegs_backward", "radegs_backward_ordere
                     # unbounded mesh extraction (bound in unbounded_mesh.py)
                     "radegs_unbounded_fuse", "radegs_unbounded_uncontract", "radegs_densemc_bytes", "radegs_densemc_plan", "radegs_densemc_emit",
                     # evaluation from files (bound in eval_io.py)
-                    "radegs_evalio_unpack_points", "radegs_evalio_unpack_faces", "radegs_evalio_ransac")
+                    "radegs_evalio_unpack_points", "radegs_evalio_unpack_faces", "radegs_evalio_ransac",
+                    # camera pose refinement (prototypes below, called from pose_opt.py)
+                    "radegs_pose_gradient_bytes", "radegs_pose_gradient", "radegs_pose_step")
 
 _lib = None
 # test hook: when True, the per-Gaussian accumulation scratch of the last backward is kept in LAST_ACC
@@ -256,6 +258,9 @@ _SIGNATURES = {
     "radegs_profile_num_stages": (_I, []),
     "radegs_profile_stage_name": (ctypes.c_char_p, [_I]),
     "radegs_profile_collect": (_I, [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(_I), _I]),
+    "radegs_pose_gradient_bytes": (_SZ, [ctypes.c_longlong]),
+    "radegs_pose_gradient": (_I, [ctypes.c_longlong, _I, _I] + [_VP] * 9 + [_SZ, _VP, _VP]),
+    "radegs_pose_step": (_I, [_VP] * 4 + [ctypes.c_double] * 6 + [_VP] * 5),
 }
 _bound = set()   # id() of the tables (module-level dicts, never freed) already set on the library
 _BIND_LOCK = threading.Lock()

@@ -58,15 +58,33 @@ def _screenspace_points(pc):
     return pts
 
 
-def render(viewpoint_camera, pc, pipe, bg_color, kernel_size, scaling_modifier=1.0, require_coord=True, require_depth=True, fused=None):
+def _refuse_for_pose(pipe):
+    """The pose gradient is formed from the cotangents of means3D, rotations and shs (pose_opt.tap).  A precomputed covariance or colour
+    depends on the pose along a path that does not pass through those three, so its part of the gradient would be missing."""
+    for flag, what in (("compute_cov3D_python", "the covariance is precomputed (cov3D_precomp): its rotation with the camera does not pass through "
+                                                 "`rotations`"),
+                       ("convert_SHs_python", "the colours are precomputed (colors_precomp / override_color): their view direction does not pass "
+                                              "through `shs`")):
+        if getattr(pipe, flag, False):
+            raise RuntimeError(f"render(pose=...): pipe.{flag} is set and {what}; the pose gradient would be incomplete")
+
+
+def render(viewpoint_camera, pc, pipe, bg_color, kernel_size, scaling_modifier=1.0, require_coord=True, require_depth=True, fused=None, pose=None):
     """Upstream's ten keys: render, mask, expected_coord, median_coord, expected_depth, median_depth, viewspace_points, visibility_filter,
-    radii, normal.  `bg_color` must be on the GPU."""
+    radii, normal.  `bg_color` must be on the GPU.  `pose`: a pose_opt.CameraPoses that holds this camera -- its delta receives the
+    gradient of the camera's pose in the backward; None: every line executes as it did before the argument existed."""
+    if pose is not None:
+        _refuse_for_pose(pipe)
     rasterizer = GaussianRasterizer(raster_settings=_settings(viewpoint_camera, pc, pipe, bg_color, kernel_size, scaling_modifier, require_coord,
                                                               require_depth))
     means2D = _screenspace_points(pc)
     shs, rotations, scales, opacity = pc.activations(fused)
+    means3D = pc.get_xyz
+    if pose is not None:
+        import pose_opt
+        means3D, rotations, shs = pose_opt.tap(means3D, rotations, shs, pose.delta(viewpoint_camera.uid), viewpoint_camera, pc.active_sh_degree)
     image, radii, expected_coord, median_coord, expected_depth, median_depth, alpha, normal = rasterizer(
-        means3D=pc.get_xyz, means2D=means2D, shs=shs, colors_precomp=None, opacities=opacity, scales=scales, rotations=rotations,
+        means3D=means3D, means2D=means2D, shs=shs, colors_precomp=None, opacities=opacity, scales=scales, rotations=rotations,
         cov3D_precomp=None)
     return {"render": image, "mask": alpha, "expected_coord": expected_coord, "median_coord": median_coord, "expected_depth": expected_depth,
             "median_depth": median_depth, "viewspace_points": means2D, "visibility_filter": radii > 0, "radii": radii, "normal": normal}

@@ -78,10 +78,26 @@ def training_report(iteration, Ll1, loss, normal_loss, testing_iterations, scene
     return record
 
 
-def training(dataset, opt, pipe, testing_iterations, saving_iterations, checkpoint_iterations, checkpoint, debug_from, view_sampler=None):
+def write_refined_cameras(scene, cameras):
+    """<model_path>/cameras_refined.json, beside upstream's cameras.json and with its keys, from the cameras' host-side R / T"""
+    from scene_io import fov2focal
+    records = []
+    for id, cam in enumerate(cameras):
+        Rt = np.zeros((4, 4))
+        Rt[:3, :3], Rt[:3, 3], Rt[3, 3] = np.asarray(cam.R).transpose(), cam.T, 1.0
+        C2W = np.linalg.inv(Rt)
+        records.append({"id": id, "img_name": cam.image_name, "width": int(cam.image_width), "height": int(cam.image_height), "position": C2W[:3, 3].tolist(),
+                        "rotation": [x.tolist() for x in C2W[:3, :3]], "fy": fov2focal(cam.FoVy, cam.image_height), "fx": fov2focal(cam.FoVx, cam.image_width)})
+    with open(os.path.join(scene.model_path, "cameras_refined.json"), "w") as f:
+        json.dump(records, f)
+
+
+def training(dataset, opt, pipe, testing_iterations, saving_iterations, checkpoint_iterations, checkpoint, debug_from, view_sampler=None, pose_args=None):
     """train.py:61-214.  view_sampler(iteration, n_train) -> index into the training cameras replaces upstream's pop from a shuffled stack
-    (which draws from Python's `random`) when given.  Returns {"iteration": the last one run, "losses": [loss per iteration],
-    "report": [training_report's records], "gaussians", "scene"}."""
+    (which draws from Python's `random`) when given.  pose_args (optimize_poses, pose_lr_translation, pose_lr_rotation, pose_from_iter):
+    refine the training cameras' poses along with the Gaussians (pose_opt.py); None or optimize_poses off: the loop is upstream's.
+    Returns {"iteration": the last one run, "losses": [loss per iteration], "report": [training_report's records], "gaussians", "scene",
+    "poses": the CameraPoses or None}."""
     import graphics_utils
     import loss_utils
     from gaussian_model import GaussianModel
@@ -92,9 +108,22 @@ def training(dataset, opt, pipe, testing_iterations, saving_iterations, checkpoi
     gaussians = GaussianModel(dataset.sh_degree)
     scene = Scene(dataset, gaussians)
     gaussians.training_setup(opt)
+    poses = None
+    if pose_args is not None and pose_args.optimize_poses:
+        import pose_opt
+        from diff_gaussian_rasterization import _C
+        poses = pose_opt.CameraPoses(scene.getTrainCameras(), pose_args.pose_lr_translation, pose_args.pose_lr_rotation)
+        if dataset.kernel_size > 0 and not _C.OPACITY_GRAD_INTENDED:
+            # the pose gradient is linear in what the backward returns and inherits the reference's argument slip, which a kernel_size above
+            # zero makes large: this run takes the intended derivative
+            _C.OPACITY_GRAD_INTENDED = True
+            print("--optimize_poses with kernel_size > 0: switching the backward to opacity_grad_intended")
     if checkpoint:
-        (model_params, first_iter) = torch.load(checkpoint, weights_only=False)
+        loaded = torch.load(checkpoint, weights_only=False)
+        (model_params, first_iter) = loaded[0], loaded[1]
         gaussians.restore(model_params, opt)
+        if poses is not None and len(loaded) > 2:
+            poses.load_state_dict(loaded[2])
     bg_color = [1, 1, 1] if dataset.white_background else [0, 0, 0]
     background = torch.tensor(bg_color, dtype=torch.float32, device="cuda")
     kernel_size = dataset.kernel_size
@@ -129,8 +158,13 @@ def training(dataset, opt, pipe, testing_iterations, saving_iterations, checkpoi
             pipe.debug = True
 
         reg_kick_on = iteration >= opt.regularization_from_iter
-        render_pkg = render(viewpoint_cam, gaussians, pipe, background, kernel_size, require_coord=require_coord and reg_kick_on,
-                            require_depth=require_depth and reg_kick_on)
+        pose_on = poses is not None and iteration >= pose_args.pose_from_iter
+        if pose_on:
+            render_pkg = render(viewpoint_cam, gaussians, pipe, background, kernel_size, require_coord=require_coord and reg_kick_on,
+                                require_depth=require_depth and reg_kick_on, pose=poses)
+        else:
+            render_pkg = render(viewpoint_cam, gaussians, pipe, background, kernel_size, require_coord=require_coord and reg_kick_on,
+                                require_depth=require_depth and reg_kick_on)
         rendered_image, viewspace_point_tensor, visibility_filter, radii = (render_pkg["render"], render_pkg["viewspace_points"],
                                                                             render_pkg["visibility_filter"], render_pkg["radii"])
         gt_image = viewpoint_cam.original_image.cuda()
@@ -168,6 +202,9 @@ def training(dataset, opt, pipe, testing_iterations, saving_iterations, checkpoi
             if iteration in saving_iterations:
                 print("\n[ITER {}] Saving Gaussians".format(iteration))
                 scene.save(iteration)
+                if poses is not None:
+                    poses.sync()
+                    write_refined_cameras(scene, poses.cameras)
 
             # densification
             if iteration < opt.densify_until_iter:
@@ -180,6 +217,8 @@ def training(dataset, opt, pipe, testing_iterations, saving_iterations, checkpoi
                     if dataset.disable_filter3D:
                         gaussians.reset_3D_filter()
                     else:
+                        if poses is not None:
+                            poses.sync()
                         gaussians.compute_3D_filter(cameras=trainCameras)
 
                 if iteration % opt.opacity_reset_interval == 0 or (dataset.white_background and iteration == opt.densify_from_iter):
@@ -187,16 +226,27 @@ def training(dataset, opt, pipe, testing_iterations, saving_iterations, checkpoi
 
             if iteration % 100 == 0 and iteration > opt.densify_until_iter and not dataset.disable_filter3D:
                 if iteration < opt.iterations - 100:     # not at the end of training
+                    if poses is not None:
+                        poses.sync()
                     gaussians.compute_3D_filter(cameras=trainCameras)
 
             if iteration < opt.iterations:
                 gaussians.optimizer.step()
                 gaussians.optimizer.zero_grad(set_to_none=True)
+                if pose_on:
+                    poses.step(viewpoint_cam.uid)
 
             if iteration in checkpoint_iterations:
                 print("\n[ITER {}] Saving Checkpoint".format(iteration))
-                torch.save((gaussians.capture(), iteration), scene.model_path + "/chkpnt" + str(iteration) + ".pth")
-    return {"iteration": iteration, "losses": losses, "report": report, "gaussians": gaussians, "scene": scene}
+                if poses is not None:
+                    poses.sync()
+                    torch.save((gaussians.capture(), iteration, poses.state_dict()), scene.model_path + "/chkpnt" + str(iteration) + ".pth")
+                else:
+                    torch.save((gaussians.capture(), iteration), scene.model_path + "/chkpnt" + str(iteration) + ".pth")
+    if poses is not None:
+        poses.sync()
+        write_refined_cameras(scene, poses.cameras)
+    return {"iteration": iteration, "losses": losses, "report": report, "gaussians": gaussians, "scene": scene, "poses": poses}
 
 
 class _Quiet:
@@ -235,6 +285,11 @@ def main(argv=None, view_sampler=None):
     parser.add_argument("--quiet", action="store_true")
     parser.add_argument("--checkpoint_iterations", nargs="+", type=int, default=[15000])
     parser.add_argument("--start_checkpoint", type=str, default=None)
+    # camera pose refinement (pose_opt.py), off by default; the trainer's own flags, not upstream's
+    parser.add_argument("--optimize_poses", action="store_true", default=False)
+    parser.add_argument("--pose_lr_translation", type=float, default=1e-4)
+    parser.add_argument("--pose_lr_rotation", type=float, default=1e-4)
+    parser.add_argument("--pose_from_iter", type=int, default=0)
     args = parser.parse_args(sys.argv[1:] if argv is None else argv)
     args.save_iterations.append(args.iterations)
     print("Optimizing " + args.model_path)
@@ -243,7 +298,7 @@ def main(argv=None, view_sampler=None):
     try:
         with torch.autograd.set_detect_anomaly(args.detect_anomaly):
             out = training(lp.extract(args), op.extract(args), pp.extract(args), args.test_iterations, args.save_iterations,
-                           args.checkpoint_iterations, args.start_checkpoint, args.debug_from, view_sampler=view_sampler)
+                           args.checkpoint_iterations, args.start_checkpoint, args.debug_from, view_sampler=view_sampler, pose_args=args)
     finally:
         sys.stdout = stdout
     print("\nTraining complete.")
