@@ -1165,6 +1165,73 @@ int radegs_pose_step(double* master, const double* grad6, float* exp_avg, float*
                      double lr_rotation, double beta1, double beta2, double eps, const float* proj, float* world_view_transform,
                      float* full_proj_transform, float* camera_center, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Mesh simplification: vertex clustering with quadric error (Lindstrom 2000), the step upstream's
+ * users take in Open3D (simplify_vertex_clustering) or MeshLab after post_process_mesh.  Conventions as above: device
+ * pointers, 0 or a negative RADEGS_ERR_*, work enqueued on `stream`, nothing read back, arguments refused before the
+ * first HIP call.  faces int64 [F,3], vertices float64 [V,3], finite; V < 2^31 and F <= 2^30, beyond that
+ * RADEGS_ERR_TOO_LARGE.  Workspaces are 16-byte aligned.  fp64, one rounding per operation in the order written, IEEE
+ * divide and sqrt, no float atomics: two calls give the same bits.  A face with an index outside [0, V) is never used
+ * to address memory: it adds to no quadric and is flagged for removal.
+ *
+ * 1. Cells (radegs_simplify_cells).  o = (ox, oy, oz) and h > 0 finite.  c_a = floor((v_a - o_a) / h) per axis; the
+ *   caller has made sure 0 <= c_a < 2^RADEGS_SIMPLIFY_CELL_BITS (a value outside is clamped to that range, never
+ *   used as it is).  key = cx << 42 | cy << 21 | cz <= max_key, which only sets how many bits are sorted.  The cells
+ *   that hold a vertex are numbered 0..K-1 by ascending key (not Open3D's hash-map order).  Outputs: vertex_cell [V];
+ *   order [V], the vertices by ascending (key, index); cell_start [V + 1], of which K + 1 entries are written: cell k
+ *   is order[cell_start[k] .. cell_start[k + 1]); cell_key [V], K written; *n_cells = K, which the host reads.
+ * 2. Averages (radegs_simplify_vertices).  averages [K,3] and attributes_out [K,A]: per cell and component the sum
+ *   over its members in ascending vertex index, added to 0.0 one by one, divided by their number.
+ * 3. Quadrics (quadric = 1).  Triangle (a, b, c): u = b - a, v = c - a, n = (uy vz - uz vy, uz vx - ux vz,
+ *   ux vy - uy vx), len = sqrt((nx nx + ny ny) + nz nz); unless len is positive and finite the triangle contributes
+ *   nothing.  w = 0.5 len, n^ = n / len, d = -((n^x ax + n^y ay) + n^z az), wn = w n^ (three products), wd = w d.
+ *   Its ten entries, in the order of quadrics [K,10]:
+ *     xx = wnx n^x, xy = wnx n^y, xz = wnx n^z, xd = wnx d, yy = wny n^y, yz = wny n^z, yd = wny d, zz = wnz n^z,
+ *     zd = wnz d, dd = wd d.
+ *   One record per corner: the entries are added to the cell of each of the three corners (twice where two corners
+ *   share a cell).
+ * 4. Order of the sums: per cell and entry the records in ascending (triangle, corner), added to 0.0 one by one -- a
+ *   function of the cell's records alone.  (The kernel gives a cell one wave: 64 records' entries are computed side
+ *   by side and then added in this order.)
+ *   The solve, per cell: A = [[xx xy xz][xy yy yz][xz yz zz]], b = (xd, yd, zd), m = the average,
+ *   g_a = ((A_a0 m_0 + A_a1 m_1) + A_a2 m_2) + b_a.  Cyclic Jacobi on A with R = I: at most
+ *   RADEGS_SIMPLIFY_JACOBI_SWEEPS sweeps, none once a01, a02 and a12 are all exactly 0; a sweep visits the pairs
+ *   (p, q) = (0,1), (0,2), (1,2), r the third index, and leaves a pair with a_pq == 0 alone; otherwise
+ *     theta = (a_qq - a_pp) / (2 a_pq);  t = (theta < 0 ? -1 : 1) / (|theta| + sqrt(theta theta + 1));
+ *     c = 1 / sqrt(t t + 1);  s = t c;  a_pp -= t a_pq (one product, then the difference);  a_qq += that product;
+ *     a_pq = 0;  (a_rp, a_rq) = (c a_rp - s a_rq, s a_rp + c a_rq);  for k = 0, 1, 2:
+ *     (R_kp, R_kq) = (c R_kp - s R_kq, s R_kp + c R_kq).
+ *   lambda_i = a_ii afterwards, r_i = column i of R, lambda_max = the largest (compared with >, starting from
+ *   lambda_0).  x = m; for i = 0, 1, 2 with lambda_i > 1e-3 lambda_max (Lindstrom's cut):
+ *     coef = ((R_0i g_0 + R_1i g_1) + R_2i g_2) / lambda_i;  x_a = x_a - coef R_ai.
+ *   x = m instead unless lambda_max is positive and finite, x is finite and, on every axis,
+ *   o_a + c_a h <= x_a <= o_a + (c_a + 1) h (a product, then a sum; c_a from the cell's key).  positions [K,3] = x.
+ * 5. Faces (radegs_simplify_faces).  cell_faces [F,3] = the corners' cell numbers, rotated so that the smallest comes
+ *   first (the orientation stays); remove [F] = 1 where two corners share a cell (the row is then 0 0 0).
+ *   remove_duplicates: of the faces with the same rotated triple only the one of lowest index stays (opposite
+ *   orientations are different triples); the triples are sorted LSD: the third number, then stable by (second, first).
+ * 6. Compaction is radegs_meshclean_compact_plan / _apply on (K, cell_faces, remove): output faces keep the ascending
+ *   order of their input face.  radegs_simplify_face_source reads that plan's workspace (of
+ *   radegs_meshclean_compact_bytes(K, F)) after the plan: face_source [nf_out] = the input face of every output face.
+ * --------------------------------------------------------------------------------------------------------------- */
+#define RADEGS_SIMPLIFY_CELL_BITS 21
+#define RADEGS_SIMPLIFY_JACOBI_SWEEPS 8
+size_t radegs_simplify_cells_bytes(long long V);
+int radegs_simplify_cells(long long V, const double* vertices, double ox, double oy, double oz, double h, long long max_key, void* workspace,
+                          size_t workspace_bytes, long long* vertex_cell /* [V] */, int* order /* [V] */, int* cell_start /* [V + 1] */,
+                          long long* cell_key /* [V] */, long long* n_cells /* [1] */, void* stream);
+size_t radegs_simplify_vertices_bytes(long long F);
+int radegs_simplify_vertices(long long V, long long F, long long K, int A, const double* vertices, const long long* faces,
+                             const double* attributes /* [V,A] */, const long long* vertex_cell, const int* order, const int* cell_start,
+                             const long long* cell_key, double ox, double oy, double oz, double h, int quadric, void* workspace,
+                             size_t workspace_bytes, double* averages /* [K,3] */, double* attributes_out /* [K,A] */, double* quadrics /* [K,10] */,
+                             double* positions /* [K,3] */, void* stream);
+size_t radegs_simplify_faces_bytes(long long F);
+int radegs_simplify_faces(long long V, long long F, long long K, const long long* faces, const long long* vertex_cell, int remove_duplicates,
+                          void* workspace, size_t workspace_bytes, long long* cell_faces /* [F,3] */, unsigned char* remove /* [F] */, void* stream);
+int radegs_simplify_face_source(long long K, long long F, const void* compact_workspace, long long nf_out, long long* face_source /* [nf_out] */,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -70,6 +70,8 @@ UNITS = {
     "radegs_evalio": ["radegs_evalio.hip", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
     # default FLAGS: the pose gradient is held to tests/pose_restatement.py bit for bit, one rounding per fp64 operation, IEEE divide / sqrt
     "radegs_pose": ["radegs_pose.hip", "rg_pose.h", "rg_reduce.h", os.path.join("..", "..", "include", "radegs.h")],
+    # default FLAGS: the quadrics and the Jacobi solve are held to tests/simplify_restatement.py bit for bit, one rounding per fp64 operation
+    "radegs_meshsimplify": ["radegs_meshsimplify.hip", "rg_filter.h", "rg_prims.h", "rg_workspace.h", os.path.join("..", "..", "include", "radegs.h")],
 }
 # Units outside the rasterizer's decision chain have no bit-exactness contract with the oracle: let them contract to fma.
 # radegs_filter3d calls expf: under `fast` the compiler also contracts INSIDE expf's expansion (x*log2e - round(x*log2e) becomes one fma and

@@ -133,7 +133,10 @@ EXPORTED_SYMBOLS = ("radegs_forward", "radegs_backward", "radegs_backward_ordere
                     # evaluation from files (bound in eval_io.py)
                     "radegs_evalio_unpack_points", "radegs_evalio_unpack_faces", "radegs_evalio_ransac",
                     # camera pose refinement (prototypes below, called from pose_opt.py)
-                    "radegs_pose_gradient_bytes", "radegs_pose_gradient", "radegs_pose_step")
+                    "radegs_pose_gradient_bytes", "radegs_pose_gradient", "radegs_pose_step",
+                    # mesh simplification (bound in mesh_simplify.py)
+                    "radegs_simplify_cells_bytes", "radegs_simplify_cells", "radegs_simplify_vertices_bytes", "radegs_simplify_vertices",
+                    "radegs_simplify_faces_bytes", "radegs_simplify_faces", "radegs_simplify_face_source")
 
 _lib = None
 # test hook: when True, the per-Gaussian accumulation scratch of the last backward is kept in LAST_ACC

@@ -43,7 +43,7 @@ setup(
     version="0.6.0",
     description="MI355X-native differentiable Gaussian-splat rasterizer behind RaDe-GS's diff_gaussian_rasterization API (HIP, gfx950)",
     packages=["diff_gaussian_rasterization", "simple_knn", "tetranerf", "tetranerf.utils", "tetranerf.utils.extension", "lpipsPyTorch"],
-    py_modules=["graphics_utils", "loss_utils", "gaussian_model_ops", "fused_adam", "view_parallel", "synth_scene", "geom_host", "tetmesh", "mesh_eval", "tnt_eval", "tnt_cull", "mesh_clean", "delaunay", "appearance_network", "image_eval", "model_io", "scene_io", "unbounded_mesh", "eval_io", "gaussian_model", "gaussian_render", "train_args", "trainer", "pose_opt"],
+    py_modules=["graphics_utils", "loss_utils", "gaussian_model_ops", "fused_adam", "view_parallel", "synth_scene", "geom_host", "tetmesh", "mesh_eval", "tnt_eval", "tnt_cull", "mesh_clean", "mesh_simplify", "delaunay", "appearance_network", "image_eval", "model_io", "scene_io", "unbounded_mesh", "eval_io", "gaussian_model", "gaussian_render", "train_args", "trainer", "pose_opt"],
     package_data={"diff_gaussian_rasterization": ["libradegs_hip.so", "_C_torch*.so"]},
     include_package_data=True,
     python_requires=">=3.8",

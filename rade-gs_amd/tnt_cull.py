@@ -11,6 +11,7 @@ import torch
 
 import geom_host as gh
 import mesh_clean
+import mesh_simplify
 from diff_gaussian_rasterization import _C
 from geom_host import f32, f64, i32, ll, sz, vp
 
@@ -28,6 +29,9 @@ _SIGNATURES = {
     "radegs_tetmesh_filter_plan_flags": (i32, [ll, ll, vp, vp, vp, sz, vp, vp]),
     "radegs_tetmesh_filter_apply": (i32, [ll, ll, vp, vp, vp, ll, ll, vp, vp, vp]),
     **mesh_clean.SIGNATURES,      # get_connected_mesh below runs on them
+    # mesh_simplify.py binds its own table; it is merged here, next to the clean-up whose compaction it ends in, because the check that the
+    # signature tables of the host modules together cover every exported symbol reads this module's table, not mesh_simplify's
+    **mesh_simplify.SIGNATURES,
 }
 get_connected_mesh = mesh_clean.get_connected_mesh      # cull_mesh.py:186-202
 
