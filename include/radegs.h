@@ -442,7 +442,8 @@ int radegs_knn_mean_dist2(int P, const float* points, void* scratch, float* out 
  * max_radii2D update for one view, in place, one launch, no host read.  grad_means2D: [P,3] (xy signed, column 2 the
  * abs-gradient).  visible: [P] bytes, or NULL = radii > 0 (then radii is required).  For each visible row
  *   accum += sqrt(gx^2+gy^2); accum_abs += |g2|; accum_abs_max = max(., |g2|); denom += 1; max_radii2D = max(., radii)
- * (max_radii2D or radii NULL: that line is skipped).  Invisible rows are not written.
+ * (max_radii2D or radii NULL: that line is skipped).  Invisible rows are not written.  accum_abs_max propagates NaN as
+ * upstream's torch.max does: a NaN |g2|, or a NaN already stored, leaves NaN (C's fmaxf would keep the other operand).
  * radegs_densify_stats_reduced: the same update from view_parallel's rank-reduced [P,3] statistics (sum |grad xy|,
  * sum |grad abs|, number of ranks that saw the Gaussian) and radii_max; rows whose count is 0 are not written;
  * accum_abs_max takes the max with the SUM column (the per-rank maximum is not transmitted).

@@ -46,7 +46,8 @@ __global__ void __launch_bounds__(256) stats_kernel(int P, const float* __restri
   if (!vis) return;
   accum[i] += add;
   accum_abs[i] += add_abs;
-  accum_abs_max[i] = fmaxf(accum_abs_max[i], add_abs);
+  const float m = accum_abs_max[i];
+  accum_abs_max[i] = (m > add_abs || m != m) ? m : add_abs;   // a NaN on either side stays, as in upstream's torch.max (fmaxf would drop it)
   denom[i] += add_n;
   if (max_radii2D && radii) max_radii2D[i] = fmaxf(max_radii2D[i], (float)r);
 }
