@@ -2,7 +2,7 @@
 // backward's scratch, densify, knn, tetmesh, mesheval, tsdf, tnteval, tntcull, meshclean, appearance, and the sort's own temp): sizes, the launch
 // status, the library's ONE carver, which every unit lays its buffers out with, and the one device binary search.  What
 // else is shared lives next door: the fixed-order fp64 sum in rg_reduce.h, the two-word sort with its joined 64-bit key in rg_prims.h /
-// radegs_sort.hip, and the Python host layer of the geometry modules in geom_host.py.
+// radegs_sort.hip, and the Python host layer of every module in geom_host.py.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

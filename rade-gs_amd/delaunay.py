@@ -6,12 +6,12 @@ by a deterministic jitter of `jitter` x the bounding-box diagonal: the result is
 tetrahedralisation of the hull of the input to 1e-9 of the scene's size.  include/radegs.h, "Delaunay", is the specification, DESIGN 11 N13
 the reasoning, tests/delaunay_restatement.py the NumPy restatement."""
 import ctypes
+import functools
 import math
 
 import torch
 
 import geom_host as gh
-from diff_gaussian_rasterization import _C
 from geom_host import f64, i32, ll, sz, vp
 
 ull = ctypes.c_ulonglong
@@ -29,6 +29,9 @@ SIGNATURES = {
 
 def _lib():
     return gh.bind(SIGNATURES)
+
+
+_call = functools.partial(gh.call, SIGNATURES)
 
 
 # ------------------------------------------------------------------------- arguments -------------------------------------------------------------------------
@@ -76,8 +79,7 @@ def perturbed(points, jitter=1e-9, seed=0):
         return p.clone()
     _, diag = _bounds(p)
     out = torch.empty_like(p)
-    with torch.cuda.device(p.device):
-        gh.check(_lib().radegs_delaunay_perturb(p.shape[0], _C._ptr(p), jitter * diag, seed, _C._ptr(out), _C._stream(p.device)), "radegs_delaunay_perturb")
+    _call("radegs_delaunay_perturb", p.device, p.shape[0], p, jitter * diag, seed, out)
     return out
 
 
@@ -86,22 +88,19 @@ def _plan(p, bounds, scale, seed):
     """the cells of every point as records in a workspace: (workspace, its bytes, record capacity, [records, deferred, uncertain, overflow]);
     one host read, one more for every time the records outgrew the workspace"""
     dev, N = p.device, p.shape[0]
-    L = _lib()
     counts4 = torch.zeros(4, dtype=torch.int64, device=dev)
     capacity = min(32 * N + 1024, MAX_RECORDS)          # 4 T is about 27 N on scattered points
-    with torch.cuda.device(dev):
-        while True:
-            nbytes = L.radegs_delaunay_bytes(N, capacity)
-            ws = gh.workspace(nbytes, dev)
-            gh.check(L.radegs_delaunay_plan(N, _C._ptr(p), gh.doubles(bounds), scale, seed, capacity, _C._ptr(ws), nbytes, _C._ptr(counts4),
-                                            _C._stream(dev)), "radegs_delaunay_plan")
-            counts = counts4.tolist()                    # the host read that sizes the sort and the output
-            if counts[0] <= capacity:
-                return ws, nbytes, capacity, counts
-            if counts[0] > MAX_RECORDS:
-                raise RuntimeError(f"radegs_delaunay_plan: {counts[0]} records (4 T) are more than the 32-bit sort addresses (include/radegs.h)")
-            del ws
-            capacity = counts[0]                         # an input with more tetrahedra a point than scattered ones have
+    while True:
+        nbytes = _lib().radegs_delaunay_bytes(N, capacity)
+        ws = gh.workspace(nbytes, dev)
+        _call("radegs_delaunay_plan", dev, N, p, gh.doubles(bounds), scale, seed, capacity, ws, nbytes, counts4)
+        counts = counts4.tolist()                    # the host read that sizes the sort and the output
+        if counts[0] <= capacity:
+            return ws, nbytes, capacity, counts
+        if counts[0] > MAX_RECORDS:
+            raise RuntimeError(f"radegs_delaunay_plan: {counts[0]} records (4 T) are more than the 32-bit sort addresses (include/radegs.h)")
+        del ws
+        capacity = counts[0]                         # an input with more tetrahedra a point than scattered ones have
 
 
 def _emit(N, ws, nbytes, capacity, records):
@@ -110,10 +109,8 @@ def _emit(N, ws, nbytes, capacity, records):
     rows = (records + 3) // 4
     cells = torch.empty((rows, 4), dtype=torch.int32, device=dev)
     counts2 = torch.zeros(2, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        gh.check(_lib().radegs_delaunay_emit(N, records, capacity, _C._ptr(ws), nbytes, rows, _C._ptr(cells), _C._ptr(counts2), _C._stream(dev)),
-                 "radegs_delaunay_emit")
-        unique, inconsistent = counts2.tolist()
+    _call("radegs_delaunay_emit", dev, N, records, capacity, ws, nbytes, rows, cells, counts2)
+    unique, inconsistent = counts2.tolist()
     return cells, unique, inconsistent
 
 

@@ -133,10 +133,8 @@ def unpack_points(buffer, byte_offset, N, S, columns):
         raise RuntimeError("`columns` must be three (offset, type) pairs inside the record")
     dev = buffer.device
     out = torch.empty((N, 3), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        gh.check(_lib().radegs_evalio_unpack_points(N, S, _C._ptr(buffer), byte_offset, _INTS3(*[o for o, _ in columns]),
-                                                    _INTS3(*[model_io.TYPE_CODES[t] for _, t in columns]), _C._ptr(out), _C._stream(dev)),
-                 "radegs_evalio_unpack_points")
+    gh.call(_SIGNATURES, "radegs_evalio_unpack_points", dev, N, S, buffer, byte_offset, _INTS3(*[o for o, _ in columns]),
+            _INTS3(*[model_io.TYPE_CODES[t] for _, t in columns]), out)
     return out
 
 
@@ -154,10 +152,8 @@ def unpack_faces(buffer, byte_offset, F, S, count_offset, count_type, index_offs
     dev = buffer.device
     faces = torch.empty((F, 3), dtype=torch.int64, device=dev)
     bad = torch.empty(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        gh.check(_lib().radegs_evalio_unpack_faces(F, S, _C._ptr(buffer), byte_offset, count_offset, model_io.TYPE_CODES[count_type], index_offset,
-                                                   model_io.TYPE_CODES[index_type], V, _C._ptr(faces), _C._ptr(bad), _C._stream(dev)),
-                 "radegs_evalio_unpack_faces")
+    gh.call(_SIGNATURES, "radegs_evalio_unpack_faces", dev, F, S, buffer, byte_offset, count_offset, model_io.TYPE_CODES[count_type], index_offset,
+            model_io.TYPE_CODES[index_type], V, faces, bad)
     return faces, bad
 
 

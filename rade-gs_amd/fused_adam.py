@@ -7,6 +7,7 @@ import ctypes
 
 import torch
 
+import geom_host as gh
 from diff_gaussian_rasterization import _C
 
 MAX_TENSORS = 16
@@ -36,7 +37,6 @@ class Adam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        L = _lib()
         todo = []
         for group in self.param_groups:
             for p in group["params"]:
@@ -73,8 +73,5 @@ class Adam(torch.optim.Optimizer):
             for i in range(0, len(items), MAX_TENSORS):
                 chunk = items[i:i + MAX_TENSORS]
                 arr = (RadegsAdamTensor * len(chunk))(*[c[0] for c in chunk])
-                with torch.cuda.device(dev):
-                    rc = L.radegs_adam_step(len(chunk), arr, float(betas[0]), float(betas[1]), eps, _C._stream(dev))
-                if rc != 0:
-                    raise RuntimeError(f"radegs_adam_step failed ({rc})")
+                gh.call(_SIGNATURES, "radegs_adam_step", dev, len(chunk), arr, float(betas[0]), float(betas[1]), eps)
         return loss

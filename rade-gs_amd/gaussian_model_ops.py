@@ -5,9 +5,11 @@ SURVEY 8f N3.  One streaming kernel per direction instead of ~10 / ~20 eager tor
 Also the HIP-backed adaptive density control of the same class: add_densification_stats,
 densify_and_prune and patch_gaussian_model, which installs both on the reference's GaussianModel."""
 import ctypes
+import functools
 
 import torch
 
+import geom_host as gh
 import model_io as _model_io
 from diff_gaussian_rasterization import _C
 
@@ -38,6 +40,9 @@ def _lib():
     return _C.bind(_SIGNATURES)
 
 
+_call = functools.partial(gh.call, _SIGNATURES)
+
+
 def _prep(t, name, cols):
     _C._require_gpu(t, name)
     if t.dtype != torch.float32 or t.dim() != 2 or t.size(1) != cols:
@@ -53,10 +58,7 @@ class _ScalingOpacity3DFilter(torch.autograd.Function):
         if op.size(0) != P or f3.size(0) != P:
             raise RuntimeError("_scaling, _opacity and filter_3D must have the same number of rows")
         scales, opacity = torch.empty_like(sc), torch.empty_like(op)
-        with torch.cuda.device(sc.device):
-            rc = _lib().radegs_filter3d_forward(P, _C._ptr(sc), _C._ptr(op), _C._ptr(f3), _C._ptr(scales), _C._ptr(opacity), _C._stream(sc.device))
-        if rc != 0:
-            raise RuntimeError(f"radegs_filter3d_forward failed ({rc})")
+        _call("radegs_filter3d_forward", sc.device, P, sc, op, f3, scales, opacity)
         ctx.save_for_backward(sc, op, f3)
         ctx.set_materialize_grads(False)     # an output that nothing downstream uses arrives as None, not as a tensor of zeros
         return scales, opacity
@@ -69,11 +71,7 @@ class _ScalingOpacity3DFilter(torch.autograd.Function):
         gs = None if g_scales is None else g_scales.contiguous()
         go = None if g_opacity is None else g_opacity.contiguous()
         g_sc, g_op = torch.empty_like(sc), torch.empty_like(op)
-        with torch.cuda.device(sc.device):
-            rc = _lib().radegs_filter3d_backward(sc.size(0), _C._ptr(sc), _C._ptr(op), _C._ptr(f3), _C._ptr(gs), _C._ptr(go), _C._ptr(g_sc),
-                                                 _C._ptr(g_op), _C._stream(sc.device))
-        if rc != 0:
-            raise RuntimeError(f"radegs_filter3d_backward failed ({rc})")
+        _call("radegs_filter3d_backward", sc.device, sc.size(0), sc, op, f3, gs, go, g_sc, g_op)
         return g_sc, g_op, None
 
 
@@ -149,11 +147,7 @@ def model_activations_forward(f_dc, f_rest, rotation_raw, scaling_raw, opacity_r
         raise RuntimeError("_features_dc, _features_rest, _rotation, _scaling, _opacity and filter_3D must be on the same device")
     dc, rest, rot = _aligned(dc.detach()), _aligned(rest.detach()), _aligned(rot.detach())
     shs, rotations, scales, opacity = _outputs(out, ((P, K + 1, 3), (P, 4), (P, 3), (P, 1)), dev)
-    with torch.cuda.device(dev):
-        rc = _lib().radegs_model_activate_forward(P, K, _C._ptr(dc), _C._ptr(rest) if K else None, _C._ptr(rot), _C._ptr(sc), _C._ptr(op), _C._ptr(f3),
-                                                  _C._ptr(shs), _C._ptr(rotations), _C._ptr(scales), _C._ptr(opacity), _C._stream(dev))
-    if rc != 0:
-        raise RuntimeError(f"radegs_model_activate_forward failed ({rc})")
+    _call("radegs_model_activate_forward", dev, P, K, dc, rest if K else None, rot, sc, op, f3, shs, rotations, scales, opacity)
     return shs, rotations, scales, opacity
 
 
@@ -175,12 +169,7 @@ def model_activations_backward(K, rotation_raw, scaling_raw, opacity_raw, filter
             raise RuntimeError(f"grad of {n} must have {P} rows")
     out = _outputs(out, ((P, 1, 3), (P, K, 3), (P, 4), (P, 3), (P, 1)), dev)
     g_dc, g_rest, g_rot, g_sc, g_op = out
-    with torch.cuda.device(dev):
-        rc = _lib().radegs_model_activate_backward(P, K, _C._ptr(rot), _C._ptr(sc), _C._ptr(op), _C._ptr(f3), _C._ptr(gsh), _C._ptr(gr), _C._ptr(gs),
-                                                   _C._ptr(go), _C._ptr(g_dc), _C._ptr(g_rest) if K else None, _C._ptr(g_rot), _C._ptr(g_sc), _C._ptr(g_op),
-                                                   _C._stream(dev))
-    if rc != 0:
-        raise RuntimeError(f"radegs_model_activate_backward failed ({rc})")
+    _call("radegs_model_activate_backward", dev, P, K, rot, sc, op, f3, gsh, gr, gs, go, g_dc, g_rest if K else None, g_rot, g_sc, g_op)
     return out
 
 
@@ -219,11 +208,7 @@ def compute_3D_filter(xyz, cameras):
     dist = torch.empty(P, dtype=torch.float32, device=x.device)
     mx = torch.empty(1, dtype=torch.int32, device=x.device)
     out = torch.empty((P, 1), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = _lib().radegs_compute_filter3d(P, _C._ptr(x), len(rows), _C._ptr(table), float(focal_length), _C._ptr(dist), _C._ptr(mx),
-                                            _C._ptr(out), _C._stream(x.device))
-    if rc != 0:
-        raise RuntimeError(f"radegs_compute_filter3d failed ({rc})")
+    _call("radegs_compute_filter3d", x.device, P, x, len(rows), table, float(focal_length), dist, mx, out)
     return out
 
 
@@ -242,12 +227,12 @@ def _rows(t, name, P, dtype=torch.float32):
     return t
 
 
-def _stat_ptrs(model, P):
-    ptrs = [_C._ptr(_rows(getattr(model, n), n, P)) for n in _STATS]
-    for n in _STATS:
-        if getattr(model, n).numel() != P:
+def _stat_rows(model, P):
+    stats = [_rows(getattr(model, n), n, P) for n in _STATS]
+    for n, t in zip(_STATS, stats):
+        if t.numel() != P:
             raise RuntimeError(f"`{n}` must have one element per Gaussian")
-    return ptrs
+    return stats
 
 
 @torch.no_grad()
@@ -270,10 +255,7 @@ def add_densification_stats(model, viewspace_point_tensor, update_filter=None, r
         mask = _rows(update_filter, "update_filter", P, update_filter.dtype).view(torch.uint8)
     rad = None if radii is None else _rows(radii, "radii", P, torch.int32)
     mr = None if radii is None else _rows(model.max_radii2D, "max_radii2D", P)
-    with torch.cuda.device(g.device):
-        rc = _lib().radegs_densify_stats(P, _C._ptr(g), _C._ptr(rad), _C._ptr(mask), *_stat_ptrs(model, P), _C._ptr(mr), _C._stream(g.device))
-    if rc != 0:
-        raise RuntimeError(f"radegs_densify_stats failed ({rc})")
+    _call("radegs_densify_stats", g.device, P, g, rad, mask, *_stat_rows(model, P), mr)
 
 
 @torch.no_grad()
@@ -287,10 +269,7 @@ def add_reduced_densification_stats(model, densify_stats, radii_max=None):
         raise RuntimeError("`densify_stats` must be (P,3)")
     rad = None if radii_max is None else _rows(radii_max, "radii_max", P, torch.int32)
     mr = None if radii_max is None else _rows(model.max_radii2D, "max_radii2D", P)
-    with torch.cuda.device(st.device):
-        rc = _lib().radegs_densify_stats_reduced(P, _C._ptr(st), _C._ptr(rad), *_stat_ptrs(model, P), _C._ptr(mr), _C._stream(st.device))
-    if rc != 0:
-        raise RuntimeError(f"radegs_densify_stats_reduced failed ({rc})")
+    _call("radegs_densify_stats_reduced", st.device, P, st, rad, *_stat_rows(model, P), mr)
 
 
 def densify_plan(accum, accum_abs, denom, scaling_raw, opacity_raw, max_grad, abs_threshold, dense_threshold, min_opacity, big_threshold=None):
@@ -303,16 +282,11 @@ def densify_plan(accum, accum_abs, denom, scaling_raw, opacity_raw, max_grad, ab
     _C._require_gpu(abs_threshold, "abs_threshold")
     if abs_threshold.dtype != torch.float32 or abs_threshold.numel() != 1:
         raise RuntimeError("`abs_threshold` must be one float32 on the GPU")
-    L = _lib()
-    nbytes = L.radegs_densify_plan_bytes(P)
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    nbytes = _lib().radegs_densify_plan_bytes(P)
+    ws = gh.workspace(nbytes, dev)
     counts = torch.empty(4, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.radegs_densify_plan(P, _C._ptr(accum), _C._ptr(accum_abs), _C._ptr(denom), _C._ptr(scaling_raw), _C._ptr(opacity_raw), float(max_grad),
-                                   _C._ptr(abs_threshold), float(dense_threshold), float(min_opacity), int(big_threshold is not None),
-                                   float(big_threshold or 0.0), _C._ptr(ws), nbytes, _C._ptr(counts), _C._stream(dev))
-    if rc != 0:
-        raise RuntimeError(f"radegs_densify_plan failed ({rc})")
+    _call("radegs_densify_plan", dev, P, accum, accum_abs, denom, scaling_raw, opacity_raw, float(max_grad), abs_threshold, float(dense_threshold),
+          float(min_opacity), int(big_threshold is not None), float(big_threshold or 0.0), ws, nbytes, counts)
     return ws, counts
 
 
@@ -346,10 +320,7 @@ def densify_apply(workspace, P_out, params, exp_avg, exp_avg_sq, unit_normals):
         z = _rows(unit_normals, "unit_normals", P)
         if tuple(z.shape) != (P, 3, 3):
             raise RuntimeError("`unit_normals` must be (P,3,3)")
-        with torch.cuda.device(dev):
-            rc = _lib().radegs_densify_apply(P, P_out, widths[2], ctypes.byref(t), _C._ptr(z), _C._ptr(workspace), _C._stream(dev))
-        if rc != 0:
-            raise RuntimeError(f"radegs_densify_apply failed ({rc})")
+        _call("radegs_densify_apply", dev, P, P_out, widths[2], ctypes.byref(t), z, workspace)
     return outs
 
 

@@ -1,5 +1,6 @@
-"""The host layer the geometry modules share (tetmesh, mesh_eval, tsdf, tnt_eval, tnt_cull): binding a module's table of C signatures to
-libradegs_hip.so, the return-code check, the workspace buffer, and the argument checks that refuse rather than convert."""
+"""The host layer of every module that calls libradegs_hip.so outside the rasterizer's own entry points (diff_gaussian_rasterization/_C.py):
+binding a module's table of C signatures to the library, call() -- the one routine through which a launching entry point is reached -- the
+return-code check, the workspace buffer, and the argument checks that refuse rather than convert."""
 import ctypes
 import math
 
@@ -19,6 +20,36 @@ def check(rc, what):
         raise RuntimeError(f"{what}: the input is larger than the 32-bit sort / scan primitives address (include/radegs.h)")
     if rc != 0:
         raise RuntimeError(f"{what} failed ({rc})")
+
+
+def call(signatures, name, dev, *args):
+    """One launching native call, the only way a module reaches an `int radegs_x(..., void* stream)` entry point: `name` with the prototype
+    the module's table `signatures` declares for it, under `dev`'s device context, on `dev`'s current stream (appended as the last
+    argument), the return code through check().  A tensor stands for its device pointer, None for NULL; every other value goes to ctypes as
+    it is.  A tensor that is not contiguous, or lies on another GPU than `dev`, is refused before anything is called (host tensors pass:
+    pinned buffers are handed over on purpose); nothing is converted or copied.  `args` keeps the tensors alive for the call."""
+    lib = bind(signatures)
+    if name not in signatures:
+        raise RuntimeError(f"{name} is not in the calling module's table of signatures")
+    restype, argtypes = signatures[name]
+    if restype is not ctypes.c_int or not argtypes or argtypes[-1] is not ctypes.c_void_p:
+        raise RuntimeError(f"{name} is not declared as `int {name}(..., void* stream)`")
+    if len(args) + 1 != len(argtypes):
+        raise RuntimeError(f"{name} takes {len(argtypes) - 1} arguments before the stream, got {len(args)}")
+    dev = torch.device(dev)
+    if dev.index is None:       # plain "cuda" means the current device, as it does to torch
+        dev = torch.device(dev.type, torch.cuda.current_device())
+    values = []
+    for i, a in enumerate(args):
+        if isinstance(a, torch.Tensor):
+            if not a.is_contiguous():
+                raise RuntimeError(f"{name}: argument {i} is a tensor that is not contiguous")
+            if a.is_cuda and a.device != dev:
+                raise RuntimeError(f"{name}: argument {i} is a tensor on {a.device}, the call runs on {dev}")
+            a = a.data_ptr()
+        values.append(a)
+    with torch.cuda.device(dev):
+        check(getattr(lib, name)(*values, torch.cuda.current_stream(dev).cuda_stream), name)
 
 
 def workspace(nbytes, dev):

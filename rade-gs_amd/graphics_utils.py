@@ -8,9 +8,11 @@ Same names, arguments (`view` needs image_width, image_height, FoVx, FoVy) and r
 (torch.autograd.Function over libradegs_hip.so's radegs_normals_* / radegs_normal_loss_* entry points).  One kernel per
 direction instead of ~10 / ~25 eager torch kernels.  GPU only: there is no CPU path."""
 import ctypes
+import functools
 
 import torch
 
+import geom_host as gh
 import scene_io
 from diff_gaussian_rasterization import _C
 
@@ -38,9 +40,7 @@ def _lib():
     return _C.bind(_SIGNATURES)
 
 
-def _check(rc, what):
-    if rc != 0:
-        raise RuntimeError(f"{what} failed: {_lib().radegs_normals_last_error().decode()}")
+_call = functools.partial(gh.call, _SIGNATURES)
 
 
 def _prep(t, name, channels, H, W):
@@ -54,7 +54,7 @@ def _prep(t, name, channels, H, W):
 
 def _args(view, m1, m2, points):
     return RadegsNormalArgs(int(view.image_width), int(view.image_height), int(points), float(view.FoVx), float(view.FoVy),
-                            _C._ptr(m1), _C._ptr(m2))
+                            m1.data_ptr(), m2.data_ptr())
 
 
 class _DoubleToNormal(torch.autograd.Function):
@@ -64,9 +64,7 @@ class _DoubleToNormal(torch.autograd.Function):
         c = 3 if points else 1
         m1, m2 = _prep(map1, "map1", c, H, W), _prep(map2, "map2", c, H, W)
         out = torch.empty((2, 3, H, W), dtype=torch.float32, device=m1.device)
-        with torch.cuda.device(m1.device):
-            _check(_lib().radegs_normals_forward(ctypes.byref(_args(view, m1, m2, points)), _C._ptr(out), _C._stream(m1.device)),
-                   "radegs_normals_forward")
+        _call("radegs_normals_forward", m1.device, ctypes.byref(_args(view, m1, m2, points)), out)
         ctx.view, ctx.points = view, points
         ctx.shapes = (map1.shape, map2.shape)
         ctx.save_for_backward(m1, m2)
@@ -77,9 +75,7 @@ class _DoubleToNormal(torch.autograd.Function):
         m1, m2 = ctx.saved_tensors
         g = grad_out.contiguous()
         g1, g2 = torch.empty_like(m1), torch.empty_like(m2)
-        with torch.cuda.device(m1.device):
-            _check(_lib().radegs_normals_backward(ctypes.byref(_args(ctx.view, m1, m2, ctx.points)), _C._ptr(g), _C._ptr(g1), _C._ptr(g2),
-                                                  _C._stream(m1.device)), "radegs_normals_backward")
+        _call("radegs_normals_backward", m1.device, ctypes.byref(_args(ctx.view, m1, m2, ctx.points)), g, g1, g2)
         return None, g1.view(ctx.shapes[0]), g2.view(ctx.shapes[1]), None
 
 
@@ -99,12 +95,9 @@ class _NormalConsistencyLoss(torch.autograd.Function):
         W, H = int(view.image_width), int(view.image_height)
         c = 3 if points else 1
         m1, m2, rn = _prep(map1, "map1", c, H, W), _prep(map2, "map2", c, H, W), _prep(rendered_normal, "rendered_normal", 3, H, W)
-        L = _lib()
-        scratch = torch.empty(L.radegs_normal_loss_scratch_bytes(W, H), dtype=torch.uint8, device=m1.device)
+        scratch = gh.workspace(_lib().radegs_normal_loss_scratch_bytes(W, H), m1.device)
         out = torch.empty(3, dtype=torch.float32, device=m1.device)
-        with torch.cuda.device(m1.device):
-            _check(L.radegs_normal_loss_forward(ctypes.byref(_args(view, m1, m2, points)), _C._ptr(rn), float(depth_ratio), _C._ptr(scratch),
-                                                _C._ptr(out), _C._stream(m1.device)), "radegs_normal_loss_forward")
+        _call("radegs_normal_loss_forward", m1.device, ctypes.byref(_args(view, m1, m2, points)), rn, float(depth_ratio), scratch, out)
         ctx.view, ctx.points, ctx.depth_ratio = view, points, float(depth_ratio)
         ctx.shapes = (rendered_normal.shape, map1.shape, map2.shape)
         ctx.save_for_backward(m1, m2, rn)
@@ -115,10 +108,7 @@ class _NormalConsistencyLoss(torch.autograd.Function):
         m1, m2, rn = ctx.saved_tensors
         up = grad_loss.to(torch.float32).reshape(1).contiguous()
         g1, g2, grn = torch.empty_like(m1), torch.empty_like(m2), torch.empty_like(rn)
-        with torch.cuda.device(m1.device):
-            _check(_lib().radegs_normal_loss_backward(ctypes.byref(_args(ctx.view, m1, m2, ctx.points)), _C._ptr(rn), ctx.depth_ratio,
-                                                      _C._ptr(up), _C._ptr(g1), _C._ptr(g2), _C._ptr(grn), _C._stream(m1.device)),
-                   "radegs_normal_loss_backward")
+        _call("radegs_normal_loss_backward", m1.device, ctypes.byref(_args(ctx.view, m1, m2, ctx.points)), rn, ctx.depth_ratio, up, g1, g2, grn)
         return None, grn.view(ctx.shapes[0]), g1.view(ctx.shapes[1]), g2.view(ctx.shapes[2]), None, None
 
 

@@ -6,6 +6,7 @@ Weights are read from files the caller provides; nothing is ever fetched.  inclu
 tests/imageeval_restatement.py restates it in torch and NumPy.  torchvision is not readable where this was written: the rounding rule of
 save_image and the division of to_tensor are from memory of its source."""
 import ctypes
+import functools
 import json
 import os
 
@@ -44,6 +45,9 @@ def _lib():
     return gh.bind(_SIGNATURES)
 
 
+_call = functools.partial(gh.call, _SIGNATURES)
+
+
 def _align(n):
     return (int(n) + 255) & ~255
 
@@ -73,8 +77,7 @@ def _quantize(image, want_u8, want_float):
     dev, (_, H, W) = x.device, x.shape
     u8 = torch.empty((H, W, 3), dtype=torch.uint8, device=dev) if want_u8 else None
     out = torch.empty_like(x) if want_float else None
-    with torch.cuda.device(dev):
-        gh.check(_lib().radegs_imageeval_quantize(H, W, _C._ptr(x), _C._ptr(u8), _C._ptr(out), _C._stream(dev)), "radegs_imageeval_quantize")
+    _call("radegs_imageeval_quantize", dev, H, W, x, u8, out)
     return u8, out
 
 
@@ -96,11 +99,9 @@ def psnr(a, b):
     """utils/image_utils.py:17-19 on a (1,3,H,W) pair: (1,1), 20 log10(1 / sqrt(mse)); identical images give inf."""
     a, b = _pair(a, b)
     dev, n = a.device, a.numel()
-    L = _lib()
-    nbytes = L.radegs_imageeval_ssd_bytes()
+    nbytes = _lib().radegs_imageeval_ssd_bytes()
     ws, out = gh.workspace(nbytes, dev), torch.empty(1, dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        gh.check(L.radegs_imageeval_ssd(n, _C._ptr(a), _C._ptr(b), _C._ptr(ws), nbytes, _C._ptr(out), _C._stream(dev)), "radegs_imageeval_ssd")
+    _call("radegs_imageeval_ssd", dev, n, a, b, ws, nbytes, out)
     mse = (out / n).to(torch.float32).view(1, 1)
     return 20 * torch.log10(1.0 / torch.sqrt(mse))
 
@@ -177,20 +178,17 @@ def _pack(w):
 
 
 # ------------------------------------------------------------------------------- kernels -------------------------------------------------------------------------------
-def _conv(L, dev, N, H, W, cin, cout, src, packed, bias, dst, mean=MEAN, std=STD):
+def _conv(dev, N, H, W, cin, cout, src, packed, bias, dst, mean=MEAN, std=STD):
     """one layer into dst; Cin = 3 is the first layer: src is the planar image, z-scored on load"""
     if cin == 3:
         mean, std = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
-        gh.check(L.radegs_imageeval_conv3x3_first(N, H, W, cout, _C._ptr(src), mean, std, _C._ptr(packed), _C._ptr(bias), _C._ptr(dst), _C._stream(dev)),
-                 "radegs_imageeval_conv3x3_first")
+        _call("radegs_imageeval_conv3x3_first", dev, N, H, W, cout, src, mean, std, packed, bias, dst)
     else:
-        gh.check(L.radegs_imageeval_conv3x3(N, H, W, cin, cout, _C._ptr(src), _C._ptr(packed), _C._ptr(bias), _C._ptr(dst), _C._stream(dev)),
-                 "radegs_imageeval_conv3x3")
+        _call("radegs_imageeval_conv3x3", dev, N, H, W, cin, cout, src, packed, bias, dst)
 
 
-def _tap(L, dev, H, W, C, feat, lin, pooled, ws, ws_bytes, out):
-    gh.check(L.radegs_imageeval_tap(H, W, C, _C._ptr(feat), _C._ptr(lin), _C._ptr(pooled), _C._ptr(ws), ws_bytes, _C._ptr(out), _C._stream(dev)),
-             "radegs_imageeval_tap")
+def _tap(dev, H, W, C, feat, lin, pooled, ws, ws_bytes, out):
+    _call("radegs_imageeval_tap", dev, H, W, C, feat, lin, pooled, ws, ws_bytes, out)
 
 
 def _floats(buf, offset, *shape):
@@ -212,8 +210,7 @@ def conv3x3_relu(x, weight, bias, first=False, mean=MEAN, std=STD):
     N, H, W = (x.shape[0], x.shape[2], x.shape[3]) if first else x.shape[:3]
     packed, b = _pack(weight.detach().to(dev, torch.float32)), bias.detach().to(dev, torch.float32).contiguous()
     y = torch.empty((N, H, W, cout), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _conv(_lib(), dev, N, H, W, cin, cout, x, packed, b, y, mean, std)
+    _conv(dev, N, H, W, cin, cout, x, packed, b, y, mean, std)
     return y
 
 
@@ -226,12 +223,10 @@ def tap_pool(feat, lin, pool=True):
     _, H, W, C = feat.shape
     if feat.shape[0] != 2 or feat.dtype != torch.float32 or lin.numel() != C:
         raise RuntimeError("`feat` must be float32 (2,H,W,C) and `lin` (C,)")
-    L = _lib()
-    nbytes = L.radegs_imageeval_tap_bytes(H, W)
+    nbytes = _lib().radegs_imageeval_tap_bytes(H, W)
     ws, out = gh.workspace(nbytes, dev), torch.empty(1, dtype=torch.float64, device=dev)
     pooled = torch.empty((2, H // 2, W // 2, C), dtype=torch.float32, device=dev) if pool else None
-    with torch.cuda.device(dev):
-        _tap(L, dev, H, W, C, feat, lin.detach().to(dev, torch.float32).contiguous(), pooled, ws, nbytes, out)
+    _tap(dev, H, W, C, feat, lin.detach().to(dev, torch.float32).contiguous(), pooled, ws, nbytes, out)
     return out, pooled
 
 
@@ -261,23 +256,22 @@ class LPIPS:
         dev, (N, _, H, W) = batch.device, batch.shape
         if H < MIN_SIDE or W < MIN_SIDE:
             raise ValueError(f"LPIPS-VGG needs H, W >= {MIN_SIDE} (the reference's fourth pool would leave an empty map), got {H}x{W}")
-        L = _lib()
         convs, lins = self._on(dev)
-        half, ws_bytes = _align(4 * N * H * W * 64), int(L.radegs_imageeval_tap_bytes(H, W))
+        half, ws_bytes = _align(4 * N * H * W * 64), int(_lib().radegs_imageeval_tap_bytes(H, W))
         key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
         out, maps = torch.empty(5, dtype=torch.float64, device=dev), []
-        with torch.cuda.device(dev), _ACT_SCRATCH.lease(key, 2 * half + _align(ws_bytes), dev) as buf:
+        with _ACT_SCRATCH.lease(key, 2 * half + _align(ws_bytes), dev) as buf:
             ws = buf[2 * half:]
             src, cur, h, w, tap = batch, 0, H, W, 0
             for k, (_, cin, cout) in enumerate(VGG_CONVS):
                 dst = _floats(buf, cur * half, N, h, w, cout)
-                _conv(L, dev, N, h, w, cin, cout, src, convs[k][0], convs[k][1], dst)
+                _conv(dev, N, h, w, cin, cout, src, convs[k][0], convs[k][1], dst)
                 src, cur = dst, 1 - cur
                 if k != TAP_AFTER[tap]:
                     continue
                 last = tap == 4
                 pooled = None if last else _floats(buf, cur * half, N, h // 2, w // 2, cout)
-                _tap(L, dev, h, w, cout, src, lins[tap], pooled, ws, ws_bytes, out[tap:])
+                _tap(dev, h, w, cout, src, lins[tap], pooled, ws, ws_bytes, out[tap:])
                 if want_maps:
                     maps.append(src[:1].permute(0, 3, 1, 2).clone())
                 if not last:

@@ -15,9 +15,11 @@ And of the decoupled appearance loss:
 with the appearance network's trunk (conv1 and the four pixel-shuffle blocks, at most half resolution) in torch and everything at
 full resolution in the HIP head kernels (radegs_appearance_*)."""
 import ctypes
+import functools
 
 import torch
 
+import geom_host as gh
 import image_eval
 from diff_gaussian_rasterization import _C
 
@@ -39,6 +41,9 @@ def _lib():
     return _C.bind(_SIGNATURES)
 
 
+_call = functools.partial(gh.call, _SIGNATURES)
+
+
 def _prep(img, gt):
     _C._require_gpu(img, "image")
     _C._require_gpu(gt, "gt")
@@ -58,17 +63,12 @@ class _Photometric(torch.autograd.Function):
     def forward(ctx, image, gt, lambda_dssim):
         a, b = _prep(image, gt)
         C, H, W = a.shape
-        L = _lib()
         dev = a.device
         need = ctx.needs_input_grad[0]
-        scratch = torch.empty(L.radegs_photometric_scratch_bytes(W, H, C), dtype=torch.uint8, device=dev)
+        scratch = gh.workspace(_lib().radegs_photometric_scratch_bytes(W, H, C), dev)
         dmaps = torch.empty((3, C, H, W), dtype=torch.float32, device=dev) if need else None
         out = torch.empty(3, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = L.radegs_photometric_forward(W, H, C, _C._ptr(a), _C._ptr(b), float(lambda_dssim), _C._ptr(scratch), _C._ptr(dmaps),
-                                              _C._ptr(out), _C._stream(dev))
-        if rc != 0:
-            raise RuntimeError(f"radegs_photometric_forward failed ({rc})")
+        _call("radegs_photometric_forward", dev, W, H, C, a, b, float(lambda_dssim), scratch, dmaps, out)
         ctx.lam = float(lambda_dssim)
         ctx.save_for_backward(a, b, dmaps)
         ctx.mark_non_differentiable()
@@ -80,11 +80,7 @@ class _Photometric(torch.autograd.Function):
         coef = torch.stack([g_loss * (1.0 - ctx.lam) + g_l1, g_ssim - g_loss * ctx.lam]).to(torch.float32).contiguous()
         grad = torch.empty_like(a)
         C, H, W = a.shape
-        with torch.cuda.device(a.device):
-            rc = _lib().radegs_photometric_backward(W, H, C, _C._ptr(a), _C._ptr(b), _C._ptr(dmaps), _C._ptr(coef), _C._ptr(grad),
-                                                    _C._stream(a.device))
-        if rc != 0:
-            raise RuntimeError(f"radegs_photometric_backward failed ({rc})")
+        _call("radegs_photometric_backward", a.device, W, H, C, a, b, dmaps, coef, grad)
         return grad, None, None
 
 
@@ -129,10 +125,7 @@ class _AppearanceDownsample(torch.autograd.Function):
         a = _appearance_image(image, "image")
         H, W, _, _ = appearance_crop(a.size(1), a.size(2))
         down = torch.empty((3, H // 32, W // 32), dtype=torch.float32, device=a.device)
-        with torch.cuda.device(a.device):
-            rc = _lib().radegs_appearance_downsample_forward(a.size(1), a.size(2), _C._ptr(a), _C._ptr(down), _C._stream(a.device))
-        if rc != 0:
-            raise RuntimeError(f"radegs_appearance_downsample_forward failed ({rc})")
+        _call("radegs_appearance_downsample_forward", a.device, a.size(1), a.size(2), a, down)
         ctx.shape = tuple(a.shape)
         return down
 
@@ -140,10 +133,7 @@ class _AppearanceDownsample(torch.autograd.Function):
     def backward(ctx, g_down):
         g = g_down.to(torch.float32).contiguous()
         grad = torch.empty(ctx.shape, dtype=torch.float32, device=g.device)
-        with torch.cuda.device(g.device):
-            rc = _lib().radegs_appearance_downsample_backward(ctx.shape[1], ctx.shape[2], _C._ptr(g), _C._ptr(grad), _C._stream(g.device))
-        if rc != 0:
-            raise RuntimeError(f"radegs_appearance_downsample_backward failed ({rc})")
+        _call("radegs_appearance_downsample_backward", g.device, ctx.shape[1], ctx.shape[2], g, grad)
         return grad
 
 
@@ -162,16 +152,12 @@ def _head_args(feat, image, gt, W2, b2, W3, b3):
 
 def _head_forward(args, want_transformed):
     feat, a = args[0], args[1]
-    L, dev = _lib(), feat.device
-    nbytes = L.radegs_appearance_head_scratch_bytes(a.size(1), a.size(2), 0)
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    dev = feat.device
+    nbytes = _lib().radegs_appearance_head_scratch_bytes(a.size(1), a.size(2), 0)
+    scratch = gh.workspace(nbytes, dev)
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     out = torch.empty((3, 2 * feat.size(1), 2 * feat.size(2)), dtype=torch.float32, device=dev) if want_transformed else None
-    with torch.cuda.device(dev):
-        rc = L.radegs_appearance_head_forward(a.size(1), a.size(2), feat.size(1), feat.size(2), *[_C._ptr(t) for t in args], _C._ptr(scratch), nbytes,
-                                              _C._ptr(loss), _C._ptr(out), _C._stream(dev))
-    if rc != 0:
-        raise RuntimeError(f"radegs_appearance_head_forward failed ({rc})")
+    _call("radegs_appearance_head_forward", dev, a.size(1), a.size(2), feat.size(1), feat.size(2), *args, scratch, nbytes, loss, out)
     return loss[0], out
 
 
@@ -190,16 +176,12 @@ class _AppearanceHead(torch.autograd.Function):
     def backward(ctx, g_loss):
         args = ctx.saved_tensors
         feat, a = args[0], args[1]
-        L, dev = _lib(), feat.device
+        dev = feat.device
         g = g_loss.to(torch.float32).reshape(1).contiguous()
-        nbytes = L.radegs_appearance_head_scratch_bytes(a.size(1), a.size(2), 1)
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        nbytes = _lib().radegs_appearance_head_scratch_bytes(a.size(1), a.size(2), 1)
+        scratch = gh.workspace(nbytes, dev)
         grads = [torch.empty_like(t) for t in (feat, a, args[3], args[4], args[5], args[6])]
-        with torch.cuda.device(dev):
-            rc = L.radegs_appearance_head_backward(a.size(1), a.size(2), feat.size(1), feat.size(2), *[_C._ptr(t) for t in args], _C._ptr(g),
-                                                   _C._ptr(scratch), nbytes, *[_C._ptr(t) for t in grads], _C._stream(dev))
-        if rc != 0:
-            raise RuntimeError(f"radegs_appearance_head_backward failed ({rc})")
+        _call("radegs_appearance_head_backward", dev, a.size(1), a.size(2), feat.size(1), feat.size(2), *args, g, scratch, nbytes, *grads)
         return grads[0], grads[1], None, grads[2], grads[3], grads[4], grads[5]
 
 

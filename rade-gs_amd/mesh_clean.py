@@ -4,6 +4,8 @@ remove_degenerate_triangles), eval_tnt/cull_mesh.py:186-202 Mesher.get_connected
 compute_vertex_normals.  GPU only.  `faces` is an int [F,3] GPU tensor, `vertices` float32 or float64 [V,3] on the same device; all arithmetic
 is float64, every sum runs in a fixed order, and two calls return the same bits.  The rules of Open3D and trimesh are written from memory
 (DESIGN 11 N12 marks each); include/radegs.h, "Mesh clean-up", is the specification and tests/meshclean_restatement.py restates it in NumPy."""
+import functools
+
 import torch
 
 import geom_host as gh
@@ -29,6 +31,9 @@ _SIGNATURES = SIGNATURES
 
 def _lib():
     return gh.bind(_SIGNATURES)
+
+
+_call = functools.partial(gh.call, _SIGNATURES)
 
 
 # ------------------------------------------------------------------------- arguments -------------------------------------------------------------------------
@@ -82,28 +87,22 @@ def _empty(dev, *shape, dtype=torch.int64):
 def _cluster(f, V, manifold):
     """(labels int64 [F], C) of checked faces, F > 0; the one host read is C"""
     dev, F = f.device, f.shape[0]
-    L = _lib()
-    nbytes = L.radegs_meshclean_cluster_bytes(F)
+    nbytes = _lib().radegs_meshclean_cluster_bytes(F)
     ws = gh.workspace(nbytes, dev)
     labels, n = _empty(dev, F), torch.zeros(1, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        gh.check(L.radegs_meshclean_cluster(V, F, _C._ptr(f), manifold, _C._ptr(ws), nbytes, _C._ptr(labels), _C._ptr(n), _C._stream(dev)),
-                 "radegs_meshclean_cluster")
+    _call("radegs_meshclean_cluster", dev, V, F, f, manifold, ws, nbytes, labels, n)
     return labels, int(n)
 
 
 def _stats(v64, f, labels, C, areas, total=False):
     """(counts int64 [C], areas float64 [C] or None, total float64 [1] or None); v64 may be None without areas"""
     dev, F = f.device, f.shape[0]
-    L = _lib()
-    nbytes = L.radegs_meshclean_stats_bytes(F, C)
+    nbytes = _lib().radegs_meshclean_stats_bytes(F, C)
     ws = gh.workspace(nbytes, dev)
     counts = _empty(dev, C)
     area = _empty(dev, C, dtype=torch.float64) if areas else None
     tot = _empty(dev, 1, dtype=torch.float64) if total else None
-    with torch.cuda.device(dev):
-        gh.check(L.radegs_meshclean_stats(0 if v64 is None else v64.shape[0], F, C, _C._ptr(v64), _C._ptr(f), _C._ptr(labels), _C._ptr(ws), nbytes,
-                                          _C._ptr(counts), _C._ptr(area), _C._ptr(tot), _C._stream(dev)), "radegs_meshclean_stats")
+    _call("radegs_meshclean_stats", dev, 0 if v64 is None else v64.shape[0], F, C, v64, f, labels, ws, nbytes, counts, area, tot)
     return counts, area, tot
 
 
@@ -134,19 +133,14 @@ def _compact(V, f, remove=None, labels=None, cluster_keep=None, drop_degenerate=
     dev, F = f.device, f.shape[0]
     if V + F == 0:
         return _empty(dev, 0), _empty(dev, 0, 3)
-    L = _lib()
-    nbytes = L.radegs_meshclean_compact_bytes(V, F)
+    nbytes = _lib().radegs_meshclean_compact_bytes(V, F)
     ws = gh.workspace(nbytes, dev)
     counts2 = torch.zeros(2, dtype=torch.int64, device=dev)
     C = 0 if cluster_keep is None else cluster_keep.shape[0]
-    with torch.cuda.device(dev):
-        stream = _C._stream(dev)
-        gh.check(L.radegs_meshclean_compact_plan(V, F, C, _C._ptr(f), _C._ptr(remove), _C._ptr(labels), _C._ptr(cluster_keep), int(drop_degenerate),
-                                                 int(drop_unreferenced), _C._ptr(ws), nbytes, _C._ptr(counts2), stream), "radegs_meshclean_compact_plan")
-        nv, nf = counts2.tolist()              # the host read that sizes the outputs
-        kept, out_f = _empty(dev, nv), _empty(dev, nf, 3)
-        gh.check(L.radegs_meshclean_compact_apply(V, F, _C._ptr(f), _C._ptr(ws), nv, nf, _C._ptr(kept), _C._ptr(out_f), stream),
-                 "radegs_meshclean_compact_apply")
+    _call("radegs_meshclean_compact_plan", dev, V, F, C, f, remove, labels, cluster_keep, int(drop_degenerate), int(drop_unreferenced), ws, nbytes, counts2)
+    nv, nf = counts2.tolist()              # the host read that sizes the outputs
+    kept, out_f = _empty(dev, nv), _empty(dev, nf, 3)
+    _call("radegs_meshclean_compact_apply", dev, V, F, f, ws, nv, nf, kept, out_f)
     return kept, out_f
 
 
@@ -239,11 +233,7 @@ def compute_vertex_normals(vertices, faces, normalized=True):
     dev, V, F = v.device, v.shape[0], f.shape[0]
     out = torch.empty((V, 3), dtype=torch.float64, device=dev)
     if V:
-        L = _lib()
-        nbytes = L.radegs_meshclean_normals_bytes(F)
+        nbytes = _lib().radegs_meshclean_normals_bytes(F)
         ws = gh.workspace(nbytes, dev)
-        v64 = v.double()
-        with torch.cuda.device(dev):
-            gh.check(L.radegs_meshclean_vertex_normals(V, F, _C._ptr(v64), _C._ptr(f), int(normalized), _C._ptr(ws), nbytes, _C._ptr(out), _C._stream(dev)),
-                     "radegs_meshclean_vertex_normals")
+        _call("radegs_meshclean_vertex_normals", dev, V, F, v.double(), f, int(normalized), ws, nbytes, out)
     return out.to(v.dtype)

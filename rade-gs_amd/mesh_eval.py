@@ -4,6 +4,7 @@ nearest-neighbour distances to and from the scan's cloud).  GPU only.  eval.py's
 decision on an exact distance.  Reading DTU's .mat / .ply files, the Procrustes alignment and the coloured clouds stay with the caller
 (INTEGRATION 5b)."""
 import ctypes
+import functools
 import math
 
 import numpy as np
@@ -46,6 +47,9 @@ def _lib():
     return gh.bind(_SIGNATURES)
 
 
+_call = functools.partial(gh.call, _SIGNATURES)
+
+
 # ------------------------------------------------------------------ triangle sampling ------------------------------------------------------------------
 @torch.no_grad()
 def sample_mesh_points(vertices, faces, density=0.2):
@@ -57,24 +61,19 @@ def sample_mesh_points(vertices, faces, density=0.2):
     gh.positive(density, "density")
     gh.finite(v, "vertices")
     V, F, dev = v.shape[0], f.shape[0], v.device
-    L = _lib()
-    nbytes = L.radegs_mesheval_sample_bytes(F)
+    nbytes = _lib().radegs_mesheval_sample_bytes(F)
     ws = gh.workspace(nbytes, dev)
     counts = torch.zeros(F, dtype=torch.int32, device=dev)
     totals = torch.zeros(2, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        stream = _C._stream(dev)
-        gh.check(L.radegs_mesheval_sample_count(V, F, _C._ptr(v), _C._ptr(f), float(density), _C._ptr(ws), nbytes, _C._ptr(counts), _C._ptr(totals), stream),
-                 "radegs_mesheval_sample_count")
-        M, too_fine = totals.tolist()          # the one host read
-        if too_fine:
-            raise RuntimeError(f"sample_mesh_points: {too_fine} triangles are subdivided more than 30 000 times along an edge at density {density}")
-        if M >= 2 ** 32 - 1:
-            gh.check(gh.ERR_TOO_LARGE, "sample_mesh_points")
-        out = torch.empty((V + M, 3), dtype=torch.float64, device=dev)
-        out[:V].copy_(v)
-        gh.check(L.radegs_mesheval_sample_emit(V, F, _C._ptr(v), _C._ptr(f), float(density), _C._ptr(ws), M, ctypes.c_void_p(out.data_ptr() + 24 * V), stream),
-                 "radegs_mesheval_sample_emit")
+    _call("radegs_mesheval_sample_count", dev, V, F, v, f, float(density), ws, nbytes, counts, totals)
+    M, too_fine = totals.tolist()          # the one host read
+    if too_fine:
+        raise RuntimeError(f"sample_mesh_points: {too_fine} triangles are subdivided more than 30 000 times along an edge at density {density}")
+    if M >= 2 ** 32 - 1:
+        gh.check(gh.ERR_TOO_LARGE, "sample_mesh_points")
+    out = torch.empty((V + M, 3), dtype=torch.float64, device=dev)
+    out[:V].copy_(v)
+    _call("radegs_mesheval_sample_emit", dev, V, F, v, f, float(density), ws, M, ctypes.c_void_p(out.data_ptr() + 24 * V))
     return out, counts
 
 
@@ -90,14 +89,11 @@ class PointGrid:
         gh.finite(self.points, "points")
         self.cell, self.n, self.device = float(cell), self.points.shape[0], self.points.device
         self.origin = gh.doubles(self.points.amin(dim=0).tolist())
-        L = _lib()
-        self.nbytes = L.radegs_mesheval_grid_bytes(self.n)
+        self.nbytes = _lib().radegs_mesheval_grid_bytes(self.n)
         if self.nbytes == 0:
             gh.check(gh.ERR_TOO_LARGE, "PointGrid")
         self.ws = gh.workspace(self.nbytes, self.device)
-        with torch.cuda.device(self.device):
-            gh.check(L.radegs_mesheval_grid_build(self.n, _C._ptr(self.points), self.origin, self.cell, _C._ptr(self.ws), self.nbytes, _C._stream(self.device)),
-                     "radegs_mesheval_grid_build")
+        _call("radegs_mesheval_grid_build", self.device, self.n, self.points, self.origin, self.cell, self.ws, self.nbytes)
 
     @torch.no_grad()
     def nearest(self, queries, max_dist):
@@ -111,9 +107,7 @@ class PointGrid:
         Q = q.shape[0]
         dist = torch.empty(Q, dtype=torch.float64, device=self.device)
         index = torch.empty(Q, dtype=torch.int64, device=self.device)
-        with torch.cuda.device(self.device):
-            gh.check(_lib().radegs_mesheval_nearest(self.n, _C._ptr(self.ws), self.origin, self.cell, Q, _C._ptr(q), float(max_dist), _C._ptr(dist),
-                                                    _C._ptr(index), _C._stream(self.device)), "radegs_mesheval_nearest")
+        _call("radegs_mesheval_nearest", self.device, self.n, self.ws, self.origin, self.cell, Q, q, float(max_dist), dist, index)
         return dist, index
 
 
@@ -124,13 +118,10 @@ def mean_below(dist, max_dist):
     if dist.dtype != torch.float64 or dist.dim() != 1:
         raise RuntimeError("`dist` must be a float64 vector")
     d, dev = dist.contiguous(), dist.device
-    L = _lib()
-    nbytes = L.radegs_mesheval_sum_bytes()
+    nbytes = _lib().radegs_mesheval_sum_bytes()
     ws = gh.workspace(nbytes, dev)
     out = torch.empty(2, dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        gh.check(L.radegs_mesheval_sum_below(d.shape[0], _C._ptr(d), float(max_dist), _C._ptr(ws), nbytes, _C._ptr(out), _C._stream(dev)),
-                 "radegs_mesheval_sum_below")
+    _call("radegs_mesheval_sum_below", dev, d.shape[0], d, float(max_dist), ws, nbytes, out)
     return out
 
 
@@ -158,14 +149,10 @@ def downsample_points(points, radius, perm=None, generator=None):
     grid = PointGrid(shuffled, float(radius) * CELL_SLACK)
     state = torch.zeros(N, dtype=torch.uint8, device=dev)
     undecided = torch.full((1,), N, dtype=torch.int64, device=dev).to(torch.int32)   # read as unsigned by the kernel; N < 2^32 - 65 536
-    L = _lib()
-    with torch.cuda.device(dev):
-        stream = _C._stream(dev)
-        while True:                            # no cap: a cloud ordered along a line needs as many rounds as it has points
-            gh.check(L.radegs_mesheval_thin_rounds(N, _C._ptr(grid.ws), grid.origin, grid.cell, float(radius), ROUNDS_PER_READ, _C._ptr(state),
-                                                   _C._ptr(undecided), stream), "radegs_mesheval_thin_rounds")
-            if int(undecided.item()) == 0:     # one host read per batch of rounds
-                break
+    while True:                            # no cap: a cloud ordered along a line needs as many rounds as it has points
+        _call("radegs_mesheval_thin_rounds", dev, N, grid.ws, grid.origin, grid.cell, float(radius), ROUNDS_PER_READ, state, undecided)
+        if int(undecided.item()) == 0:     # one host read per batch of rounds
+            break
     keep = state == 1
     return shuffled[keep], keep, perm
 
@@ -195,9 +182,7 @@ def obs_mask_select(points, obs_mask, BB, Res, patch=60):
     dims = (ctypes.c_int * 3)(*vol.shape)
     N = p.shape[0]
     out = torch.zeros((3, N), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        gh.check(_lib().radegs_mesheval_obs_mask(N, _C._ptr(p), box, dims, _C._ptr(vol), _C._ptr(out[0]), _C._ptr(out[1]), _C._ptr(out[2]), _C._stream(dev)),
-                 "radegs_mesheval_obs_mask")
+    _call("radegs_mesheval_obs_mask", dev, N, p, box, dims, vol, out[0], out[1], out[2])
     return out[0].bool(), out[1].bool(), out[2].bool()
 
 
@@ -209,8 +194,7 @@ def above_plane(points, plane):
     if pl.shape != (4,) or not np.isfinite(pl).all():
         raise RuntimeError("`plane` must hold four finite numbers")
     out = torch.zeros(p.shape[0], dtype=torch.uint8, device=p.device)
-    with torch.cuda.device(p.device):
-        gh.check(_lib().radegs_mesheval_above_plane(p.shape[0], _C._ptr(p), gh.doubles(pl), _C._ptr(out), _C._stream(p.device)), "radegs_mesheval_above_plane")
+    _call("radegs_mesheval_above_plane", p.device, p.shape[0], p, gh.doubles(pl), out)
     return out.bool()
 
 
@@ -262,8 +246,7 @@ def dilate_mask(mask, radius=6):
     if not isinstance(radius, int) or not 0 <= radius <= 64:
         raise RuntimeError("`radius` must be an integer in [0, 64]")
     out = torch.empty_like(m)
-    with torch.cuda.device(m.device):
-        gh.check(_lib().radegs_mesheval_dilate(m.shape[1], m.shape[0], _C._ptr(m), radius, _C._ptr(out), _C._stream(m.device)), "radegs_mesheval_dilate")
+    _call("radegs_mesheval_dilate", m.device, m.shape[1], m.shape[0], m, radius, out)
     return out.bool()
 
 
@@ -309,25 +292,19 @@ def cull_mesh(vertices, faces, cameras, masks=None, dilation=6):
         table[i].W, table[i].H, table[i].mask_offset = W, H, offset
         dilated.append(dilate_mask(m, dilation).view(torch.uint8).reshape(-1))
         offset += W * H
-    L = _lib()
     flags = torch.ones(NV, dtype=torch.int32, device=dev)
-    nbytes = L.radegs_tetmesh_filter_plan_bytes(NV, NF)
+    nbytes = _lib().radegs_tetmesh_filter_plan_bytes(NV, NF)
     ws = gh.workspace(nbytes, dev)
     counts = torch.zeros(2, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        stream = _C._stream(dev)
-        if cameras:
-            cam_dev = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
-            all_masks = torch.cat(dilated)
-            gh.check(L.radegs_mesheval_cull_vertices(NV, _C._ptr(v32), len(cameras), _C._ptr(cam_dev), _C._ptr(all_masks), _C._ptr(flags), stream),
-                     "radegs_mesheval_cull_vertices")
-        gh.check(L.radegs_tetmesh_filter_plan_flags(NV, NF, _C._ptr(flags), _C._ptr(f), _C._ptr(ws), nbytes, _C._ptr(counts), stream),
-                 "radegs_tetmesh_filter_plan_flags")
-        nv, nf = counts.tolist()               # the one host read
-        out_v = torch.empty((nv, 3), dtype=torch.float32, device=dev)
-        out_f = torch.empty((nf, 3), dtype=torch.int64, device=dev)
-        gh.check(L.radegs_tetmesh_filter_apply(NV, NF, _C._ptr(v32), _C._ptr(f), _C._ptr(ws), nv, nf, _C._ptr(out_v), _C._ptr(out_f), stream),
-                 "radegs_tetmesh_filter_apply")
+    if cameras:
+        cam_dev = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
+        all_masks = torch.cat(dilated)
+        _call("radegs_mesheval_cull_vertices", dev, NV, v32, len(cameras), cam_dev, all_masks, flags)
+    _call("radegs_tetmesh_filter_plan_flags", dev, NV, NF, flags, f, ws, nbytes, counts)
+    nv, nf = counts.tolist()               # the one host read
+    out_v = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+    out_f = torch.empty((nf, 3), dtype=torch.int64, device=dev)
+    _call("radegs_tetmesh_filter_apply", dev, NV, NF, v32, f, ws, nv, nf, out_v, out_f)
     if v_in.dtype == torch.float64:            # the kept rows of the caller's own precision
         out_v = v_in[flags.bool()]
     return out_v, out_f

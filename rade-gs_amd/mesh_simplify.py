@@ -4,6 +4,7 @@ floaters.  GPU only.  `vertices` float32 or float64 [V,3], `faces` int32 or int6
 sum runs in a fixed order, the result is rounded once to the dtype of `vertices`, and two calls return the same bits.  Open3D's rules are
 written from memory (DESIGN 11 N21 marks each); include/radegs.h, "Mesh simplification", is the specification and
 tests/simplify_restatement.py restates it in NumPy."""
+import functools
 import math
 
 import torch
@@ -30,6 +31,9 @@ _SIGNATURES = SIGNATURES
 
 def _lib():
     return gh.bind(_SIGNATURES)
+
+
+_call = functools.partial(gh.call, _SIGNATURES)
 
 
 # ------------------------------------------------------------------------- arguments -------------------------------------------------------------------------
@@ -108,17 +112,13 @@ class _Cells:
 def _cells(v64, origin, h, max_key):
     """the cells of checked, non-empty vertices; the one host read is K"""
     dev, V = v64.device, v64.shape[0]
-    L = _lib()
-    nbytes = L.radegs_simplify_cells_bytes(V)
+    nbytes = _lib().radegs_simplify_cells_bytes(V)
     ws = gh.workspace(nbytes, dev)
     c = _Cells()
     c.vertex_cell, c.order, c.cell_key = _empty(dev, V), _empty(dev, V, dtype=torch.int32), _empty(dev, V)
     c.cell_start = _empty(dev, V + 1, dtype=torch.int32)
     n = torch.zeros(1, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        gh.check(L.radegs_simplify_cells(V, _C._ptr(v64), origin[0], origin[1], origin[2], h, max_key, _C._ptr(ws), nbytes, _C._ptr(c.vertex_cell),
-                                         _C._ptr(c.order), _C._ptr(c.cell_start), _C._ptr(c.cell_key), _C._ptr(n), _C._stream(dev)),
-                 "radegs_simplify_cells")
+    _call("radegs_simplify_cells", dev, V, v64, origin[0], origin[1], origin[2], h, max_key, ws, nbytes, c.vertex_cell, c.order, c.cell_start, c.cell_key, n)
     c.K = int(n)
     return c
 
@@ -127,44 +127,34 @@ def _cell_vertices(v64, f, a64, cells, origin, h, quadric):
     """(positions float64 [K,3], attributes float64 [K,A] or None, averages float64 [K,3], quadrics float64 [K,10] or None).  No host read."""
     dev, V, F, K = v64.device, v64.shape[0], f.shape[0], cells.K
     A = 0 if a64 is None else a64.shape[1]
-    L = _lib()
-    nbytes = L.radegs_simplify_vertices_bytes(F) if quadric and F else 0
+    nbytes = _lib().radegs_simplify_vertices_bytes(F) if quadric and F else 0
     ws = gh.workspace(nbytes, dev)
     averages = _empty(dev, K, 3, dtype=torch.float64)
     attr = _empty(dev, K, A, dtype=torch.float64) if A else None
     quadrics = _empty(dev, K, 10, dtype=torch.float64) if quadric else None
     positions = _empty(dev, K, 3, dtype=torch.float64) if quadric else averages
-    with torch.cuda.device(dev):
-        gh.check(L.radegs_simplify_vertices(V, F, K, A, _C._ptr(v64), _C._ptr(f), _C._ptr(a64), _C._ptr(cells.vertex_cell), _C._ptr(cells.order),
-                                            _C._ptr(cells.cell_start), _C._ptr(cells.cell_key), origin[0], origin[1], origin[2], h, int(quadric),
-                                            _C._ptr(ws), nbytes, _C._ptr(averages), _C._ptr(attr), _C._ptr(quadrics),
-                                            _C._ptr(positions) if quadric else None, _C._stream(dev)), "radegs_simplify_vertices")
+    _call("radegs_simplify_vertices", dev, V, F, K, A, v64, f, a64, cells.vertex_cell, cells.order, cells.cell_start, cells.cell_key, origin[0], origin[1],
+          origin[2], h, int(quadric), ws, nbytes, averages, attr, quadrics, positions if quadric else None)
     return positions, attr, averages, quadrics
 
 
 def _cell_faces(f, V, cells, remove_duplicates):
     """(cell_faces int64 [F,3], remove uint8 [F]) of checked faces, F > 0.  No host read."""
     dev, F = f.device, f.shape[0]
-    L = _lib()
-    nbytes = L.radegs_simplify_faces_bytes(F) if remove_duplicates else 0
+    nbytes = _lib().radegs_simplify_faces_bytes(F) if remove_duplicates else 0
     ws = gh.workspace(nbytes, dev)
     cell_faces, remove = _empty(dev, F, 3), _empty(dev, F, dtype=torch.uint8)
-    with torch.cuda.device(dev):
-        gh.check(L.radegs_simplify_faces(V, F, cells.K, _C._ptr(f), _C._ptr(cells.vertex_cell), int(remove_duplicates), _C._ptr(ws), nbytes,
-                                         _C._ptr(cell_faces), _C._ptr(remove), _C._stream(dev)), "radegs_simplify_faces")
+    _call("radegs_simplify_faces", dev, V, F, cells.K, f, cells.vertex_cell, int(remove_duplicates), ws, nbytes, cell_faces, remove)
     return cell_faces, remove
 
 
 def _compact_plan(K, cell_faces, remove, drop_unreferenced):
     """radegs_meshclean_compact_plan on the cells and the flagged faces: (workspace, cells kept, faces kept); the one host read is the two counts"""
     dev, F = cell_faces.device, cell_faces.shape[0]
-    L = mesh_clean._lib()
-    nbytes = L.radegs_meshclean_compact_bytes(K, F)
+    nbytes = mesh_clean._lib().radegs_meshclean_compact_bytes(K, F)
     ws = gh.workspace(nbytes, dev)
     counts2 = torch.zeros(2, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        gh.check(L.radegs_meshclean_compact_plan(K, F, 0, _C._ptr(cell_faces), _C._ptr(remove), None, None, 0, int(drop_unreferenced), _C._ptr(ws), nbytes,
-                                                 _C._ptr(counts2), _C._stream(dev)), "radegs_meshclean_compact_plan")
+    mesh_clean._call("radegs_meshclean_compact_plan", dev, K, F, 0, cell_faces, remove, None, None, 0, int(drop_unreferenced), ws, nbytes, counts2)
     nv, nf = counts2.tolist()
     return ws, nv, nf
 
@@ -173,11 +163,8 @@ def _compact_apply(K, cell_faces, ws, nv, nf):
     """(kept_cells int64 [nv], faces int64 [nf,3], face_source int64 [nf]) of a plan.  No host read."""
     dev, F = cell_faces.device, cell_faces.shape[0]
     kept, out_f, source = _empty(dev, nv), _empty(dev, nf, 3), _empty(dev, nf)
-    with torch.cuda.device(dev):
-        stream = _C._stream(dev)
-        gh.check(mesh_clean._lib().radegs_meshclean_compact_apply(K, F, _C._ptr(cell_faces), _C._ptr(ws), nv, nf, _C._ptr(kept), _C._ptr(out_f), stream),
-                 "radegs_meshclean_compact_apply")
-        gh.check(_lib().radegs_simplify_face_source(K, F, _C._ptr(ws), nf, _C._ptr(source), stream), "radegs_simplify_face_source")
+    mesh_clean._call("radegs_meshclean_compact_apply", dev, K, F, cell_faces, ws, nv, nf, kept, out_f)
+    _call("radegs_simplify_face_source", dev, K, F, ws, nf, source)
     return kept, out_f, source
 
 

@@ -187,8 +187,7 @@ def _column_table(S, columns, dev):
 
 
 def _launch_unpack(records, P, S, D, table, dev):
-    with torch.cuda.device(dev):
-        gh.check(_lib().radegs_modelio_unpack(P, S, _C._ptr(records), D, _C._ptr(table), _C._stream(dev)), "radegs_modelio_unpack")
+    gh.call(_SIGNATURES, "radegs_modelio_unpack", dev, P, S, records, D, table)
 
 
 def _upload(records, dev):
@@ -233,8 +232,7 @@ def _state(xyz, features_dc, features_rest, opacity, scaling, rotation, filter_3
 
 
 def _pack(t, P, K, begin, end, out, dev):
-    with torch.cuda.device(dev):
-        gh.check(_lib().radegs_modelio_pack(P, begin, end, K, *[_C._ptr(x) for x in t], _C._ptr(out), _C._stream(dev)), "radegs_modelio_pack")
+    gh.call(_SIGNATURES, "radegs_modelio_pack", dev, P, begin, end, K, *t, out)
 
 
 @torch.no_grad()
@@ -393,9 +391,7 @@ def init_from_points(points, colors, max_sh_degree, dist2=None):
     d2 = _rows(dist2, "dist2", P, (), dev)
     new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
     st = GaussianState(pts.clone(), new(P, 1, 3), new(P, K, 3), new(P, 1), new(P, 3), new(P, 4), None)
-    with torch.cuda.device(dev):
-        gh.check(_lib().radegs_modelio_init(P, K, _C._ptr(col), _C._ptr(d2), initial_opacity(), _C._ptr(st.features_dc), _C._ptr(st.features_rest),
-                                            _C._ptr(st.opacity), _C._ptr(st.scaling), _C._ptr(st.rotation), _C._stream(dev)), "radegs_modelio_init")
+    gh.call(_SIGNATURES, "radegs_modelio_init", dev, P, K, col, d2, initial_opacity(), st.features_dc, st.features_rest, st.opacity, st.scaling, st.rotation)
     return st
 
 
@@ -411,9 +407,7 @@ def reset_opacity(opacity_raw, scaling_raw, filter_3D, zero_moments=False):
     sc, f3 = _rows(scaling_raw, "scaling_raw", P, (3,), dev), _rows(filter_3D, "filter_3D", P, (1,), dev)
     out = torch.empty_like(op)
     m, v = (torch.empty_like(op), torch.empty_like(op)) if zero_moments else (None, None)
-    with torch.cuda.device(dev):
-        gh.check(_lib().radegs_modelio_reset_opacity(P, _C._ptr(op), _C._ptr(sc), _C._ptr(f3), _C._ptr(out), _C._ptr(m), _C._ptr(v), _C._stream(dev)),
-                 "radegs_modelio_reset_opacity")
+    gh.call(_SIGNATURES, "radegs_modelio_reset_opacity", dev, P, op, sc, f3, out, m, v)
     return (out, m, v) if zero_moments else out
 
 

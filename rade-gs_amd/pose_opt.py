@@ -14,6 +14,7 @@ kernel_size > 0 makes visible.  Not covered: intrinsics, integr
 import numpy as np
 import torch
 
+import geom_host as gh
 from diff_gaussian_rasterization import _C
 
 KEEP_LAST = False   # test hook: when True the tap's backward leaves what it saw in LAST
@@ -51,14 +52,10 @@ def pose_gradient(means3D, rotations, shs, sh_degree, campos, viewmatrix, dL_dme
     if any(t.device != dev for t in (rotations, shs, gm, gr, gs, campos, viewmatrix)):
         raise RuntimeError("pose_gradient: the tensors are on different devices")
     campos, viewmatrix = campos.detach().contiguous(), viewmatrix.detach().contiguous()
-    L = _lib()
-    nbytes = L.radegs_pose_gradient_bytes(P)
+    nbytes = _lib().radegs_pose_gradient_bytes(P)
     work = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
     out = torch.empty(12, dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        _C._check(L.radegs_pose_gradient(P, M, sh_degree, _C._ptr(means3D), _C._ptr(rotations), _C._ptr(shs), _C._ptr(campos), _C._ptr(viewmatrix),
-                                         _C._ptr(gm), _C._ptr(gr), _C._ptr(gs), _C._ptr(work), nbytes, _C._ptr(out), _C._stream(dev)),
-                  "radegs_pose_gradient")
+    gh.call(_C._SIGNATURES, "radegs_pose_gradient", dev, P, M, sh_degree, means3D, rotations, shs, campos, viewmatrix, gm, gr, gs, work, nbytes, out)
     return out
 
 
@@ -147,11 +144,9 @@ class CameraPoses:
             raise RuntimeError(f"CameraPoses.step: camera {uid} has no pose gradient -- render it with pose= and run the backward first")
         cam = self.cameras[i]
         self.steps[i] += 1
-        with torch.cuda.device(self.device):
-            _C._check(_lib().radegs_pose_step(_C._ptr(self.master[i]), _C._ptr(g), _C._ptr(self.exp_avg[i]), _C._ptr(self.exp_avg_sq[i]), float(self.steps[i]),
-                                              self.lr_translation, self.lr_rotation, self.betas[0], self.betas[1], self.eps, _C._ptr(cam.projection_matrix),
-                                              _C._ptr(cam.world_view_transform), _C._ptr(cam.full_proj_transform), _C._ptr(cam.camera_center),
-                                              _C._stream(self.device)), "radegs_pose_step")
+        gh.call(_C._SIGNATURES, "radegs_pose_step", self.device, self.master[i], g, self.exp_avg[i], self.exp_avg_sq[i], float(self.steps[i]),
+                self.lr_translation, self.lr_rotation, self.betas[0], self.betas[1], self.eps, cam.projection_matrix, cam.world_view_transform,
+                cam.full_proj_transform, cam.camera_center)
         del self._delta[uid]
 
     def world_to_camera(self):

@@ -437,11 +437,8 @@ def _resize(src, size, passes, want_u8, want_float):
     out = torch.empty((h, w, C), dtype=torch.uint8, device=dev) if want_u8 else None
     image = torch.empty((min(C, 3), h, w), dtype=torch.float32, device=dev) if want_float else None
     mask = torch.empty((1, h, w), dtype=torch.float32, device=dev) if want_float and C == 4 else None
-    with torch.cuda.device(dev):
-        gh.check(_lib().radegs_sceneio_resize(H, W, C, h, w, _C._ptr(src), ctypes.byref(th) if th is not None else None,
-                                              ctypes.byref(tv) if tv is not None else None, first, rows, _C._ptr(mid),
-                                              _C._ptr(_lut(dev)) if want_float else None, _C._ptr(out), _C._ptr(image), _C._ptr(mask), _C._stream(dev)),
-                 "radegs_sceneio_resize")
+    gh.call(_SIGNATURES, "radegs_sceneio_resize", dev, H, W, C, h, w, src, ctypes.byref(th) if th is not None else None,
+            ctypes.byref(tv) if tv is not None else None, first, rows, mid, _lut(dev) if want_float else None, out, image, mask)
     return out, image, mask
 
 
@@ -473,9 +470,7 @@ def composite_rgba(pixels_u8, white_background):
     if t.data_ptr() % 16:
         t = t.clone()
     out = torch.empty(t.shape[:-1] + (3,), dtype=torch.uint8, device=t.device)
-    with torch.cuda.device(t.device):
-        gh.check(_lib().radegs_sceneio_composite(t.numel() // 4, _C._ptr(t), int(bool(white_background)), _C._ptr(out), _C._stream(t.device)),
-                 "radegs_sceneio_composite")
+    gh.call(_SIGNATURES, "radegs_sceneio_composite", t.device, t.numel() // 4, t, int(bool(white_background)), out)
     return out
 
 
@@ -487,8 +482,7 @@ def edge_map(image):
         raise RuntimeError("`image` must be float32 of shape [1, H, W] or [3, H, W]")
     x = image.contiguous()
     out = torch.empty(x.shape[1:], dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        gh.check(_lib().radegs_sceneio_edge(x.shape[0], x.shape[1], x.shape[2], _C._ptr(x), _C._ptr(out), _C._stream(x.device)), "radegs_sceneio_edge")
+    gh.call(_SIGNATURES, "radegs_sceneio_edge", x.device, x.shape[0], x.shape[1], x.shape[2], x, out)
     return out
 
 

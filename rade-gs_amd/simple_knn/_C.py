@@ -5,6 +5,7 @@ import ctypes
 
 import torch
 
+import geom_host as gh
 from diff_gaussian_rasterization import _C as _radegs
 
 _SIGNATURES = {"radegs_knn_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int]),
@@ -24,10 +25,6 @@ def distCUDA2(points):
     out = torch.empty(P, dtype=torch.float32, device=pts.device)
     if P == 0:
         return out
-    L = _lib()
-    scratch = torch.empty(L.radegs_knn_scratch_bytes(P), dtype=torch.uint8, device=pts.device)
-    with torch.cuda.device(pts.device):
-        rc = L.radegs_knn_mean_dist2(P, _radegs._ptr(pts), _radegs._ptr(scratch), _radegs._ptr(out), _radegs._stream(pts.device))
-    if rc != 0:
-        raise RuntimeError(f"radegs_knn_mean_dist2 failed ({rc})")
+    scratch = gh.workspace(_lib().radegs_knn_scratch_bytes(P), pts.device)
+    gh.call(_SIGNATURES, "radegs_knn_mean_dist2", pts.device, P, pts, scratch, out)
     return out

@@ -4,6 +4,8 @@ accumulation of evaluage_cull_alpha, the bisection along every crossing edge and
 upstream moves marching tetrahedra to the CPU to save memory; here it is a sort over the crossing edges on the device.
 The Delaunay triangulation (`cells`) is an input of every function here; delaunay.triangulate, the step that makes it
 (mesh_extract_tetrahedra.py:63), is passed on under its name."""
+import functools
+
 import numpy as np
 import torch
 
@@ -37,6 +39,9 @@ def _lib():
     return gh.bind(_SIGNATURES)
 
 
+_call = functools.partial(gh.call, _SIGNATURES)
+
+
 def _f32(t, name, shape=None):
     """a float32 GPU tensor as the kernels address it: contiguous, optionally of a given shape (-1 = any)"""
     _C._require_gpu(t, name)
@@ -66,22 +71,17 @@ def _unbatched_marching_tetrahedra(vertices, tets32, sdf, scales):
     V, T, dev = vertices.shape[0], tets32.shape[0], vertices.device
     if V >= 2 ** 31:
         raise RuntimeError("marching_tetrahedra: more than 2^31 - 1 vertices")
-    L = _lib()
-    nbytes = L.radegs_tetmesh_plan_bytes(V, T)
+    nbytes = _lib().radegs_tetmesh_plan_bytes(V, T)
     ws = gh.workspace(nbytes, dev)
     counts = torch.zeros(2, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        stream = _C._stream(dev)
-        gh.check(L.radegs_tetmesh_plan(V, T, _C._ptr(tets32), _C._ptr(sdf), _C._ptr(ws), nbytes, _C._ptr(counts), stream), "radegs_tetmesh_plan")
-        nv, nf = counts.tolist()          # the one host read: the two sizes
-        end_points = torch.empty((nv, 2, 3), dtype=torch.float32, device=dev)
-        end_sdf = torch.empty((nv, 2, 1), dtype=torch.float32, device=dev)
-        end_scales = torch.empty((nv, 2, 1), dtype=torch.float32, device=dev)
-        faces = torch.empty((nf, 3), dtype=torch.int64, device=dev)
-        interp_v = torch.empty((nv, 2), dtype=torch.int64, device=dev)
-        gh.check(L.radegs_tetmesh_emit(V, T, _C._ptr(tets32), _C._ptr(sdf), _C._ptr(vertices), _C._ptr(scales), _C._ptr(ws), nv, nf,
-                                       _C._ptr(end_points), _C._ptr(end_sdf), _C._ptr(end_scales), _C._ptr(faces), _C._ptr(interp_v), stream),
-                 "radegs_tetmesh_emit")
+    _call("radegs_tetmesh_plan", dev, V, T, tets32, sdf, ws, nbytes, counts)
+    nv, nf = counts.tolist()          # the one host read: the two sizes
+    end_points = torch.empty((nv, 2, 3), dtype=torch.float32, device=dev)
+    end_sdf = torch.empty((nv, 2, 1), dtype=torch.float32, device=dev)
+    end_scales = torch.empty((nv, 2, 1), dtype=torch.float32, device=dev)
+    faces = torch.empty((nf, 3), dtype=torch.int64, device=dev)
+    interp_v = torch.empty((nv, 2), dtype=torch.int64, device=dev)
+    _call("radegs_tetmesh_emit", dev, V, T, tets32, sdf, vertices, scales, ws, nv, nf, end_points, end_sdf, end_scales, faces, interp_v)
     return (end_points, end_sdf), end_scales, faces, interp_v
 
 
@@ -115,8 +115,7 @@ def tetra_points(xyz, scales3, rotation_raw):
     s, q = _f32(scales3, "scales", (P, 3)), _f32(rotation_raw, "rotation", (P, 4))
     pts = torch.empty((9 * P, 3), dtype=torch.float32, device=x.device)
     sc = torch.empty((9 * P, 1), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        gh.check(_lib().radegs_tetra_points(P, _C._ptr(x), _C._ptr(s), _C._ptr(q), _C._ptr(pts), _C._ptr(sc), _C._stream(x.device)), "radegs_tetra_points")
+    _call("radegs_tetra_points", x.device, P, x, s, q, pts, sc)
     return pts, sc
 
 
@@ -155,17 +154,12 @@ class CullAlpha:
         gt = getattr(view, "gt_mask", None)
         gt = None if gt is None else _f32(gt.reshape(H, W), "gt_mask", (H, W))
         extra = None if extra_mask is None else _f32(extra_mask.reshape(H, W), "extra_mask", (H, W))
-        with torch.cuda.device(self.device):
-            gh.check(_lib().radegs_cull_alpha_accumulate(self.n, _C._ptr(alpha), _C._ptr(coord), _C._ptr(mask), _C._ptr(gt), _C._ptr(extra), W, H,
-                                                         _C._ptr(self.final_sdf), _C._ptr(self.weight), _C._stream(self.device)),
-                     "radegs_cull_alpha_accumulate")
+        _call("radegs_cull_alpha_accumulate", self.device, self.n, alpha, coord, mask, gt, extra, W, H, self.final_sdf, self.weight)
 
     @torch.no_grad()
     def sdf(self):
         out = torch.empty(self.n, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            gh.check(_lib().radegs_cull_alpha_finish(self.n, _C._ptr(self.final_sdf), _C._ptr(self.weight), _C._ptr(out), _C._stream(self.device)),
-                     "radegs_cull_alpha_finish")
+        _call("radegs_cull_alpha_finish", self.device, self.n, self.final_sdf, self.weight, out)
         return out
 
 
@@ -190,9 +184,7 @@ def bisect_step(left_pts, right_pts, left_sdf, right_sdf, mid_sdf, mid_pts_out=N
             raise RuntimeError(f"`{n}` must be a contiguous float32 GPU tensor of shape {shape} (it is updated in place)")
     mid = _f32(mid_sdf.reshape(-1), "mid_sdf", (N,))
     out = torch.empty_like(left_pts) if mid_pts_out is None else mid_pts_out
-    with torch.cuda.device(left_pts.device):
-        gh.check(_lib().radegs_tetmesh_bisect(N, _C._ptr(left_pts), _C._ptr(right_pts), _C._ptr(left_sdf), _C._ptr(right_sdf), _C._ptr(mid), _C._ptr(out),
-                                              _C._stream(left_pts.device)), "radegs_tetmesh_bisect")
+    _call("radegs_tetmesh_bisect", left_pts.device, N, left_pts, right_pts, left_sdf, right_sdf, mid, out)
     return out
 
 
@@ -206,19 +198,14 @@ def filter_mesh(end_points, end_scales, points, faces):
     _C._require_gpu(faces, "faces")
     f = faces.to(torch.int64).contiguous()
     NF, dev = f.shape[0], ep.device
-    L = _lib()
-    nbytes = L.radegs_tetmesh_filter_plan_bytes(NV, NF)
+    nbytes = _lib().radegs_tetmesh_filter_plan_bytes(NV, NF)
     ws = gh.workspace(nbytes, dev)
     counts = torch.zeros(2, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        stream = _C._stream(dev)
-        gh.check(L.radegs_tetmesh_filter_plan(NV, NF, _C._ptr(ep), _C._ptr(es), _C._ptr(f), _C._ptr(ws), nbytes, _C._ptr(counts), stream),
-                 "radegs_tetmesh_filter_plan")
-        nv, nf = counts.tolist()          # the one host read
-        out_v = torch.empty((nv, 3), dtype=torch.float32, device=dev)
-        out_f = torch.empty((nf, 3), dtype=torch.int64, device=dev)
-        gh.check(L.radegs_tetmesh_filter_apply(NV, NF, _C._ptr(pts), _C._ptr(f), _C._ptr(ws), nv, nf, _C._ptr(out_v), _C._ptr(out_f), stream),
-                 "radegs_tetmesh_filter_apply")
+    _call("radegs_tetmesh_filter_plan", dev, NV, NF, ep, es, f, ws, nbytes, counts)
+    nv, nf = counts.tolist()          # the one host read
+    out_v = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+    out_f = torch.empty((nf, 3), dtype=torch.int64, device=dev)
+    _call("radegs_tetmesh_filter_apply", dev, NV, NF, pts, f, ws, nv, nf, out_v, out_f)
     return out_v, out_f
 
 

@@ -4,6 +4,7 @@ tnt_eval.evaluate -- one depth map of the mesh per camera (upstream: pyrender / 
 is float64 and pinned to a written rule set (include/radegs.h); the vertex test is float32, as upstream's.  Reading the
 trajectory, trimesh's load / merge_vertices and the forecast branch stay with the caller; Mesher.get_connected_mesh, the
 step after cull_mesh (cull_mesh.py:283), is mesh_clean's and is passed on here under the name the reference's class has it."""
+import functools
 import math
 
 import numpy as np
@@ -38,6 +39,9 @@ get_connected_mesh = mesh_clean.get_connected_mesh      # cull_mesh.py:186-202
 
 def _lib():
     return gh.bind(_SIGNATURES)
+
+
+_call = functools.partial(gh.call, _SIGNATURES)
 
 
 # ------------------------------------------------------------------------- arguments -------------------------------------------------------------------------
@@ -141,11 +145,9 @@ def _render(v64, f, w2c, H, W, K, znear, zfar, stats=None):
     nbytes = L.radegs_tntcull_render_bytes(F, B) if QUEUE_ENTRIES is None else L.radegs_tntcull_render_bytes(0, 0) + 16 * int(QUEUE_ENTRIES)
     ws = gh.workspace(nbytes, dev)
     cams = _cameras_to(dev, w2c, torch.float64)
-    with torch.cuda.device(dev):
-        stream = _C._stream(dev)
-        args = (V, F, _C._ptr(v64), _C._ptr(f), B, _C._ptr(cams), H, W, *K, znear, zfar, _C._ptr(ws), nbytes, _C._ptr(depth))
-        gh.check(L.radegs_tntcull_render_begin(*args, stream), "radegs_tntcull_render_begin")
-        gh.check(L.radegs_tntcull_render_finish(*args, _C._ptr(stats), stream), "radegs_tntcull_render_finish")
+    args = (V, F, v64, f, B, cams, H, W, *K, znear, zfar, ws, nbytes, depth)
+    _call("radegs_tntcull_render_begin", dev, *args)
+    _call("radegs_tntcull_render_finish", dev, *args, stats)
     return depth
 
 
@@ -169,9 +171,7 @@ def _count(p32, depths, w2c, K, eps, counts):
         return
     dev = p32.device
     cams = _cameras_to(dev, w2c, torch.float32)      # inverted in float64, rounded once: upstream inverts in float32
-    with torch.cuda.device(dev):
-        gh.check(_lib().radegs_tntcull_count_views(p32.shape[0], _C._ptr(p32), B, H, W, _C._ptr(depths), _C._ptr(cams), *K, eps, _C._ptr(counts),
-                                                   _C._stream(dev)), "radegs_tntcull_count_views")
+    _call("radegs_tntcull_count_views", dev, p32.shape[0], p32, B, H, W, depths, cams, *K, eps, counts)
 
 
 def _min_views(min_views):
@@ -231,19 +231,14 @@ def cull_mesh(vertices, faces, c2w, H=1080, W=1920, fx=1163.8678928442187, fy=11
         depths = _render(v64, f, render_w2c[b:b + step], H, W, K, znear, zfar)
         _count(v32, depths, test_w2c[b:b + step], K, eps, counts)
     flags = (counts >= min_views).to(torch.int32)
-    L = _lib()
-    nbytes = L.radegs_tetmesh_filter_plan_bytes(NV, NF)
+    nbytes = _lib().radegs_tetmesh_filter_plan_bytes(NV, NF)
     ws = gh.workspace(nbytes, dev)
     counts2 = torch.zeros(2, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        stream = _C._stream(dev)
-        gh.check(L.radegs_tetmesh_filter_plan_flags(NV, NF, _C._ptr(flags), _C._ptr(f), _C._ptr(ws), nbytes, _C._ptr(counts2), stream),
-                 "radegs_tetmesh_filter_plan_flags")
-        nv, nf = counts2.tolist()              # the one host read
-        out_v = torch.empty((nv, 3), dtype=torch.float32, device=dev)
-        out_f = torch.empty((nf, 3), dtype=torch.int64, device=dev)
-        gh.check(L.radegs_tetmesh_filter_apply(NV, NF, _C._ptr(v32), _C._ptr(f), _C._ptr(ws), nv, nf, _C._ptr(out_v), _C._ptr(out_f), stream),
-                 "radegs_tetmesh_filter_apply")
+    _call("radegs_tetmesh_filter_plan_flags", dev, NV, NF, flags, f, ws, nbytes, counts2)
+    nv, nf = counts2.tolist()              # the one host read
+    out_v = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+    out_f = torch.empty((nf, 3), dtype=torch.int64, device=dev)
+    _call("radegs_tetmesh_filter_apply", dev, NV, NF, v32, f, ws, nv, nf, out_v, out_f)
     if v_in.dtype == torch.float64:            # the kept rows of the caller's own precision
         out_v = v_in[flags.bool()]
     return out_v, out_f

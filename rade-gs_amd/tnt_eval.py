@@ -6,6 +6,7 @@ produces `init_transform`, is ransac_correspondence below, a deterministic RANSA
 to the scores.  estimate_normals, the coloured clouds and the plots stay with the caller; eval_tnt/cull_mesh.py is
 tnt_cull."""
 import ctypes
+import functools
 import json
 import math
 import os
@@ -41,6 +42,9 @@ def _lib():
     return gh.bind(_SIGNATURES)
 
 
+_call = functools.partial(gh.call, _SIGNATURES)
+
+
 def _matrix(transform, name="transform"):
     """a finite affine 4x4 as float64 numpy, or None"""
     if transform is None:
@@ -71,9 +75,7 @@ def mesh_points(vertices, faces):
     V, F = v.shape[0], f.shape[0]
     out = torch.empty((V + F, 3), dtype=torch.float64, device=v.device)
     out[:V].copy_(v)
-    with torch.cuda.device(v.device):
-        gh.check(_lib().radegs_tnteval_centroids(V, F, _C._ptr(v), _C._ptr(f), ctypes.c_void_p(out.data_ptr() + 24 * V), _C._stream(v.device)),
-                 "radegs_tnteval_centroids")
+    _call("radegs_tnteval_centroids", v.device, V, F, v, f, ctypes.c_void_p(out.data_ptr() + 24 * V))
     return out
 
 
@@ -85,9 +87,7 @@ def transform_points(points, transform):
     if m is None:
         return p
     out = torch.empty_like(p)
-    with torch.cuda.device(p.device):
-        gh.check(_lib().radegs_tnteval_transform(p.shape[0], _C._ptr(p), gh.doubles(m[:3].reshape(-1)), _C._ptr(out), _C._stream(p.device)),
-                 "radegs_tnteval_transform")
+    _call("radegs_tnteval_transform", p.device, p.shape[0], p, gh.doubles(m[:3].reshape(-1)), out)
     return out
 
 
@@ -135,9 +135,7 @@ def crop_points(points, volume, transform=None):
     u, v, w = volume.axes
     poly = torch.from_numpy(np.ascontiguousarray(volume.bounding_polygon[:, [u, v]])).to(dev)
     keep = torch.zeros(N, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        gh.check(_lib().radegs_tnteval_crop(N, _C._ptr(p), w, volume.axis_min, volume.axis_max, poly.shape[0], _C._ptr(poly), _C._ptr(keep), _C._stream(dev)),
-                 "radegs_tnteval_crop")
+    _call("radegs_tnteval_crop", dev, N, p, w, volume.axis_min, volume.axis_max, poly.shape[0], poly, keep)
     keep = keep.bool()
     return p[keep], keep
 
@@ -154,21 +152,18 @@ def voxel_down_sample(points, voxel):
     if N == 0:
         return torch.empty((0, 3), dtype=torch.float64, device=dev), torch.empty(0, dtype=torch.int32, device=dev)
     origin = (p.amin(dim=0).cpu().numpy() - 0.5 * voxel)
-    L = _lib()
-    nbytes = L.radegs_tnteval_voxel_bytes(N)
+    nbytes = _lib().radegs_tnteval_voxel_bytes(N)
     if nbytes == 0:
         gh.check(gh.ERR_TOO_LARGE, "voxel_down_sample")
     ws = gh.workspace(nbytes, dev)
     counts2 = torch.zeros(2, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        stream = _C._stream(dev)
-        gh.check(L.radegs_tnteval_voxel_plan(N, _C._ptr(p), gh.doubles(origin), voxel, _C._ptr(ws), nbytes, _C._ptr(counts2), stream), "radegs_tnteval_voxel_plan")
-        M, outside = counts2.tolist()          # the one host read
-        if outside:
-            raise RuntimeError(f"voxel_down_sample ({gh.ERR_TOO_LARGE}): the cloud spans more than 2^21 voxels of {voxel} along an axis")
-        means = torch.empty((M, 3), dtype=torch.float64, device=dev)
-        counts = torch.empty(M, dtype=torch.int32, device=dev)
-        gh.check(L.radegs_tnteval_voxel_emit(N, _C._ptr(p), _C._ptr(ws), M, _C._ptr(means), _C._ptr(counts), stream), "radegs_tnteval_voxel_emit")
+    _call("radegs_tnteval_voxel_plan", dev, N, p, gh.doubles(origin), voxel, ws, nbytes, counts2)
+    M, outside = counts2.tolist()          # the one host read
+    if outside:
+        raise RuntimeError(f"voxel_down_sample ({gh.ERR_TOO_LARGE}): the cloud spans more than 2^21 voxels of {voxel} along an axis")
+    means = torch.empty((M, 3), dtype=torch.float64, device=dev)
+    counts = torch.empty(M, dtype=torch.int32, device=dev)
+    _call("radegs_tnteval_voxel_emit", dev, N, p, ws, M, means, counts)
     return means, counts
 
 
@@ -228,20 +223,16 @@ def icp(source, target, max_dist, max_iter=20, relative_fitness=1e-6, relative_r
         return dict(transformation=T, fitness=0.0, inlier_rmse=0.0, iterations=0, history=[rec],
                     correspondence=torch.full((Q,), -1, dtype=torch.int64, device=dev))
     grid = PointGrid(tgt, cell)                      # built once; refuses a non-finite target
-    L = _lib()
-    nbytes = L.radegs_tnteval_sums_bytes()
+    nbytes = _lib().radegs_tnteval_sums_bytes()
     ws = gh.workspace(nbytes, dev)
     out = torch.empty(18, dtype=torch.float64, device=dev)
     moved = torch.empty_like(src)
     state = {}
 
     def evaluate():
-        with torch.cuda.device(dev):
-            stream = _C._stream(dev)
-            gh.check(L.radegs_tnteval_transform(Q, _C._ptr(src), gh.doubles(T[:3].reshape(-1)), _C._ptr(moved), stream), "radegs_tnteval_transform")
-            _, index = grid.nearest(moved, max_dist)
-            gh.check(L.radegs_tnteval_pair_sums(Q, _C._ptr(moved), NT, _C._ptr(tgt), _C._ptr(index), _C._ptr(ws), nbytes, _C._ptr(out), stream),
-                     "radegs_tnteval_pair_sums")
+        _call("radegs_tnteval_transform", dev, Q, src, gh.doubles(T[:3].reshape(-1)), moved)
+        _, index = grid.nearest(moved, max_dist)
+        _call("radegs_tnteval_pair_sums", dev, Q, moved, NT, tgt, index, ws, nbytes, out)
         sums = out.cpu().numpy()                     # the one host read of an evaluation
         n = int(sums[0])
         state["index"] = index
@@ -314,10 +305,8 @@ def precision_recall(dist_s, dist_t, threshold, plot_stretch=5):
     dev = d1.device
     e = torch.from_numpy(edges).to(dev)
     out = torch.empty((2, edges.shape[0]), dtype=torch.int64, device=dev)      # per side: the bins, then the count below the threshold
-    with torch.cuda.device(dev):
-        for row, d in zip(out, (d1, d2)):
-            gh.check(_lib().radegs_tnteval_histogram(d.shape[0], _C._ptr(d), edges.shape[0], _C._ptr(e), threshold, _C._ptr(row),
-                                                     ctypes.c_void_p(row.data_ptr() + 8 * (edges.shape[0] - 1)), _C._stream(dev)), "radegs_tnteval_histogram")
+    for row, d in zip(out, (d1, d2)):
+        _call("radegs_tnteval_histogram", dev, d.shape[0], d, edges.shape[0], e, threshold, row, ctypes.c_void_p(row.data_ptr() + 8 * (edges.shape[0] - 1)))
     h = out.cpu().numpy()                                                        # the one host read
     precision, recall = float(h[0, -1]) / float(len(d1)), float(h[1, -1]) / float(len(d2))
     fscore = 2 * recall * precision / (recall + precision) if recall + precision else float("nan")   # upstream divides by zero there
@@ -414,9 +403,7 @@ def ransac_correspondence(source, target, max_dist=0.2, ransac_n=6, max_iteratio
     counts = torch.empty(K, dtype=torch.int32, device=dev)
     sumsq = torch.empty(K, dtype=torch.float64, device=dev)
     out = torch.empty(15, dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        gh.check(_lib().radegs_evalio_ransac(N, _C._ptr(src), _C._ptr(tgt), max_dist, ransac_n, K, seed, _C._ptr(counts), _C._ptr(sumsq), _C._ptr(out),
-                                             _C._stream(dev)), "radegs_evalio_ransac")
+    _call("radegs_evalio_ransac", dev, N, src, tgt, max_dist, ransac_n, K, seed, counts, sumsq, out)
     o = out.cpu().numpy()                              # the one host read
     T = np.eye(4)
     T[:3] = o[:12].reshape(3, 4)

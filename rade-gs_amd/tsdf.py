@@ -4,6 +4,7 @@ hands to Open3D's VoxelBlockGrid on the CPU.  Here the volume lives on the GPU f
 has upstream's three calls (compute_unique_block_coordinates, integrate, extract_triangle_mesh), `fuse_views` is the loop around them.
 GPU only.  The specification is include/radegs.h, "TSDF fusion" (DESIGN 11 N9 says which of its points are from memory of Open3D)."""
 import ctypes
+import functools
 import math
 
 import numpy as np
@@ -32,6 +33,9 @@ _SIGNATURES = {
 
 def _lib():
     return gh.bind(_SIGNATURES)
+
+
+_call = functools.partial(gh.call, _SIGNATURES)
 
 
 def _matrix(m, name, shape):
@@ -88,20 +92,17 @@ def unique_block_coordinates(coords):
     _block_coords(coords, "coords")
     c = _on_device(coords, "coords")
     dev, n = c.device, c.shape[0]
-    L = _lib()
-    nbytes = L.radegs_tsdf_unique_bytes(n)
+    nbytes = _lib().radegs_tsdf_unique_bytes(n)
     if n and nbytes == 0:
         gh.check(gh.ERR_TOO_LARGE, "unique_block_coordinates")
     ws = gh.workspace(nbytes, dev)
     counts = torch.zeros(3, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        stream = _C._stream(dev)
-        gh.check(L.radegs_tsdf_unique_plan(n, _C._ptr(c), 0, None, _C._ptr(ws), nbytes, _C._ptr(counts), stream), "radegs_tsdf_unique_plan")
-        n_unique, _, bad = counts.tolist()          # the one host read
-        if bad:
-            _range_error("unique_block_coordinates")
-        out = torch.empty((n_unique, 3), dtype=torch.int32, device=dev)
-        gh.check(L.radegs_tsdf_unique_emit(n, _C._ptr(ws), n_unique, _C._ptr(out), stream), "radegs_tsdf_unique_emit")
+    _call("radegs_tsdf_unique_plan", dev, n, c, 0, None, ws, nbytes, counts)
+    n_unique, _, bad = counts.tolist()          # the one host read
+    if bad:
+        _range_error("unique_block_coordinates")
+    out = torch.empty((n_unique, 3), dtype=torch.int32, device=dev)
+    _call("radegs_tsdf_unique_emit", dev, n, ws, n_unique, out)
     return out
 
 
@@ -176,19 +177,15 @@ class VoxelBlockGrid:
         cam = _camera16(K, pose[:3])
         H, W = d.shape
         n = 4 * (H // 4) * (W // 4)
-        L = _lib()
-        nbytes = L.radegs_tsdf_unique_bytes(n)
+        nbytes = _lib().radegs_tsdf_unique_bytes(n)
         ws = gh.workspace(nbytes, self.device)
         counts = torch.zeros(3, dtype=torch.int64, device=self.device)
-        with torch.cuda.device(self.device):
-            stream = _C._stream(self.device)
-            gh.check(L.radegs_tsdf_touch(W, H, _C._ptr(d), cam, scale, dmax, trunc, self.block_size, _C._ptr(ws), nbytes, _C._ptr(counts), stream),
-                     "radegs_tsdf_touch")
-            n_unique, _, bad = counts.tolist()      # the one host read
-            if bad:
-                _range_error("compute_unique_block_coordinates")
-            out = torch.empty((n_unique, 3), dtype=torch.int32, device=self.device)
-            gh.check(L.radegs_tsdf_unique_emit(n, _C._ptr(ws), n_unique, _C._ptr(out), stream), "radegs_tsdf_unique_emit")
+        _call("radegs_tsdf_touch", self.device, W, H, d, cam, scale, dmax, trunc, self.block_size, ws, nbytes, counts)
+        n_unique, _, bad = counts.tolist()      # the one host read
+        if bad:
+            _range_error("compute_unique_block_coordinates")
+        out = torch.empty((n_unique, 3), dtype=torch.int32, device=self.device)
+        _call("radegs_tsdf_unique_emit", self.device, n, ws, n_unique, out)
         return out
 
     # ---------------------------------------------------------------- integrate ----------------------------------------------------------------
@@ -213,35 +210,29 @@ class VoxelBlockGrid:
         n = coords.shape[0]
         if n == 0:
             return
-        L = _lib()
-        nbytes = L.radegs_tsdf_unique_bytes(n)
+        nbytes = _lib().radegs_tsdf_unique_bytes(n)
         if nbytes == 0:
             gh.check(gh.ERR_TOO_LARGE, "integrate")
         ws = gh.workspace(nbytes, self.device)
         counts = torch.zeros(3, dtype=torch.int64, device=self.device)
-        with torch.cuda.device(self.device):
-            stream = _C._stream(self.device)
-            gh.check(L.radegs_tsdf_unique_plan(n, _C._ptr(coords), self.n, _C._ptr(self.keys), _C._ptr(ws), nbytes, _C._ptr(counts), stream),
-                     "radegs_tsdf_unique_plan")
-            n_unique, n_new, bad = counts.tolist()  # the one host read
-            if bad:
-                _range_error("integrate")
-            self._reserve(self.n + n_new)
-            keys = torch.empty(self.n + n_new, dtype=torch.int64, device=self.device)
-            slots = torch.empty(self.n + n_new, dtype=torch.int32, device=self.device)
-            active_slots = torch.empty(n_unique, dtype=torch.int32, device=self.device)
-            active_coords = torch.empty((n_unique, 3), dtype=torch.int32, device=self.device)
-            gh.check(L.radegs_tsdf_insert_apply(n, _C._ptr(ws), self.n, _C._ptr(self.keys), _C._ptr(self.slots), n_unique, n_new, _C._ptr(keys),
-                                                _C._ptr(slots), _C._ptr(active_slots), _C._ptr(active_coords), stream), "radegs_tsdf_insert_apply")
-            if n_new:                               # the new blocks' slots are one range of the storage
-                self.tsdf[self.n:self.n + n_new].zero_()
-                self.weight[self.n:self.n + n_new].zero_()
-                if self.with_color:
-                    self.color[self.n:self.n + n_new].zero_()
-            self.keys, self.slots, self.n = keys, slots, self.n + n_new
-            gh.check(L.radegs_tsdf_integrate(n_unique, _C._ptr(active_slots), _C._ptr(active_coords), self.capacity, W, H, _C._ptr(d), _C._ptr(c), cam,
-                                             scale, dmax, trunc, _C._ptr(self.tsdf), _C._ptr(self.weight), _C._ptr(self.color), stream),
-                     "radegs_tsdf_integrate")
+        _call("radegs_tsdf_unique_plan", self.device, n, coords, self.n, self.keys, ws, nbytes, counts)
+        n_unique, n_new, bad = counts.tolist()  # the one host read
+        if bad:
+            _range_error("integrate")
+        self._reserve(self.n + n_new)
+        keys = torch.empty(self.n + n_new, dtype=torch.int64, device=self.device)
+        slots = torch.empty(self.n + n_new, dtype=torch.int32, device=self.device)
+        active_slots = torch.empty(n_unique, dtype=torch.int32, device=self.device)
+        active_coords = torch.empty((n_unique, 3), dtype=torch.int32, device=self.device)
+        _call("radegs_tsdf_insert_apply", self.device, n, ws, self.n, self.keys, self.slots, n_unique, n_new, keys, slots, active_slots, active_coords)
+        if n_new:                               # the new blocks' slots are one range of the storage
+            self.tsdf[self.n:self.n + n_new].zero_()
+            self.weight[self.n:self.n + n_new].zero_()
+            if self.with_color:
+                self.color[self.n:self.n + n_new].zero_()
+        self.keys, self.slots, self.n = keys, slots, self.n + n_new
+        _call("radegs_tsdf_integrate", self.device, n_unique, active_slots, active_coords, self.capacity, W, H, d, c, cam, scale, dmax, trunc,
+              self.tsdf, self.weight, self.color)
 
     # ----------------------------------------------------------------- extract -----------------------------------------------------------------
     @torch.no_grad()
@@ -254,22 +245,17 @@ class VoxelBlockGrid:
         if self.n == 0:
             return (torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty((0, 3), dtype=torch.int64, device=dev),
                     torch.empty((0, 3), dtype=torch.float32, device=dev) if self.with_color else None)
-        L = _lib()
-        nbytes = L.radegs_tsdf_extract_bytes(self.n)
+        nbytes = _lib().radegs_tsdf_extract_bytes(self.n)
         ws = gh.workspace(nbytes, dev)
         counts = torch.zeros(2, dtype=torch.int64, device=dev)
-        with torch.cuda.device(dev):
-            stream = _C._stream(dev)
-            gh.check(L.radegs_tsdf_extract_plan(self.n, _C._ptr(self.keys), _C._ptr(self.slots), _C._ptr(self.tsdf), _C._ptr(self.weight),
-                                                float(weight_threshold), _C._ptr(ws), nbytes, _C._ptr(counts), stream), "radegs_tsdf_extract_plan")
-            V, F = counts.tolist()                  # the one host read: the two sizes
-            if V >= 2 ** 32 - 1 or F >= 2 ** 32 - 1:
-                gh.check(gh.ERR_TOO_LARGE, "extract_triangle_mesh")
-            vertices = torch.empty((V, 3), dtype=torch.float32, device=dev)
-            faces = torch.empty((F, 3), dtype=torch.int64, device=dev)
-            colors = torch.empty((V, 3), dtype=torch.float32, device=dev) if self.with_color else None
-            gh.check(L.radegs_tsdf_extract_emit(self.n, _C._ptr(self.keys), _C._ptr(self.slots), _C._ptr(self.tsdf), _C._ptr(self.color), self.voxel_size,
-                                                _C._ptr(ws), V, F, _C._ptr(vertices), _C._ptr(faces), _C._ptr(colors), stream), "radegs_tsdf_extract_emit")
+        _call("radegs_tsdf_extract_plan", dev, self.n, self.keys, self.slots, self.tsdf, self.weight, float(weight_threshold), ws, nbytes, counts)
+        V, F = counts.tolist()                  # the one host read: the two sizes
+        if V >= 2 ** 32 - 1 or F >= 2 ** 32 - 1:
+            gh.check(gh.ERR_TOO_LARGE, "extract_triangle_mesh")
+        vertices = torch.empty((V, 3), dtype=torch.float32, device=dev)
+        faces = torch.empty((F, 3), dtype=torch.int64, device=dev)
+        colors = torch.empty((V, 3), dtype=torch.float32, device=dev) if self.with_color else None
+        _call("radegs_tsdf_extract_emit", dev, self.n, self.keys, self.slots, self.tsdf, self.color, self.voxel_size, ws, V, F, vertices, faces, colors)
         return vertices, faces, colors
 
 

@@ -39,6 +39,9 @@ def _lib():
     return gh.bind(_SIGNATURES)
 
 
+_call = partial(gh.call, _SIGNATURES)
+
+
 def _host(a):
     return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
 
@@ -197,10 +200,8 @@ def fuse_samples(stack, samples, voxel_size, center, radius, contract=True, retu
     tsdf = torch.empty(M, dtype=torch.float32, device=dev)
     rgb = torch.empty((M, 3), dtype=torch.float32, device=dev) if return_rgb else None
     trunc5 = float(np.float32(5.0 * voxel_size))
-    with torch.cuda.device(dev):
-        gh.check(_lib().radegs_unbounded_fuse(M, _C._ptr(pts), _C._ptr(ax), _C._ptr(ay), _C._ptr(az), dims[0], dims[1], dims[2], mapping, stack.n,
-                                              _C._ptr(stack.table), 1 if contract else 0, float(np.float32(radius)), _floats3(center), trunc5,
-                                              _C._ptr(tsdf), _C._ptr(rgb), _C._stream(dev)), "radegs_unbounded_fuse")
+    _call("radegs_unbounded_fuse", dev, M, pts, ax, ay, az, dims[0], dims[1], dims[2], mapping, stack.n, stack.table, 1 if contract else 0,
+          float(np.float32(radius)), _floats3(center), trunc5, tsdf, rgb)
     return (tsdf, rgb) if return_rgb else tsdf
 
 
@@ -209,9 +210,8 @@ def world_points(contracted, center, radius, max_range=32.0):
     """the vertices after the weld: uncontracted, un-normalised, clamped to +-max_range; float32 [M,3] on the GPU"""
     y = gh.points(contracted, "contracted", torch.float32)
     out = torch.empty_like(y)
-    with torch.cuda.device(y.device):
-        gh.check(_lib().radegs_unbounded_uncontract(y.shape[0], _C._ptr(y), float(np.float32(gh.positive(radius, "radius"))), _floats3(center),
-                                                    gh.positive(max_range, "max_range"), _C._ptr(out), _C._stream(y.device)), "radegs_unbounded_uncontract")
+    _call("radegs_unbounded_uncontract", y.device, y.shape[0], y, float(np.float32(gh.positive(radius, "radius"))), _floats3(center),
+          gh.positive(max_range, "max_range"), out)
     return out
 
 
@@ -236,21 +236,17 @@ def dense_marching_cubes(values, ax, ay, az, lattice_offset=(0, 0, 0), G=None):
     if len(off) != 3 or min(off) < 0 or any(o + n > G for o, n in zip(off, (nx, ny, nz))) or G > 2 ** 20:
         raise RuntimeError("`lattice_offset` and `G` must satisfy 0 <= offset, offset + n <= G <= 2^20")
     v = values.detach().contiguous()
-    L = _lib()
-    nbytes = L.radegs_densemc_bytes(nx, ny, nz)
+    nbytes = _lib().radegs_densemc_bytes(nx, ny, nz)
     if nbytes == 0:
         gh.check(gh.ERR_TOO_LARGE, "dense_marching_cubes")
     ws = gh.workspace(nbytes, dev)
     counts = torch.zeros(2, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        stream = _C._stream(dev)
-        gh.check(L.radegs_densemc_plan(_C._ptr(v), nx, ny, nz, _C._ptr(ws), nbytes, _C._ptr(counts), stream), "radegs_densemc_plan")
-        V, F = counts.tolist()                      # the one host read: the two sizes
-        vertices = torch.empty((V, 3), dtype=torch.float32, device=dev)
-        keys = torch.empty(V, dtype=torch.int64, device=dev)
-        faces = torch.empty((F, 3), dtype=torch.int64, device=dev)
-        gh.check(L.radegs_densemc_emit(_C._ptr(v), _C._ptr(ax), _C._ptr(ay), _C._ptr(az), nx, ny, nz, (ctypes.c_int * 3)(*off), G, _C._ptr(ws), V, F,
-                                       _C._ptr(vertices), _C._ptr(keys), _C._ptr(faces), stream), "radegs_densemc_emit")
+    _call("radegs_densemc_plan", dev, v, nx, ny, nz, ws, nbytes, counts)
+    V, F = counts.tolist()                      # the one host read: the two sizes
+    vertices = torch.empty((V, 3), dtype=torch.float32, device=dev)
+    keys = torch.empty(V, dtype=torch.int64, device=dev)
+    faces = torch.empty((F, 3), dtype=torch.int64, device=dev)
+    _call("radegs_densemc_emit", dev, v, ax, ay, az, nx, ny, nz, (ctypes.c_int * 3)(*off), G, ws, V, F, vertices, keys, faces)
     return vertices, keys, faces
 
 

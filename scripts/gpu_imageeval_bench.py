@@ -94,7 +94,7 @@ def main():
         hip_ms2 = timed(lambda: net.forward(x, y), args.iters)          # alternated once more: the spread between two windows of the same code
         eager_ms2 = timed(lambda: eager_lpips(x, y, vgg_d, lin_d), args.iters)
 
-        L, (convs, _) = ie._lib(), net._on(dev)
+        convs, _ = net._on(dev)
         layers, h, w, tap = [], H, W, 0
         for k, (idx, cin, cout) in enumerate(ie.VGG_CONVS):
             if k == 0:
@@ -105,7 +105,7 @@ def main():
                 src_hip = src_eager.permute(0, 2, 3, 1).contiguous()
             dst = torch.empty(2, h, w, cout, device=dev)
             wk, bk = vgg_d[f"features.{idx}.weight"], vgg_d[f"features.{idx}.bias"]
-            ms = timed(lambda: ie._conv(L, dev, 2, h, w, cin, cout, src_hip, convs[k][0], convs[k][1], dst), args.iters)
+            ms = timed(lambda: ie._conv(dev, 2, h, w, cin, cout, src_hip, convs[k][0], convs[k][1], dst), args.iters)
             ms_eager = timed(lambda: F.relu(F.conv2d(src_eager, wk, bk, padding=1)), args.iters)
             flop = 2.0 * 2 * h * w * 9 * cin * cout
             layers.append(dict(conv=f"features.{idx}", cin=cin, cout=cout, height=h, width=w, flop=flop, hip_ms=ms, hip_tflops=flop / ms / 1e9,
